@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
-"""Headline benchmark: training images/sec on synthetic 640x192 three-frame triplets + roofline of the fused kernel.
+"""Headline benchmark: training images/sec on synthetic 640x192 three-frame triplets (+ roofline of the fused kernel with --full).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full                  # + rooflines, decoder kernels, CPU baseline
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR      # + what the last timed step computed, as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A step = one full optimizer step of BASELINE.json configs[1] (ResNet-18 depth + ResNet-18 pose, b=12 per GPU, 640x192,
 2 support frames, 4 scales, min-reprojection + automask + edge-aware smoothness, AdamW): network forward (PyTorch-ROCm),
 K0 + fused reconstruction + smoothness (HIP, this repository), backward of both, optimizer.  Inputs are resident in HBM
-before the timed region.  Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for every field).
+before the timed region.  Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for every field).  A plain run sets up,
+warms up, times the steps and prints the headline; everything else it measures (the library's per-kernel event profile of
+the timed steps and the rooflines built on it, the measured HBM ceilings, the selection-map statistics, the decoder kernels,
+the inline-prep forward and the CPU baseline) runs only with --full.
 """
 from __future__ import annotations
 
@@ -192,6 +197,24 @@ def decoder_roofline(wl, device):
     return out
 
 
+DUMP_PARAMS = 1 << 22   # parameters sampled by --dump-outputs: 16 MB of float32 (cfg 2's two networks hold ~27 M)
+
+
+def dump_outputs(out_dir: str, loss: torch.Tensor, module: torch.nn.Module) -> dict:
+    """What a caller of the timed step receives from its last step: the loss, and the parameters the optimizer step left behind —
+    all of them when they fit in DUMP_PARAMS floats, else that many at positions drawn once from a fixed seed over the parameters
+    concatenated in `named_parameters()` order (sorted, so the sample is the same for the same workload).  -> {file: shape}."""
+    import numpy as np
+    d = Path(out_dir); d.mkdir(parents=True, exist_ok=True)
+    flat = torch.cat([p.detach().reshape(-1).float() for _, p in module.named_parameters()])
+    if flat.numel() > DUMP_PARAMS:
+        idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_PARAMS].sort().values
+        flat = flat[idx.to(flat.device)]
+    arrays = {'loss': loss.detach().float().reshape(1).cpu().numpy(), 'params_sample': flat.cpu().numpy()}
+    for name, a in arrays.items(): np.save(d/f'{name}.npy', a.astype(np.float32))
+    return {f'{name}.npy': list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -199,7 +222,12 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--workload', default='cfg2', choices=sorted(WORKLOADS))
     ap.add_argument('--channels-last', action='store_true')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also measure everything beyond the headline: the per-kernel event profile of the timed steps and '
+                                                         'the rooflines, measured HBM ceilings, selection-map statistics, decoder kernels, inline-prep forward, CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline and the inline-prep forward (the last steps of '
+                                                                   'the process stay the timed ones, for profilers)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what the last one computed (its loss and a '
+                                                                        'fixed, seeded sample of the updated parameters) as DIR/<name>.npy, float32')
     ap.add_argument('--graph', action='store_true', help='capture one whole training step (networks, loss path, backward, optimizer) into a HIP graph after the warm-up and time its '
                                                           'replays: what the host has to enqueue per step drops from ~1000 launches to one (multi-GPU readiness: eight ranks\' Python '
                                                           'threads); the library\'s event profile is off in this mode, so the roofline fields are null')
@@ -317,7 +345,8 @@ def main():
             run_steps = lambda k: train_steps(model, opt, batch_fn, k)
         note(graph_note)
     note('warm-up done; timing')
-    profiled = not (args.graph and graph_note and graph_note.startswith('whole step'))
+    # --full: the library's event profile of the timed steps (HIP events around its kernels), the source of the roofline fields
+    profiled = args.full and not (args.graph and graph_note and graph_note.startswith('whole step'))
     if profiled:
         for which in range(5): _lib.lib.smd_profile_enable(which, args.steps)
     t0, c0 = time.perf_counter(), time.process_time()
@@ -330,6 +359,45 @@ def main():
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    # before anything else runs a step: the --full extras below train on
+    dumped = dump_outputs(args.dump_outputs, losses[-1], module) if (args.dump_outputs and rank == 0) else None
+    rccl_ranks = dist.get_world_size() if dist.is_initialized() else 1
+    last_loss = losses[-1].item()
+    assert last_loss == last_loss, 'loss is NaN'
+
+    n, out = len(wl['supp']), None
+    if rank == 0:
+        out = {
+            'metric': BASELINE_METRIC,
+            'value': round(wl['b']*world*args.steps/elapsed, 2), 'unit': 'images/s',
+            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(elapsed/args.steps*1e3, 3),
+            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+            'dtype': 'bf16' if wl['precision'] == 'bf16' else 'f32', 'data': 'synthetic',
+            'config': {'workload': f'{args.workload}: {wl["depth"]} depth + {wl["pose"]} pose, {wl["w"]}x{wl["h"]}, {n} supports, 4 scales, '
+                                   f'img_recon(ssim,min,automask)+disp_smooth(edges), AdamW, random init',
+                       'global_batch': wl['b']*world, 'per_gpu_batch': wl['b'], 'parallelism': f'dp{world}',
+                       'loss_dtype': 'f32', 'channels_last': args.channels_last, 'two_stream_nets': os.environ.get('SMD_OVERLAP_NETS', '1') != '0', 'final_loss': round(last_loss, 6),
+                       'rccl_ranks': rccl_ranks, 'dp_impl': (os.environ.get('SMD_DP_IMPL', 'flat') if rccl_ranks > 1 or os.environ.get('SMD_FORCE_DDP') == '1' else None),
+                       'host_enqueue_ms_per_step': round(host_enqueue/args.steps*1e3, 3), 'host_cpu_ms_per_step': round(host_cpu/args.steps*1e3, 3), 'hip_graph': graph_note,
+                       'prep_ahead': module.prep_ahead if not args.graph else 'False (forced by --graph: the prep-ahead hand-off across streams crashes hipStreamEndCapture on this stack; the default bench runs prep_ahead=pose)',
+                       'loss_path': getattr(module.backend, 'last_path', None), 'knobs': args.knob or None,
+                       'decoder_conv_routes': {'mode': args.conv_route, 'decisions': {f'{k[0]} {k[2]}->{k[3]} {k[4]}x{k[5]} b{k[1]}': (('bf16 mfma' if k[0].endswith('_bf16') else 'split-bf16 mfma') if v[0] else ('f32 mfma' if (k[3] == 16 and not k[0].endswith('_bf16')) else 'miopen')) + f' ({v[1]:.0f} vs {v[2]:.0f} us)' for k, v in sorted(_HF.conv_routes().items(), key=lambda kv: (-kv[0][4], kv[0][0]))}},
+                       'full': args.full, 'outputs_dumped': dumped},
+        }
+        note(f'timed region done: {out["value"]} img/s')
+    if args.full:
+        full_report(args, out, wl, n, rank, device, module, model, opt, batch_fn, profiled, note)
+    if rank == 0: print(json.dumps(out), flush=True)
+    if dist.is_initialized(): dist.destroy_process_group()
+
+
+def full_report(args, out, wl, n, rank, device, module, model, opt, batch_fn, profiled, note):
+    """--full: everything the headline does not need, added to `out` (rank 0) after the timed steps: the event profile of those steps
+    and the rooflines built on it, the measured HBM ceilings, the selection-map statistics of the last step, the inline-prep forward,
+    the decoder kernels and the CPU baseline."""
+    from slowtv_monodepth_amd import _lib
+    from slowtv_monodepth_amd import functional as _F
+    from slowtv_monodepth_amd.train import train_steps
     kernel_variants = (_lib.lib.smd_last_kernel_variant(0).decode() or 'unknown', _lib.lib.smd_last_kernel_variant(1).decode() or 'unknown')
     fwd_ms = collect_profile(_lib.lib, 0, args.steps); bwd_ms = collect_profile(_lib.lib, 1, args.steps)
     fwd_all_ms = collect_profile(_lib.lib, 2, args.steps); bwd_all_ms = collect_profile(_lib.lib, 3, args.steps)
@@ -347,92 +415,70 @@ def main():
         fwd_inline_ms = collect_profile(_lib.lib, 0, 8)
         _lib.lib.smd_profile_enable(0, 0)
         module.prep_ahead = ahead
-    rccl_ranks = dist.get_world_size() if dist.is_initialized() else 1
-    last_loss = losses[-1].item()
-    assert last_loss == last_loss, 'loss is NaN'
+    if rank != 0: return
+    # What the selection maps of the LAST step looked like (outside the timed region): the share of auto-masked pixels and of pixels routed to each
+    # support.  The backward's cost depends on it (a support nobody selects in a strip costs its wave nothing: the liveness table) — a bench whose
+    # masks have collapsed (cfg 4 with randomly initialised learned intrinsics: > 99 % auto-masked from the second step on) times the all-masked floor.
+    sel_stats = None
+    sel = getattr(module.backend, 'last_sel', None)
+    if sel is not None:
+        sel_stats = {'automasked_share': round((sel == 255).float().mean().item(), 4),
+                     'routed_share_per_support': [round((sel == i).float().mean().item(), 4) for i in range(n)],
+                     'dead_wave_share_per_support': {'as_the_liveness_table_sees_it': [round(v, 4) for v in _F.dead_wave_shares(sel, True, n, table_rh=16).tolist()],
+                                                     'exact_footprint': [round(v, 4) for v in _F.dead_wave_shares(sel, True, n).tolist()]}}
 
-    if rank == 0:
-        n, S = len(wl['supp']), 4
-        B_fwd, B_bwd = recon_bytes(wl['b'], wl['h'], wl['w'], n, S)
-        avg = lambda v: sum(v)/max(len(v), 1)
-        f_ms, b_ms, fa_ms, ba_ms, p_ms = avg(fwd_ms), avg(bwd_ms), avg(fwd_all_ms), avg(bwd_all_ms), avg(prep_ms)
-        copy_gbps, read_gbps = measured_hbm_ceilings(_lib.lib, device)
-        # HBM traffic cannot be measured inside this run (it needs rocprofv3 --pmc passes, which serialise the kernels): it is
-        # read from the committed summary of such passes over THIS command (scripts/pmc_traffic.sh -> profiles/traffic.json).
-        traffic, traffic_source, tj = None, None, {}
-        tf = ROOT/'profiles'/'traffic.json'
-        if tf.is_file():
-            try:
-                tj = json.loads(tf.read_text())
-                traffic = tj.get(args.workload, {}).get('recon_fwd_bytes')
-                if traffic: traffic_source = f"profiles/traffic.json ({tj.get('_source', 'rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes')})"
-            except Exception: traffic = None
-        from slowtv_monodepth_amd import functional as _F
-        tuner = _F.row_skip_tuner(torch.cuda.current_device())
-        skipping = (int(os.environ['SMD_BWD_SKIP']) >= 1) if 'SMD_BWD_SKIP' in os.environ else tuner.skip
-        k_fwd, k_bwd = kernel_variants
-        # What the selection maps of the LAST step looked like (outside the timed region): the share of auto-masked pixels and of pixels routed to each
-        # support.  The backward's cost depends on it (a support nobody selects in a strip costs its wave nothing: the liveness table) — a bench whose
-        # masks have collapsed (cfg 4 with randomly initialised learned intrinsics: > 99 % auto-masked from the second step on) times the all-masked floor.
-        sel_stats = None
-        sel = getattr(module.backend, 'last_sel', None)
-        if sel is not None:
-            sel_stats = {'automasked_share': round((sel == 255).float().mean().item(), 4),
-                         'routed_share_per_support': [round((sel == i).float().mean().item(), 4) for i in range(n)],
-                         'dead_wave_share_per_support': {'as_the_liveness_table_sees_it': [round(v, 4) for v in _F.dead_wave_shares(sel, True, n, table_rh=16).tolist()],
-                                                         'exact_footprint': [round(v, 4) for v in _F.dead_wave_shares(sel, True, n).tolist()]}}
-        out = {
-            'metric': BASELINE_METRIC,
-            'value': round(wl['b']*world*args.steps/elapsed, 2), 'unit': 'images/s',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(elapsed/args.steps*1e3, 3),
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': 'bf16' if wl['precision'] == 'bf16' else 'f32', 'data': 'synthetic',
-            'config': {'workload': f'{args.workload}: {wl["depth"]} depth + {wl["pose"]} pose, {wl["w"]}x{wl["h"]}, {n} supports, 4 scales, '
-                                   f'img_recon(ssim,min,automask)+disp_smooth(edges), AdamW, random init',
-                       'global_batch': wl['b']*world, 'per_gpu_batch': wl['b'], 'parallelism': f'dp{world}',
-                       'loss_dtype': 'f32', 'channels_last': args.channels_last, 'two_stream_nets': os.environ.get('SMD_OVERLAP_NETS', '1') != '0', 'final_loss': round(last_loss, 6),
-                       'rccl_ranks': rccl_ranks, 'dp_impl': (os.environ.get('SMD_DP_IMPL', 'flat') if rccl_ranks > 1 or os.environ.get('SMD_FORCE_DDP') == '1' else None),
-                       'host_enqueue_ms_per_step': round(host_enqueue/args.steps*1e3, 3), 'host_cpu_ms_per_step': round(host_cpu/args.steps*1e3, 3), 'hip_graph': graph_note,
-                       'prep_ahead': module.prep_ahead if not args.graph else 'False (forced by --graph: the prep-ahead hand-off across streams crashes hipStreamEndCapture on this stack; the default bench runs prep_ahead=pose)',
-                       'loss_path': getattr(module.backend, 'last_path', None), 'knobs': args.knob or None,
-                       'decoder_conv_routes': {'mode': args.conv_route, 'decisions': {f'{k[0]} {k[2]}->{k[3]} {k[4]}x{k[5]} b{k[1]}': (('bf16 mfma' if k[0].endswith('_bf16') else 'split-bf16 mfma') if v[0] else ('f32 mfma' if (k[3] == 16 and not k[0].endswith('_bf16')) else 'miopen')) + f' ({v[1]:.0f} vs {v[2]:.0f} us)' for k, v in sorted(_HF.conv_routes().items(), key=lambda kv: (-kv[0][4], kv[0][0]))}},
-                       'automasked_share': sel_stats['automasked_share'] if sel_stats else None, 'routed_share_per_support': sel_stats['routed_share_per_support'] if sel_stats else None,
-                       'dead_wave_share_per_support': sel_stats['dead_wave_share_per_support'] if sel_stats else None},
-            'roofline': {'kernel': f'{k_fwd} (disp->depth + warp + SSIM + L1 + min-reproj + automask forward in one launch; the instantiation the library reports for the last forward launch, name as rocprofv3 prints it)', 'bound': 'hbm',
-                         'achieved': round(B_fwd/(f_ms*1e-3)/1e9, 1) if f_ms else None, 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
-                         'frac': round(B_fwd/(f_ms*1e-3)/1e9/HBM_PEAK_GBPS, 4) if f_ms else None, 'traffic': traffic, 'traffic_source': traffic_source,
-                         'whole_forward_ms': round(fa_ms, 5), 'whole_forward_launches': 'the forward entry point on the critical path: k_recon_main (all 4 scales; the loss is reduced inside it by the last block; in the single-node loss path the smoothness sweep rides in the same launch as guest blocks and the weighted sum is formed in-launch)',
-                         'prep_ms': round(p_ms, 5), 'prep_launch': 'k_recon_prep (frame-only: texel repack, target window sums, identity error), enqueued on the pose network\'s side stream behind that network, i.e. under the depth network (trainer.prep_ahead)',
-                         'whole_forward_frac': round(B_fwd/(fa_ms*1e-3)/1e9/HBM_PEAK_GBPS, 4) if fa_ms else None,
-                         'forward_incl_prep_frac': round(B_fwd/((fa_ms + p_ms)*1e-3)/1e9/HBM_PEAK_GBPS, 4) if fa_ms else None,
-                         'algorithmic_bytes': B_fwd, 'avg_kernel_ms': round(f_ms, 5), 'launches_timed': len(fwd_ms),
-                         'avg_kernel_ms_inline_prep': round(avg(fwd_inline_ms), 5) if fwd_inline_ms else None,
-                         'frac_inline_prep': round(B_fwd/(avg(fwd_inline_ms)*1e-3)/1e9/HBM_PEAK_GBPS, 4) if fwd_inline_ms else None,
-                         # since round 5 the launch also carries the smoothness sweep as guest blocks (single-node loss path): `frac` stays on the reconstruction's
-                         # bytes alone (comparable with earlier rounds and with BASELINE's "fused warp+SSIM+min-reproj kernel"); this is the launch's whole algorithmic work
-                         'frac_incl_guest_smoothness_sweep': (round((B_fwd + wl['b']*wl['h']*wl['w']*17.3125)/(f_ms*1e-3)/1e9/HBM_PEAK_GBPS, 4)
-                                                              if (f_ms and str(getattr(module.backend, 'last_path', '')).startswith('single node')) else None),
-                         'guest_note': 'the forward launch also runs the smoothness sweep of handlers.disp_smooth (25.5 MB algorithmic at cfg 2: b*h*w*17.3125, SURVEY.md §8d) as guest blocks behind its own; its duration includes them',
-                         'peak_measured_copy': round(copy_gbps, 1), 'peak_measured_read': round(read_gbps, 1), 'frac_of_measured_copy': round(B_fwd/(f_ms*1e-3)/1e9/copy_gbps, 4) if f_ms else None},
-            'roofline_bwd': {'kernel': f'{k_bwd} (fused adjoint, one wave per (strip, support); the pose / intrinsics epilogue rides in the K0-adjoint launch that follows; the instantiation the library reports for the last backward launch)', 'bound': 'hbm',
-                             'row_loop': {'dead_row_skipping': skipping, 'timed': tuner.last,
-                                          'chosen_by': 'SMD_BWD_SKIP' if 'SMD_BWD_SKIP' in os.environ else 'functional.row_skip_tuner: four early backward calls of every period (16 calls, doubling up to 256 while the timings confirm the choice) alternate between the two row loops (same gradients bit for bit) with HIP events around the entry point; skipping is kept if it is more than 3 % faster (profiles/r04_skip_regimes.txt)',
-                                          'liveness_table': 'on: a backward wave whose (strip, support) no pixel selects parks zeros instead of running its row loop (the forward records, per strip and support, the columns with such a pixel)' if not any(k.startswith('bwd_live=0') for k in args.knob) else 'off (--knob bwd_live=0)'},
-                             'achieved': round(B_bwd/(b_ms*1e-3)/1e9, 1) if b_ms else None, 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
-                             'frac': round(B_bwd/(b_ms*1e-3)/1e9/HBM_PEAK_GBPS, 4) if b_ms else None,
-                             'algorithmic_bytes': B_bwd, 'avg_kernel_ms': round(b_ms, 5), 'launches_timed': len(bwd_ms),
-                             'traffic': (tj.get(args.workload, {}).get('recon_bwd_bytes') if tf.is_file() else None),
-                             'whole_backward_ms': round(ba_ms, 5), 'whole_backward_launches': 'k_recon_bwd alone (events around the fused backward\'s launch; the K0 adjoint — two launches, the first also carrying the pose epilogue through to the pose network\'s outputs and the smoothness adjoint as guest blocks — follows outside this pair)'},
-        }
-        note(f'timed region done: {out["value"]} img/s')
-        if world == 1 and profiled:
-            try: out['roofline_decoder'] = decoder_roofline(wl, device)
-            except Exception as e: out['roofline_decoder'] = {'error': f'{type(e).__name__}: {str(e)[:200]}'}
-        if world == 1 and not args.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline(wl)
-            note('cpu baseline done')
-        print(json.dumps(out), flush=True)
-    if dist.is_initialized(): dist.destroy_process_group()
+    world = out['n_gpus']
+    S = 4
+    B_fwd, B_bwd = recon_bytes(wl['b'], wl['h'], wl['w'], n, S)
+    avg = lambda v: sum(v)/max(len(v), 1)
+    f_ms, b_ms, fa_ms, ba_ms, p_ms = avg(fwd_ms), avg(bwd_ms), avg(fwd_all_ms), avg(bwd_all_ms), avg(prep_ms)
+    copy_gbps, read_gbps = measured_hbm_ceilings(_lib.lib, device)
+    # HBM traffic cannot be measured inside this run (it needs rocprofv3 --pmc passes, which serialise the kernels): it is
+    # read from the committed summary of such passes over THIS command (scripts/pmc_traffic.sh -> profiles/traffic.json).
+    traffic, traffic_source, tj = None, None, {}
+    tf = ROOT/'profiles'/'traffic.json'
+    if tf.is_file():
+        try:
+            tj = json.loads(tf.read_text())
+            traffic = tj.get(args.workload, {}).get('recon_fwd_bytes')
+            if traffic: traffic_source = f"profiles/traffic.json ({tj.get('_source', 'rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes')})"
+        except Exception: traffic = None
+    tuner = _F.row_skip_tuner(torch.cuda.current_device())
+    skipping = (int(os.environ['SMD_BWD_SKIP']) >= 1) if 'SMD_BWD_SKIP' in os.environ else tuner.skip
+    k_fwd, k_bwd = kernel_variants
+    out['config'].update({'automasked_share': sel_stats['automasked_share'] if sel_stats else None, 'routed_share_per_support': sel_stats['routed_share_per_support'] if sel_stats else None,
+                          'dead_wave_share_per_support': sel_stats['dead_wave_share_per_support'] if sel_stats else None})
+    out['roofline'] = {'kernel': f'{k_fwd} (disp->depth + warp + SSIM + L1 + min-reproj + automask forward in one launch; the instantiation the library reports for the last forward launch, name as rocprofv3 prints it)', 'bound': 'hbm',
+                       'achieved': round(B_fwd/(f_ms*1e-3)/1e9, 1) if f_ms else None, 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
+                       'frac': round(B_fwd/(f_ms*1e-3)/1e9/HBM_PEAK_GBPS, 4) if f_ms else None, 'traffic': traffic, 'traffic_source': traffic_source,
+                       'whole_forward_ms': round(fa_ms, 5), 'whole_forward_launches': 'the forward entry point on the critical path: k_recon_main (all 4 scales; the loss is reduced inside it by the last block; in the single-node loss path the smoothness sweep rides in the same launch as guest blocks and the weighted sum is formed in-launch)',
+                       'prep_ms': round(p_ms, 5), 'prep_launch': 'k_recon_prep (frame-only: texel repack, target window sums, identity error), enqueued on the pose network\'s side stream behind that network, i.e. under the depth network (trainer.prep_ahead)',
+                       'whole_forward_frac': round(B_fwd/(fa_ms*1e-3)/1e9/HBM_PEAK_GBPS, 4) if fa_ms else None,
+                       'forward_incl_prep_frac': round(B_fwd/((fa_ms + p_ms)*1e-3)/1e9/HBM_PEAK_GBPS, 4) if fa_ms else None,
+                       'algorithmic_bytes': B_fwd, 'avg_kernel_ms': round(f_ms, 5), 'launches_timed': len(fwd_ms),
+                       'avg_kernel_ms_inline_prep': round(avg(fwd_inline_ms), 5) if fwd_inline_ms else None,
+                       'frac_inline_prep': round(B_fwd/(avg(fwd_inline_ms)*1e-3)/1e9/HBM_PEAK_GBPS, 4) if fwd_inline_ms else None,
+                       # since round 5 the launch also carries the smoothness sweep as guest blocks (single-node loss path): `frac` stays on the reconstruction's
+                       # bytes alone (comparable with earlier rounds and with BASELINE's "fused warp+SSIM+min-reproj kernel"); this is the launch's whole algorithmic work
+                       'frac_incl_guest_smoothness_sweep': (round((B_fwd + wl['b']*wl['h']*wl['w']*17.3125)/(f_ms*1e-3)/1e9/HBM_PEAK_GBPS, 4)
+                                                            if (f_ms and str(getattr(module.backend, 'last_path', '')).startswith('single node')) else None),
+                       'guest_note': 'the forward launch also runs the smoothness sweep of handlers.disp_smooth (25.5 MB algorithmic at cfg 2: b*h*w*17.3125, SURVEY.md §8d) as guest blocks behind its own; its duration includes them',
+                       'peak_measured_copy': round(copy_gbps, 1), 'peak_measured_read': round(read_gbps, 1), 'frac_of_measured_copy': round(B_fwd/(f_ms*1e-3)/1e9/copy_gbps, 4) if f_ms else None}
+    out['roofline_bwd'] = {'kernel': f'{k_bwd} (fused adjoint, one wave per (strip, support); the pose / intrinsics epilogue rides in the K0-adjoint launch that follows; the instantiation the library reports for the last backward launch)', 'bound': 'hbm',
+                           'row_loop': {'dead_row_skipping': skipping, 'timed': tuner.last,
+                                        'chosen_by': 'SMD_BWD_SKIP' if 'SMD_BWD_SKIP' in os.environ else 'functional.row_skip_tuner: four early backward calls of every period (16 calls, doubling up to 256 while the timings confirm the choice) alternate between the two row loops (same gradients bit for bit) with HIP events around the entry point; skipping is kept if it is more than 3 % faster (profiles/r04_skip_regimes.txt)',
+                                        'liveness_table': 'on: a backward wave whose (strip, support) no pixel selects parks zeros instead of running its row loop (the forward records, per strip and support, the columns with such a pixel)' if not any(k.startswith('bwd_live=0') for k in args.knob) else 'off (--knob bwd_live=0)'},
+                           'achieved': round(B_bwd/(b_ms*1e-3)/1e9, 1) if b_ms else None, 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
+                           'frac': round(B_bwd/(b_ms*1e-3)/1e9/HBM_PEAK_GBPS, 4) if b_ms else None,
+                           'algorithmic_bytes': B_bwd, 'avg_kernel_ms': round(b_ms, 5), 'launches_timed': len(bwd_ms),
+                           'traffic': (tj.get(args.workload, {}).get('recon_bwd_bytes') if tf.is_file() else None),
+                           'whole_backward_ms': round(ba_ms, 5), 'whole_backward_launches': 'k_recon_bwd alone (events around the fused backward\'s launch; the K0 adjoint — two launches, the first also carrying the pose epilogue through to the pose network\'s outputs and the smoothness adjoint as guest blocks — follows outside this pair)'}
+    if world == 1 and profiled:
+        try: out['roofline_decoder'] = decoder_roofline(wl, device)
+        except Exception as e: out['roofline_decoder'] = {'error': f'{type(e).__name__}: {str(e)[:200]}'}
+    if world == 1 and not args.no_cpu_baseline:
+        out['cpu_baseline'] = cpu_baseline(wl)
+        note('cpu baseline done')
 
 
 if __name__ == '__main__':

@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT"
 # The backward picks its row loop by timing both on the live data (functional.row_skip_tuner); a profiler perturbs that timing, so the
 # traced and counter runs are pinned (SMD_BWD_SKIP) to what the un-traced bench of the same workload chose.
 for wl in cfg2 cfg4 cfg5; do
-  skip=$(python bench.py --workload $wl --no-cpu-baseline 2>/dev/null | python -c "import json,sys; print(2 if json.loads(sys.stdin.read().strip().splitlines()[-1])['roofline_bwd']['row_loop']['dead_row_skipping'] else 0)")
+  skip=$(python bench.py --workload $wl --full --no-cpu-baseline 2>/dev/null | python -c "import json,sys; print(2 if json.loads(sys.stdin.read().strip().splitlines()[-1])['roofline_bwd']['row_loop']['dead_row_skipping'] else 0)")
   echo "$wl: un-traced bench chose SMD_BWD_SKIP=$skip" | tee gpurun_out/row_loop_$wl.txt
   SMD_BWD_SKIP=$skip bash scripts/gpu_profile.sh ${tag}_$wl --workload $wl > gpurun_out/prof_${tag}_$wl.log 2>&1
   grep -m1 '"metric"' gpurun_out/prof_${tag}_$wl/bench.log | cut -c1-200

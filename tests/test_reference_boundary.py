@@ -5,6 +5,7 @@ subprocess, so that the import shim and the reference's `src` package never leak
 the fused operators are replaced by recorders, because the point is the plumbing — registry keys, constructor and call
 signatures, and that the reference's own `MonoDepthModule.forward_loss` lands in this package's handlers."""
 import json
+import os
 import re
 import subprocess
 import sys
@@ -14,6 +15,12 @@ import pytest
 
 ROOT = Path(__file__).resolve().parents[1]
 REF = Path('/root/reference')
+
+
+def reference_readable() -> bool:
+    """The checkout is there and this user may read it (`Path.is_dir` raises instead of answering where a parent directory is closed)."""
+    return os.path.isdir(REF) and os.access(REF, os.R_OK | os.X_OK)
+
 
 DRIVER = r'''
 import importlib.abc, importlib.machinery, inspect, json, sys, types
@@ -120,7 +127,7 @@ print('RESULT ' + json.dumps(out))
 '''
 
 
-@pytest.mark.skipif(not REF.is_dir(), reason='needs the reference checkout (build container only)')
+@pytest.mark.skipif(not reference_readable(), reason='needs a checkout of the reference project that this user can read (build container only)')
 def test_integration_snippet_plugs_into_the_reference(tmp_path):
     text = (ROOT/'INTEGRATION.md').read_text()
     blocks = re.findall(r'```python\n(.*?)```', text, flags=re.S)
