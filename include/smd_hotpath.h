@@ -331,6 +331,22 @@ int smd_conv3x3_mfma_bwd_data(const void* g_y, const void* wp_bwd, void* g_xp, v
 int smd_conv3x3_mfma_bwd_weight(const void* xp, const void* g_y, float* g_weight, void* workspace, size_t workspace_bytes,
                                 int B, int C, int CO, int h, int w, int pieces, void* stream);
 
+/* The ResNet encoders' 3x3 stride-1 convolutions (ABI 8; reference: the timm BasicBlock / Bottleneck built at src/networks/depth.py:95-98,
+ * src/networks/pose.py:39-41 — `nn.Conv2d(c, co, 3, 1, padding=1, bias=False)`): y (B,CO,h,w) = conv2d(x (B,C,h,w), weight (CO,C,3,3), padding = 1) with
+ * ZERO padding done inside the kernels (no padded copy of any tensor), on the same split-bf16 matrix-core kernels and the same operand images as
+ * smd_conv3x3_mfma_* above (pack with smd_conv3x3_mfma_pack, smd_conv3x3_mfma_packed_bytes(C, CO, pieces) bytes each).  fp32 tensors only: pieces 3 (or the
+ * experiment's 2); pieces 1 is SMD_E_UNSUPPORTED.  Backward: g_y (B,CO,h,w) -> g_x (B,C,h,w), the gradient of the UNPADDED input; g_weight (CO,C,3,3) from x
+ * and g_y.  Served: forward C % 16 == 0 and CO % 32 == 0; data gradient CO % 16 == 0 and C % 32 == 0; weight gradient CO % 32 == 0 (any C); anything else
+ * SMD_E_UNSUPPORTED, nothing launched.  Every call takes a workspace of smd_conv3x3z_mfma_workspace_bytes (0: sizes not served; the limits are those of
+ * smd_conv3x3_mfma_*).  Deterministic. */
+size_t smd_conv3x3z_mfma_workspace_bytes(int B, int C, int CO, int h, int w);
+int smd_conv3x3z_mfma_fwd(const float* x, const void* wp_fwd, float* y, void* workspace, size_t workspace_bytes,
+                          int B, int C, int CO, int h, int w, int pieces, void* stream);
+int smd_conv3x3z_mfma_bwd_data(const float* g_y, const void* wp_bwd, float* g_x, void* workspace, size_t workspace_bytes,
+                               int B, int C, int CO, int h, int w, int pieces, void* stream);
+int smd_conv3x3z_mfma_bwd_weight(const float* x, const float* g_y, float* g_weight, void* workspace, size_t workspace_bytes,
+                                 int B, int C, int CO, int h, int w, int pieces, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Producer side of the path: training-mode BatchNorm2d of the ResNet encoders fused with the residual add and ReLU
  * that follow it (timm resnet blocks built at src/networks/depth.py:95-98, src/networks/pose.py:39-41;

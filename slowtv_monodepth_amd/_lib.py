@@ -76,6 +76,10 @@ PROTOTYPES = {
     'smd_conv3x3_mfma_fwd': (_i, [_vp]*4 + [_sz] + [_i]*6 + [_vp]),
     'smd_conv3x3_mfma_bwd_data': (_i, [_vp]*4 + [_sz] + [_i]*6 + [_vp]),
     'smd_conv3x3_mfma_bwd_weight': (_i, [_vp]*4 + [_sz] + [_i]*6 + [_vp]),
+    'smd_conv3x3z_mfma_workspace_bytes': (_sz, [_i]*5),
+    'smd_conv3x3z_mfma_fwd': (_i, [_vp]*4 + [_sz] + [_i]*6 + [_vp]),
+    'smd_conv3x3z_mfma_bwd_data': (_i, [_vp]*4 + [_sz] + [_i]*6 + [_vp]),
+    'smd_conv3x3z_mfma_bwd_weight': (_i, [_vp]*4 + [_sz] + [_i]*6 + [_vp]),
     'smd_conv3x3_head_workspace_bytes': (_sz, [_i]*4),
     'smd_conv3x3_head_fwd': (_i, [_vp]*4 + [_i]*5 + [_vp]),
     'smd_conv3x3_head_bwd': (_i, [_vp]*8 + [_sz] + [_i]*5 + [_vp]),

@@ -882,6 +882,42 @@ int smd_conv3x3_mfma_bwd_weight(const void* xp, const void* g_y, float* g_weight
   if (workspace_bytes < smd_conv3x3_mfma_workspace_bytes(B, C, CO, h, w)) return fail(SMD_E_WORKSPACE, "workspace too small");
   return check_launch(smd::launch_conv_mfma_bwd_wgt(xp, g_y, g_weight, (float*)workspace, B, C, CO, h, w, pieces, (hipStream_t)stream), "conv3x3_mfma_bwd_weight");
 }
+// the zero-padded "same" forms (the encoders' 3x3 stride-1 convolutions): unpadded x and g_x, fp32 tensors only
+static bool mfmaz_pieces_ok(int pieces) { return pieces == 2 || pieces == 3; }
+size_t smd_conv3x3z_mfma_workspace_bytes(int B, int C, int CO, int h, int w) {   // one size for the three operators
+  if (!mfma_sizes_ok(B, C, CO, h, w)) return 0;
+  smd::set_conv_two_tiles(knob("conv_two_tiles", 0));
+  size_t n = std::max((size_t)64, smd::conv_mfma_z_split_elems(B, C, CO, h, w));
+  if (CO % 32 == 0) n = std::max(n, smd::conv_mfma_wgrad_partials(B, C, CO, h, w));
+  return align256(n*sizeof(float));
+}
+int smd_conv3x3z_mfma_fwd(const float* x, const void* wp_fwd, float* y, void* workspace, size_t workspace_bytes,
+                          int B, int C, int CO, int h, int w, int pieces, void* stream) {
+  if (!x || !wp_fwd || !y || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (!mfmaz_pieces_ok(pieces)) return fail(SMD_E_UNSUPPORTED, "the zero-padded forms take float tensors: pieces 2 or 3, not %d", pieces);
+  if (!mfma_sizes_ok(B, C, CO, h, w)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d CO=%d h=%d w=%d", B, C, CO, h, w);
+  if (C % 16 || CO % 32) return fail(SMD_E_UNSUPPORTED, "the zero-padded forward serves C %% 16 == 0 with CO %% 32 == 0, not C=%d CO=%d", C, CO);
+  if (workspace_bytes < smd_conv3x3z_mfma_workspace_bytes(B, C, CO, h, w)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return check_launch(smd::launch_conv_mfma_z_fwd(x, wp_fwd, y, (float*)workspace, B, C, CO, h, w, pieces, (hipStream_t)stream), "conv3x3z_mfma_fwd");
+}
+int smd_conv3x3z_mfma_bwd_data(const float* g_y, const void* wp_bwd, float* g_x, void* workspace, size_t workspace_bytes,
+                               int B, int C, int CO, int h, int w, int pieces, void* stream) {
+  if (!g_y || !wp_bwd || !g_x || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (!mfmaz_pieces_ok(pieces)) return fail(SMD_E_UNSUPPORTED, "the zero-padded forms take float tensors: pieces 2 or 3, not %d", pieces);
+  if (!mfma_sizes_ok(B, C, CO, h, w)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d CO=%d h=%d w=%d", B, C, CO, h, w);
+  if (CO % 16 || C % 32) return fail(SMD_E_UNSUPPORTED, "the zero-padded data gradient serves CO %% 16 == 0 with C %% 32 == 0, not C=%d CO=%d", C, CO);
+  if (workspace_bytes < smd_conv3x3z_mfma_workspace_bytes(B, C, CO, h, w)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return check_launch(smd::launch_conv_mfma_z_bwd_data(g_y, wp_bwd, g_x, (float*)workspace, B, C, CO, h, w, pieces, (hipStream_t)stream), "conv3x3z_mfma_bwd_data");
+}
+int smd_conv3x3z_mfma_bwd_weight(const float* x, const float* g_y, float* g_weight, void* workspace, size_t workspace_bytes,
+                                 int B, int C, int CO, int h, int w, int pieces, void* stream) {
+  if (!x || !g_y || !g_weight || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (!mfmaz_pieces_ok(pieces)) return fail(SMD_E_UNSUPPORTED, "the zero-padded forms take float tensors: pieces 2 or 3, not %d", pieces);
+  if (!mfma_sizes_ok(B, C, CO, h, w)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d CO=%d h=%d w=%d", B, C, CO, h, w);
+  if (CO % 32) return fail(SMD_E_UNSUPPORTED, "the zero-padded weight gradient serves CO %% 32 == 0, not C=%d CO=%d", C, CO);
+  if (workspace_bytes < smd_conv3x3z_mfma_workspace_bytes(B, C, CO, h, w)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return check_launch(smd::launch_conv_mfma_z_bwd_wgt(x, g_y, g_weight, (float*)workspace, B, C, CO, h, w, pieces, (hipStream_t)stream), "conv3x3z_mfma_bwd_weight");
+}
 int smd_elu_up_cat_pad_fwd(const void* a, const float* bias, const void* skip, void* out, int B, int Ca, int Cs, int h, int w, int dtypes, void* stream) {
   if (!a || !out || (Cs > 0 && !skip)) return fail(SMD_E_INVALID, "null pointer");
   if (B < 1 || Ca < 1 || Cs < 0 || h < 1 || w < 1 || !dec_sizes_ok((long long)B*(Ca + Cs), 2*h, 2*w))

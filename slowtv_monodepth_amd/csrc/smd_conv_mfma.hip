@@ -10,6 +10,7 @@
 // multiply-add.  Six `v_mfma_f32_32x32x16_bf16` per K step of 16 = 6/16 of the f32 MFMA's time for the same arithmetic: a ceiling of 2.67 x the fp32
 // matrix peak with fp32-class error (tests: <= 2e-6 of the tensor's max against fp64 `conv2d`, the same bound the f32-MFMA kernels are held to).
 // PIECES = 2 (three products, 16 significant bits, "better than TF32") exists as an experiment knob only; PIECES = 1 is plain bf16.
+// Round 7: the same kernels serve the ResNet encoders' zero-padded 3x3 stride-1 layers (OFF = 1 below, k_conv_wgrad_dma's ZP form; profiles/r07_encoder_convs.txt).
 //
 // Forward and data gradient are one kernel (implicit GEMM, M = output channels, N = pixels, K = (tap, input channel)); the weight gradient is a GEMM
 // with K = pixels (M = output channels, N = input channels, one accumulator tile per tap).  Operand layouts, per `v_mfma_f32_32x32x16_bf16`:
@@ -76,8 +77,10 @@ __global__ __launch_bounds__(256) void k_conv_pack_w(const float* __restrict__ w
 }
 
 // ---- forward / data gradient ----
-// out[b][m][y][x] = sum over k < CK and taps of in[b][k][y + ky - off][x + kx - off] Wt[m][k][tap]; off = 0 for the forward (in = the reflection-padded input,
-// every read of a stored output is inside it), off = 2 for the data gradient (in = dL/dy, zero outside; out = the gradient of the PADDED input).
+// out[b][m][y][x] = sum over k < CK and taps of in[b][k][y + ky - OFF][x + kx - OFF] Wt[m][k][tap]; OFF = 0 for the forward (in = the reflection-padded input,
+// every read of a stored output is inside it), OFF = 2 for the data gradient (in = dL/dy, zero outside; out = the gradient of the PADDED input), OFF = 1 for a
+// zero-padded "same" layer (the encoders' 3x3 stride-1 convolutions: in and out both h x w, reads outside the image are zeros) — with the forward operand image
+// its forward, with the data-gradient image (flipped taps) its data gradient, which lands on the unpadded input's gradient directly.
 // A block of four waves owns 8 pixel tiles of 32 consecutive pixels (TC = 64: 4 rows x 64 columns, a wave per row; TC = 32: 8 rows x 32 columns, a wave
 // per row pair) and one tile of 32 output channels; K runs in chunks of 16 input channels x 9 taps.  Per chunk the block stages its (TRB + 2) x (TC + 2)
 // patch of the 16 channels in LDS — coalesced row pieces, split into the bf16 pieces ONCE per element (it is used by 9 taps x every output channel),
@@ -111,12 +114,13 @@ template <int TC> struct ConvTile {
 // the next 32 output channels' weights — the patch is staged once for 64 channels (by all 512 lanes).  Built to halve what a block pulls through the CU's
 // vector-memory path per MFMA; measured neutral (128 -> 64 at 48x160: 103.0 vs 104.7 us forward, 108.0 vs 104.7 data gradient; 512 -> 256 at 12x40: 183 vs 171;
 // 128 -> 64 at 24x80 data gradient 42.7 vs 52.3), so the default stays one tile per block.  Same bits either way.
-template <int TC, int P, bool BWD, typename TI, typename TO, int NM>
+template <int TC, int P, int OFF, typename TI, typename TO, int NM>
 __global__ __launch_bounds__(256*NM, 2/NM) void k_conv_mfma(const TI* __restrict__ in_, const uint4* __restrict__ wp, TO* __restrict__ out,
                                                    int CK, int M, int hi, int wi, int ho, int wo, int KS, int kc_per_split, size_t split_stride,
                                                    unsigned gx, unsigned gy, unsigned gz) {
   using T = ConvTile<TC>;
-  constexpr int NPIX = T::NPIX, PW = T::PW, off = BWD ? 2 : 0, NPROD = n_products(P);
+  constexpr int NPIX = T::NPIX, PW = T::PW, off = OFF, NPROD = n_products(P);
+  constexpr bool ZERO = OFF != 0;                                 // reads outside the image are zeros (OFF = 0: every read of a stored output is inside)
   constexpr int kBuf = P*NPIX*2;
   __shared__ uint4 tile[2*kBuf];                                  // two patches, [piece][pixel][half]
   const int lane = threadIdx.x & 63, wall = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), wv = wall & 3, mt = wall >> 2, j = lane & 31, g = lane >> 5;
@@ -139,14 +143,14 @@ __global__ __launch_bounds__(256*NM, 2/NM) void k_conv_mfma(const TI* __restrict
 
   // staging: an item = 8 channels of one patch pixel; its address inside a channel plane does not depend on the chunk
   constexpr int ITEMS = 2*NPIX, TRIPS = (ITEMS + NT - 1)/NT;
-  int pofs[TRIPS];                                               // offset inside the plane, or -1: outside (data gradient: zero)
+  int pofs[TRIPS];                                               // offset inside the plane, or -1: outside (OFF = 1, 2: zero)
 #pragma unroll
   for (int t = 0; t < TRIPS; ++t) {
     const int item = min(t*NT + (int)threadIdx.x, ITEMS - 1);
     const int half = item >= NPIX ? 1 : 0, pix = item - half*NPIX;
     const int r = pix/PW, cc = pix - r*PW;
     const int yy = y0 + r - off, xx = x0 + cc - off;
-    if (BWD) pofs[t] = (yy >= 0 && yy < hi && xx >= 0 && xx < wi) ? yy*wi + xx : -1;
+    if (ZERO) pofs[t] = (yy >= 0 && yy < hi && xx >= 0 && xx < wi) ? yy*wi + xx : -1;
     else pofs[t] = min(yy, hi - 1)*wi + min(xx, wi - 1);         // (beyond the image: any valid address, those outputs are not stored)
   }
   R v[TRIPS][8];
@@ -157,7 +161,7 @@ __global__ __launch_bounds__(256*NM, 2/NM) void k_conv_mfma(const TI* __restrict
       const int half = item >= NPIX ? 1 : 0;
       const R* p = src + (size_t)(kc*16 + half*8)*plane + (size_t)max(pofs[t], 0);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) v[t][e] = (!BWD || pofs[t] >= 0) ? p[(size_t)e*plane] : R(0);
+      for (int e = 0; e < 8; ++e) v[t][e] = (!ZERO || pofs[t] >= 0) ? p[(size_t)e*plane] : R(0);
     }
   };
   auto file_trip = [&](int buf, int t) {
@@ -600,7 +604,10 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_mfma(const TI* __restrict
 // [64 input channels][36 dwords: 34 columns + 2][32 g_y channels][36: 32 columns + 4], 13.8 KB a slot — three rows in flight per block instead of one; a wave
 // splits its own slice of a row at fragment read (10 columns of its input channel, 8 of its g_y channel, the latter also split by the other channel tile's wave)
 // and keeps the g_y fragments of the two rows before in registers.
-template <int P>
+// ZP: xp is the UNPADDED input (B, C, h, w) of a zero-padded layer (the encoders' 3x3 stride-1 convolutions): column col of padded row r is input column
+// col - 1 of input row r - 1; columns outside the row carry the out-of-range offset and rows above / below the image an empty buffer resource — the DMA writes
+// zeros for both, so the block sees the zero-padded rows without a padded copy of the activation.
+template <int P, bool ZP>
 __global__ __launch_bounds__(256, 2) void k_conv_wgrad_dma(const float* __restrict__ xp, const float* __restrict__ gy, float* __restrict__ partial,
                                                         int C, int CO, int h, int w, int rows_per_block) {
   constexpr int COB = 32, CB = 64, NW = 4, NPROD = n_products(P), CS = 36, D = 4;
@@ -614,7 +621,9 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_dma(const float* __restri
   const int cg = blockIdx.z % CGRP, cog = (blockIdx.z/CGRP) % COGRP, b = blockIdx.z/(CGRP*COGRP);
   const int x0 = blockIdx.x*32, ybeg = blockIdx.y*rows_per_block, nrows = min(rows_per_block, h - ybeg), nsteps = nrows + 2;
   const int W = w + 2, H = h + 2;
-  const rsrc_t rs_x = make_rsrc(xp + (size_t)b*C*H*W, (size_t)C*H*W*4), rs_g = make_rsrc(gy + ((size_t)b*CO + (size_t)cog*COB)*h*w, (size_t)COB*h*w*4);
+  const rsrc_t rs_x = ZP ? make_rsrc(xp + (size_t)b*C*h*w, (size_t)C*h*w*4) : make_rsrc(xp + (size_t)b*C*H*W, (size_t)C*H*W*4);   // (ZP: unpadded planes)
+  const rsrc_t rs_g = make_rsrc(gy + ((size_t)b*CO + (size_t)cog*COB)*h*w, (size_t)COB*h*w*4);
+  [[maybe_unused]] const rsrc_t rs_0 = make_rsrc(xp, 0);          // (ZP: the rows above and below the image — every load out of range, zeros)
   const unsigned lds0 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)(__attribute__((address_space(3))) unsigned*)lds);
   auto dma = [&](const rsrc_t& rs, unsigned v, unsigned so, unsigned dst) {
     unsigned keep;
@@ -628,7 +637,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_dma(const float* __restri
 #pragma unroll
   for (int n = 0; n < NX; ++n) {
     const int k = n*NW + wv, d = k*64 + lane, ch = d/CS, col = d - ch*CS, c = cg*CB + ch;
-    tab[n*64] = (k < NPX && col < 34 && x0 + col < W && c < C) ? (unsigned)((c*H)*W + x0 + col)*4u : 0x80000000u;
+    if constexpr (ZP) tab[n*64] = (k < NPX && col < 34 && x0 + col >= 1 && x0 + col <= w && c < C) ? (unsigned)((c*h)*w + x0 + col - 1)*4u : 0x80000000u;
+    else tab[n*64] = (k < NPX && col < 34 && x0 + col < W && c < C) ? (unsigned)((c*H)*W + x0 + col)*4u : 0x80000000u;
   }
 #pragma unroll
   for (int n = 0; n < NG; ++n) {
@@ -637,12 +647,19 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_dma(const float* __restri
   }
   auto issue = [&](int r) {
     const unsigned base = lds0 + (unsigned)((r % D)*SLOT*4);
-    const unsigned sx = (unsigned)min(ybeg + r, H - 1)*(unsigned)W*4u, sg = (unsigned)min(ybeg + r, h - 1)*(unsigned)w*4u;
+    rsrc_t rx = rs_x;
+    unsigned sx;
+    if constexpr (ZP) {                                           // input row ybeg + r - 1; rows -1 and h are the zero rows
+      const int yx = ybeg + r - 1;
+      const bool xin = yx >= 0 && yx < h;
+      rx = xin ? rs_x : rs_0; sx = xin ? (unsigned)yx*(unsigned)w*4u : 0u;
+    } else sx = (unsigned)min(ybeg + r, H - 1)*(unsigned)W*4u;
+    const unsigned sg = (unsigned)min(ybeg + r, h - 1)*(unsigned)w*4u;
     unsigned v[NDMA];
 #pragma unroll
     for (int n = 0; n < NDMA; ++n) v[n] = tab[n*64];
 #pragma unroll
-    for (int n = 0; n < NX; ++n) { const int k = n*NW + wv; dma(rs_x, v[n], sx, base + (unsigned)(k < NPX ? k*256 : (XDW + GDW)*4)); }
+    for (int n = 0; n < NX; ++n) { const int k = n*NW + wv; dma(rx, v[n], sx, base + (unsigned)(k < NPX ? k*256 : (XDW + GDW)*4)); }
 #pragma unroll
     for (int n = 0; n < NG; ++n) { const int k = n*NW + wv; dma(rs_g, v[NX + n], sg, base + (unsigned)(k < NPG ? XDW*4 + k*256 : (XDW + GDW)*4)); }
   };
@@ -1109,17 +1126,17 @@ size_t conv_mfma_split_elems(int B, int CK, int M, int ho, int wo) {
   return s.KS > 1 ? (size_t)s.KS*s.out_elems : 0;
 }
 
-template <int P, bool BWD, typename T>
+template <int P, int OFF, typename T>
 static void launch_conv_form(const void* in, const void* wp, void* out, float* split_ws, int B, int CK, int M, int hi, int wi, int ho, int wo, hipStream_t st) {
   const ConvShape s = conv_shape(B, CK, M, ho, wo);
   const uint4* wq = (const uint4*)wp;
   const T* i_ = (const T*)in;
   T* dst = s.KS > 1 ? reinterpret_cast<T*>(split_ws) : (T*)out;    // (the kernel writes a split's partial output as fp32 whatever T)
   if (s.NM == 2) {
-    if (s.TC == 64) hipLaunchKernelGGL((k_conv_mfma<64, P, BWD, T, T, 2>), s.grid, dim3(512), 0, st, i_, wq, dst, CK, M, hi, wi, ho, wo, s.KS, s.kcs, s.out_elems, s.gx, s.gy, s.gz);
-    else hipLaunchKernelGGL((k_conv_mfma<32, P, BWD, T, T, 2>), s.grid, dim3(512), 0, st, i_, wq, dst, CK, M, hi, wi, ho, wo, s.KS, s.kcs, s.out_elems, s.gx, s.gy, s.gz);
-  } else if (s.TC == 64) hipLaunchKernelGGL((k_conv_mfma<64, P, BWD, T, T, 1>), s.grid, dim3(256), 0, st, i_, wq, dst, CK, M, hi, wi, ho, wo, s.KS, s.kcs, s.out_elems, s.gx, s.gy, s.gz);
-  else hipLaunchKernelGGL((k_conv_mfma<32, P, BWD, T, T, 1>), s.grid, dim3(256), 0, st, i_, wq, dst, CK, M, hi, wi, ho, wo, s.KS, s.kcs, s.out_elems, s.gx, s.gy, s.gz);
+    if (s.TC == 64) hipLaunchKernelGGL((k_conv_mfma<64, P, OFF, T, T, 2>), s.grid, dim3(512), 0, st, i_, wq, dst, CK, M, hi, wi, ho, wo, s.KS, s.kcs, s.out_elems, s.gx, s.gy, s.gz);
+    else hipLaunchKernelGGL((k_conv_mfma<32, P, OFF, T, T, 2>), s.grid, dim3(512), 0, st, i_, wq, dst, CK, M, hi, wi, ho, wo, s.KS, s.kcs, s.out_elems, s.gx, s.gy, s.gz);
+  } else if (s.TC == 64) hipLaunchKernelGGL((k_conv_mfma<64, P, OFF, T, T, 1>), s.grid, dim3(256), 0, st, i_, wq, dst, CK, M, hi, wi, ho, wo, s.KS, s.kcs, s.out_elems, s.gx, s.gy, s.gz);
+  else hipLaunchKernelGGL((k_conv_mfma<32, P, OFF, T, T, 1>), s.grid, dim3(256), 0, st, i_, wq, dst, CK, M, hi, wi, ho, wo, s.KS, s.kcs, s.out_elems, s.gx, s.gy, s.gz);
   if (s.KS > 1) {
     const size_t n4 = s.out_elems/4;                              // (B M ho wo is a multiple of 4: M is a multiple of 32)
     hipLaunchKernelGGL((k_conv_split_sum<T>), dim3((unsigned)((n4 + 255)/256)), dim3(256), 0, st, split_ws, (T*)out, n4, s.KS);
@@ -1136,7 +1153,7 @@ hipError_t launch_conv_mfma_fwd(const void* xp, const void* wp_fwd, void* y, flo
 #undef SMD_CALL
     return hipGetLastError();
   }
-#define SMD_CALL(P, T) launch_conv_form<P, false, T>(xp, wp_fwd, y, split_ws, B, C, CO, h + 2, w + 2, h, w, st)
+#define SMD_CALL(P, T) launch_conv_form<P, 0, T>(xp, wp_fwd, y, split_ws, B, C, CO, h + 2, w + 2, h, w, st)
   SMD_BY_PIECES(pieces, SMD_CALL);
 #undef SMD_CALL
   return hipGetLastError();
@@ -1149,7 +1166,7 @@ hipError_t launch_conv_mfma_bwd_data(const void* gy, const void* wp_bwd, void* g
 #undef SMD_CALL
     return hipGetLastError();
   }
-#define SMD_CALL(P, T) launch_conv_form<P, true, T>(gy, wp_bwd, g_xp, split_ws, B, CO, C, h, w, h + 2, w + 2, st)
+#define SMD_CALL(P, T) launch_conv_form<P, 2, T>(gy, wp_bwd, g_xp, split_ws, B, CO, C, h, w, h + 2, w + 2, st)
   SMD_BY_PIECES(pieces, SMD_CALL);
 #undef SMD_CALL
   return hipGetLastError();
@@ -1171,13 +1188,10 @@ static void launch_wgrad(const void* xp_, const void* gy_, float* partial, int B
     return;
   }
   wgrad_shape(B, C, CO, h, w, grid, rows);
-  if constexpr (std::is_same<T, float>::value) hipLaunchKernelGGL((k_conv_wgrad_dma<P>), grid, dim3(256), 0, st, xp, gy, partial, C, CO, h, w, rows);
+  if constexpr (std::is_same<T, float>::value) hipLaunchKernelGGL((k_conv_wgrad_dma<P, false>), grid, dim3(256), 0, st, xp, gy, partial, C, CO, h, w, rows);
   else hipLaunchKernelGGL((k_conv_wgrad_mfma<P, T>), grid, dim3(256), 0, st, xp, gy, partial, C, CO, h, w, rows);
 }
-hipError_t launch_conv_mfma_bwd_wgt(const void* xp, const void* gy, float* g_w, float* partial, int B, int C, int CO, int h, int w, int pieces, hipStream_t st) {
-#define SMD_CALL(P, T) launch_wgrad<P, T>(xp, gy, partial, B, C, CO, h, w, st)
-  SMD_BY_PIECES(pieces, SMD_CALL);
-#undef SMD_CALL
+static hipError_t wgrad_finalize(float* g_w, float* partial, int B, int C, int CO, int h, int w, hipStream_t st) {
   dim3 grid; int rows;
   if (CO == 16) wgrad16_shape(B, C, h, w, grid, rows); else wgrad_shape(B, C, CO, h, w, grid, rows);
   const unsigned T = grid.x*grid.y*(unsigned)B, G = wgrad_slices(T);
@@ -1189,6 +1203,45 @@ hipError_t launch_conv_mfma_bwd_wgt(const void* xp, const void* gy, float* g_w, 
     hipLaunchKernelGGL(k_conv_wgrad_finalize2, dim3(ceil_div(n, 256)), dim3(256), 0, st, slice, G, CO, C, g_w);
   }
   return hipGetLastError();
+}
+hipError_t launch_conv_mfma_bwd_wgt(const void* xp, const void* gy, float* g_w, float* partial, int B, int C, int CO, int h, int w, int pieces, hipStream_t st) {
+#define SMD_CALL(P, T) launch_wgrad<P, T>(xp, gy, partial, B, C, CO, h, w, st)
+  SMD_BY_PIECES(pieces, SMD_CALL);
+#undef SMD_CALL
+  return wgrad_finalize(g_w, partial, B, C, CO, h, w, st);
+}
+
+// ---- zero-padded "same" layers (the ResNet encoders' 3x3 stride-1 convolutions, padding 1): x (B, C, h, w) -> y (B, CO, h, w), g_y -> g_x (B, C, h, w),
+// g_w from x and g_y — no padded copy of any tensor.  fp32 tensors only (`pieces` 3, or the experiment's 2); the same operand images as the padded forms.
+#define SMD_BY_PIECES_F32(pieces, CALL) do { if ((pieces) == 3) { CALL(3); } else { CALL(2); } } while (0)
+size_t conv_mfma_z_split_elems(int B, int C, int CO, int h, int w) {
+  size_t n = 0;
+  if (C % 16 == 0 && CO % 32 == 0) n = std::max(n, conv_mfma_split_elems(B, C, CO, h, w));
+  if (CO % 16 == 0 && C % 32 == 0) n = std::max(n, conv_mfma_split_elems(B, CO, C, h, w));
+  return n;
+}
+// y = conv2d(x, w, padding = 1): C % 16 == 0, CO % 32 == 0
+hipError_t launch_conv_mfma_z_fwd(const float* x, const void* wp_fwd, float* y, float* split_ws, int B, int C, int CO, int h, int w, int pieces, hipStream_t st) {
+#define SMD_CALL(P) launch_conv_form<P, 1, float>(x, wp_fwd, y, split_ws, B, C, CO, h, w, h, w, st)
+  SMD_BY_PIECES_F32(pieces, SMD_CALL);
+#undef SMD_CALL
+  return hipGetLastError();
+}
+// g_x (B, C, h, w) from g_y (B, CO, h, w): CO % 16 == 0, C % 32 == 0
+hipError_t launch_conv_mfma_z_bwd_data(const float* gy, const void* wp_bwd, float* g_x, float* split_ws, int B, int C, int CO, int h, int w, int pieces, hipStream_t st) {
+#define SMD_CALL(P) launch_conv_form<P, 1, float>(gy, wp_bwd, g_x, split_ws, B, CO, C, h, w, h, w, st)
+  SMD_BY_PIECES_F32(pieces, SMD_CALL);
+#undef SMD_CALL
+  return hipGetLastError();
+}
+// g_w (CO, C, 3, 3): CO % 32 == 0, any C >= 1; the same launch shape and workspace as the padded form
+hipError_t launch_conv_mfma_z_bwd_wgt(const float* x, const float* gy, float* g_w, float* partial, int B, int C, int CO, int h, int w, int pieces, hipStream_t st) {
+  dim3 grid; int rows;
+  wgrad_shape(B, C, CO, h, w, grid, rows);
+#define SMD_CALL(P) hipLaunchKernelGGL((k_conv_wgrad_dma<P, true>), grid, dim3(256), 0, st, x, gy, partial, C, CO, h, w, rows)
+  SMD_BY_PIECES_F32(pieces, SMD_CALL);
+#undef SMD_CALL
+  return wgrad_finalize(g_w, partial, B, C, CO, h, w, st);
 }
 
 }  // namespace smd

@@ -279,6 +279,11 @@ size_t conv_mfma_bwd_split_elems(int B, int C, int CO, int h, int w);
 hipError_t launch_conv_mfma_fwd(const void* xp, const void* wp_fwd, void* y, float* split_ws, int B, int C, int CO, int h, int w, int pieces, hipStream_t st);
 hipError_t launch_conv_mfma_bwd_data(const void* gy, const void* wp_bwd, void* g_xp, float* split_ws, int B, int C, int CO, int h, int w, int pieces, hipStream_t st);
 hipError_t launch_conv_mfma_bwd_wgt(const void* xp, const void* gy, float* g_w, float* partial, int B, int C, int CO, int h, int w, int pieces, hipStream_t st);
+// the zero-padded "same" forms (the encoders' 3x3 stride-1 layers): unpadded x / g_x, fp32 only (pieces 3 or 2)
+size_t conv_mfma_z_split_elems(int B, int C, int CO, int h, int w);           // floats of K-split partial outputs the forward / the data gradient want
+hipError_t launch_conv_mfma_z_fwd(const float* x, const void* wp_fwd, float* y, float* split_ws, int B, int C, int CO, int h, int w, int pieces, hipStream_t st);
+hipError_t launch_conv_mfma_z_bwd_data(const float* gy, const void* wp_bwd, float* g_x, float* split_ws, int B, int C, int CO, int h, int w, int pieces, hipStream_t st);
+hipError_t launch_conv_mfma_z_bwd_wgt(const float* x, const float* gy, float* g_w, float* partial, int B, int C, int CO, int h, int w, int pieces, hipStream_t st);
 size_t decoder_bias_partials(int B, int C, int h, int w);
 hipError_t launch_elu_pad_fwd(const void* x, const float* bias, void* out, int B, int C, int h, int w, int apply_elu, int dt, hipStream_t st);
 hipError_t launch_elu_pad_bwd(const void* x, const float* bias, const void* g_out, void* g_x, float* g_bias, float* ws, int B, int C, int h, int w,

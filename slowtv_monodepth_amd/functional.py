@@ -16,7 +16,7 @@ from . import _lib
 from ._lib import FLAGS, REGR_FLAGS, SEL_MASKED, int_array, ptr_array
 from ._lib import call as _raw_call
 
-__all__ = ['conv3x3_mfma', 'conv3x3_wide', 'set_conv_route', 'conv_routes', 'loss_path_fused', 'crop_resize', 'disp_to_depth', 'image_recon_prep', 'PreparedFrames', 'image_recon_fused', 'image_recon_fused_disp', 'disp_smooth_fused', 'view_synth', 'photo_error', 'recon_reduce',
+__all__ = ['conv3x3_mfma', 'conv3x3_wide', 'conv3x3_same', 'set_conv_route', 'conv_routes', 'loss_path_fused', 'crop_resize', 'disp_to_depth', 'image_recon_prep', 'PreparedFrames', 'image_recon_fused', 'image_recon_fused_disp', 'disp_smooth_fused', 'view_synth', 'photo_error', 'recon_reduce',
            'lane_shift_selftest', 'recon_flags', 'regression_loss', 'elu_pad', 'elu_up_cat_pad', 'batch_norm_act', 'max_pool3x3s2', 'dwconv7x7', 'layer_norm_cf', 'pose_matrices', 'intrinsics', 'inv_intrinsics']
 
 
@@ -942,13 +942,23 @@ def conv_routes() -> dict:
 
 
 def _conv_static_rule(op, B, C, CO, h, w):
-    """Stand-in where nothing may be timed (graph capture): the shapes that won on an MI355X at cfg 2 (profiles/r06_decoder_convs.txt)."""
+    """Stand-in where nothing may be timed (graph capture): the shapes that won on an MI355X at cfg 2 (profiles/r06_decoder_convs.txt; the zero-padded
+    encoder layers, `*_z`: profiles/r07_encoder_convs.txt)."""
     px = B*h*w
     if op.endswith('_bf16'): return CO == 16           # (bf16 tensors: MIOpen's bf16 kernels serve the wide layers; the thin stage is the stencil-like case)
+    if op.endswith('_z'): return _conv_static_rule_z(op[:-2], B, C, CO, h, w)
     if CO == 16: return op != 'wgt'
     if op == 'fwd': return px >= 20000 and C*CO <= 128*64
     if op == 'data': return px >= 5000 and C <= 256
     return px >= 20000 and CO <= 64
+
+
+def _conv_static_rule_z(op, B, C, CO, h, w):
+    """The zero-padded encoder layers (C = CO): the kernels win 1.4-1.8 x at 64 channels and 48 x 160, 1.2-1.3 x at 128 channels and 24 x 80 with b = 24, and
+    only the weight gradient there with b = 12; from 256 channels on they are even with MIOpen or behind it (profiles/r07_encoder_convs.txt)."""
+    px = B*h*w
+    if op == 'wgt': return px >= 20000 and CO <= 128
+    return px >= 40000 and C <= 128 and CO <= 128
 
 
 def _conv_route(op, B, C, CO, h, w, run_mfma, run_ref):
@@ -976,9 +986,34 @@ def _mfma_pack(weight, C, CO, pieces, want_fwd, want_bwd):
     return wf, wb
 
 
-def _mfma_ws(B, C, CO, h, w, dev):
-    nws = _lib.lib.smd_conv3x3_mfma_workspace_bytes(B, C, CO, h, w)
+def _mfma_ws_bytes(B, C, CO, h, w, zpad):
+    return (_lib.lib.smd_conv3x3z_mfma_workspace_bytes if zpad else _lib.lib.smd_conv3x3_mfma_workspace_bytes)(B, C, CO, h, w)
+
+
+def _mfma_ws(B, C, CO, h, w, dev, zpad=False):
+    nws = _mfma_ws_bytes(B, C, CO, h, w, zpad)
     return torch.empty(max(nws, 256), device=dev, dtype=torch.uint8), nws
+
+
+def _routed(op, B, C, CO, h, w, force, run_mfma, run_ref):
+    """Whether the MFMA kernels serve this operator: always under `force` (their errors propagate); otherwise as `_conv_route` says, and where the kernel
+    path turns the shape down — sizes its workspace query refuses (0), `Unsupported` or `ValueError` from a call — the reference serves it instead."""
+    if force: return True
+    try:
+        return _conv_route(op, B, C, CO, h, w, run_mfma, run_ref)
+    except (_lib.Unsupported, ValueError):
+        _CONV_ROUTES[(op, B, C, CO, h, w)] = (False, float('nan'), float('nan'))
+        return False
+
+
+def _ran(force, run_mfma):
+    """Run the MFMA kernels; False where the kernel path turned the call down (`Unsupported`, `ValueError`) and the caller takes the reference instead
+    (under `force` the error propagates)."""
+    if force: run_mfma(); return True
+    try:
+        run_mfma(); return True
+    except (_lib.Unsupported, ValueError):
+        return False
 
 
 class _Conv3x3Wide(torch.autograd.Function):
@@ -986,40 +1021,47 @@ class _Conv3x3Wide(torch.autograd.Function):
     on the bf16 matrix cores (`smd_conv3x3_mfma_*`) or through the alternative — MIOpen, or for the 16-channel last stage in fp32 the f32-MFMA kernels
     `smd_conv3x3_thin_*` — as `_conv_route` says (`force`: always the MFMA kernels).  fp32 tensors: every operand split into three bf16 pieces, fp32-class
     results.  bfloat16 tensors (the decoder under bf16 autocast): one piece, bf16 in and out, the weights as their bf16 rounding (what autocast hands a bf16
-    convolution), fp32 accumulation and an fp32 weight gradient."""
+    convolution), fp32 accumulation and an fp32 weight gradient.
+    `zpad`: the zero-padded "same" layer instead, `F.conv2d(x, weight, padding=1)` on the UNPADDED x (the encoders' 3x3 stride-1 convolutions; fp32 only;
+    `smd_conv3x3z_mfma_*`, zero padding inside the kernels), its operators routed under op names of their own (`fwd_z`, `data_z`, `wgt_z`)."""
     @staticmethod
-    def forward(ctx, xp, weight, pieces, force):
+    def forward(ctx, xp, weight, pieces, force, zpad=False):
         xp = _check_fb('xp', xp)
-        if xp.ndim != 4 or xp.shape[2] < 3 or xp.shape[3] < 3: raise ValueError(f'expected a padded (B,C,h+2,w+2), got {tuple(xp.shape)}')
+        if zpad and xp.dtype != torch.float32: raise TypeError(f'the zero-padded convolution takes float32 tensors, got {xp.dtype}')
+        if xp.ndim != 4 or (not zpad and (xp.shape[2] < 3 or xp.shape[3] < 3)):
+            raise ValueError(f'expected {"(B,C,h,w)" if zpad else "a padded (B,C,h+2,w+2)"}, got {tuple(xp.shape)}')
         B, C, H, W = xp.shape
         if weight.ndim != 4 or tuple(weight.shape[1:]) != (C, 3, 3): raise ValueError(f'weight: expected (CO,{C},3,3), got {tuple(weight.shape)}')
         CO = weight.shape[0]
         weight = _check('weight', weight, (CO, C, 3, 3))
-        h, w, dev = H - 2, W - 2, xp.device
+        h, w, dev = (H, W, xp.device) if zpad else (H - 2, W - 2, xp.device)
         bf = xp.dtype == _BF
         if bf: pieces = 1
-        thin = CO == 16 and C in (16, 32)                   # the last stage
+        thin = CO == 16 and C in (16, 32) and not zpad      # the last stage
         fwd_ok = (C % 16 == 0 and CO % 32 == 0) or thin
         if force and not fwd_ok:
-            raise _lib.Unsupported(f'the MFMA forward serves C % 16 == 0 with CO % 32 == 0, or CO = 16 with C = 16 | 32, not C={C} CO={CO}')
-        bwd_form = (CO % 16 == 0 and C % 32 == 0) or (C == 16 and CO == 16)   # the data gradient's own operand order (what the backward kernel serves)
+            raise _lib.Unsupported(f'the MFMA forward serves C % 16 == 0 with CO % 32 == 0{"" if zpad else ", or CO = 16 with C = 16 | 32"}, not C={C} CO={CO}')
+        if not force and _mfma_ws_bytes(B, C, CO, h, w, zpad) == 0: fwd_ok = False   # (sizes the kernels do not take: the reference serves every operator)
+        bwd_form = (CO % 16 == 0 and C % 32 == 0) or (C == 16 and CO == 16 and not zpad)   # the data gradient's own operand order (what the backward kernel serves)
         y = torch.empty((B, CO, h, w), device=dev, dtype=xp.dtype)
         packed = {}
 
-        def run_mfma():
-            if 'wf' not in packed: packed['wf'], packed['wb'] = _mfma_pack(weight, C, CO, pieces, True, bwd_form)
-            ws, nws = _mfma_ws(B, C, CO, h, w, dev)
-            call('smd_conv3x3_mfma_fwd', xp.data_ptr(), packed['wf'].data_ptr(), y.data_ptr(), ws.data_ptr(), nws, B, C, CO, h, w, pieces, _stream())
+        def run_mfma():                                     # the pack included: production pays it on every call, so the A/B times it too
+            packed['wf'], packed['wb'] = _mfma_pack(weight, C, CO, pieces, True, bwd_form)
+            ws, nws = _mfma_ws(B, C, CO, h, w, dev, zpad)
+            call('smd_conv3x3z_mfma_fwd' if zpad else 'smd_conv3x3_mfma_fwd', xp.data_ptr(), packed['wf'].data_ptr(), y.data_ptr(), ws.data_ptr(), nws,
+                 B, C, CO, h, w, pieces, _stream())
 
         def run_ref():
+            if zpad: return torch.conv2d(xp, weight, None, 1, 1)
             if bf: return torch.conv2d(xp, weight.to(_BF))
             if thin: call('smd_conv3x3_thin_fwd', xp.data_ptr(), weight.data_ptr(), y.data_ptr(), B, C, h, w, _stream()); return y
             return torch.conv2d(xp, weight)
-        use = fwd_ok and (force or _conv_route('fwd_bf16' if bf else 'fwd', B, C, CO, h, w, run_mfma, run_ref))
-        if use: run_mfma()
-        else: y = run_ref()
+        op = 'fwd_z' if zpad else 'fwd_bf16' if bf else 'fwd'
+        use = fwd_ok and _routed(op, B, C, CO, h, w, force, run_mfma, run_ref)
+        if not (use and _ran(force, run_mfma)): y = run_ref()
         ctx.save_for_backward(xp, weight, packed.get('wb'))
-        ctx.pieces, ctx.force = pieces, force
+        ctx.pieces, ctx.force, ctx.zpad, ctx.served = pieces, force, zpad, force or _mfma_ws_bytes(B, C, CO, h, w, zpad) > 0
         return y
 
     @staticmethod
@@ -1027,15 +1069,18 @@ class _Conv3x3Wide(torch.autograd.Function):
         xp, weight, wp_bwd = ctx.saved_tensors
         dev = _on(xp)
         B, C, H, W = xp.shape
-        CO, pieces, force, h, w = weight.shape[0], ctx.pieces, ctx.force, H - 2, W - 2
+        zpad = ctx.zpad
+        CO, pieces, force = weight.shape[0], ctx.pieces, ctx.force
+        h, w = (H, W) if zpad else (H - 2, W - 2)
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         bf = xp.dtype == _BF
         g_y = _check_fb('grad(y)', g_y.to(xp.dtype), (B, CO, h, w))
         g_xp = g_w = None
-        thin = CO == 16 and C in (16, 32)
+        thin = CO == 16 and C in (16, 32) and not zpad
         w_ref = weight.to(_BF) if bf else weight
-        cb = lambda mask: torch.ops.aten.convolution_backward(g_y, xp, w_ref, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1, mask)
-        sfx = '_bf16' if bf else ''
+        pad = [1, 1] if zpad else [0, 0]
+        cb = lambda mask: torch.ops.aten.convolution_backward(g_y, xp, w_ref, None, [1, 1], pad, [1, 1], False, [0, 0], 1, mask)
+        sfx = '_z' if zpad else '_bf16' if bf else ''
 
         def thin_bwd(want_x, want_w):                       # the f32-MFMA kernels of the last stage (smd_conv3x3_thin_bwd; fp32 tensors only)
             gx_ = torch.empty_like(xp) if want_x else None
@@ -1051,23 +1096,24 @@ class _Conv3x3Wide(torch.autograd.Function):
 
             def run_data():
                 if packed['wb'] is None: packed['wb'] = _mfma_pack(weight, C, CO, pieces, False, True)[1]
-                ws, nws = _mfma_ws(B, C, CO, h, w, dev)
-                call('smd_conv3x3_mfma_bwd_data', g_y.data_ptr(), packed['wb'].data_ptr(), g_xp.data_ptr(), ws.data_ptr(), nws, B, C, CO, h, w, pieces, _stream())
-            ok = (CO % 16 == 0 and C % 32 == 0) or (C == 16 and CO == 16)
+                ws, nws = _mfma_ws(B, C, CO, h, w, dev, zpad)
+                call('smd_conv3x3z_mfma_bwd_data' if zpad else 'smd_conv3x3_mfma_bwd_data', g_y.data_ptr(), packed['wb'].data_ptr(), g_xp.data_ptr(), ws.data_ptr(), nws,
+                     B, C, CO, h, w, pieces, _stream())
+            ok = ctx.served and ((CO % 16 == 0 and C % 32 == 0) or (C == 16 and CO == 16 and not zpad))
             ref_data = (lambda: thin_bwd(True, False)[0]) if (thin and not bf) else (lambda: cb([True, False, False])[0])
-            if ok and (force or _conv_route('data' + sfx, B, C, CO, h, w, run_data, ref_data)): run_data()
-            else: g_xp = ref_data()                         # (also: channel counts the data-gradient kernel does not tile)
+            if not (ok and _routed('data' + sfx, B, C, CO, h, w, force, run_data, ref_data) and _ran(force, run_data)):
+                g_xp = ref_data()                           # (also: channel counts the data-gradient kernel does not tile)
         if need_w:
             g_w = torch.empty_like(weight)
 
             def run_wgt():
-                ws, nws = _mfma_ws(B, C, CO, h, w, dev)
-                call('smd_conv3x3_mfma_bwd_weight', xp.data_ptr(), g_y.data_ptr(), g_w.data_ptr(), ws.data_ptr(), nws, B, C, CO, h, w, pieces, _stream())
-            ok = CO % 32 == 0 or thin
+                ws, nws = _mfma_ws(B, C, CO, h, w, dev, zpad)
+                call('smd_conv3x3z_mfma_bwd_weight' if zpad else 'smd_conv3x3_mfma_bwd_weight', xp.data_ptr(), g_y.data_ptr(), g_w.data_ptr(), ws.data_ptr(), nws,
+                     B, C, CO, h, w, pieces, _stream())
+            ok = ctx.served and (CO % 32 == 0 or thin)
             ref_wgt = (lambda: thin_bwd(False, True)[1]) if (thin and not bf) else (lambda: cb([False, True, False])[1].float())
-            if ok and (force or _conv_route('wgt' + sfx, B, C, CO, h, w, run_wgt, ref_wgt)): run_wgt()
-            else: g_w = ref_wgt()
-        return g_xp, g_w, None, None
+            if not (ok and _routed('wgt' + sfx, B, C, CO, h, w, force, run_wgt, ref_wgt) and _ran(force, run_wgt)): g_w = ref_wgt()
+        return g_xp, g_w, None, None, None
 
 
 def conv3x3_mfma(xp, weight, pieces: int = 3):
@@ -1081,6 +1127,14 @@ def conv3x3_mfma(xp, weight, pieces: int = 3):
 def conv3x3_wide(xp, weight):
     """The same convolution, each operator through whichever of the MFMA kernels and MIOpen won this box's A/B for its shape (`_conv_route`)."""
     return _Conv3x3Wide.apply(xp, weight, 3, False)
+
+
+def conv3x3_same(x, weight):
+    """`F.conv2d(x, weight (CO,C,3,3), padding=1)`, bias-free, zero padding: the ResNet encoders' 3x3 stride-1 convolutions (the timm blocks built at
+    src/networks/depth.py:95-98, src/networks/pose.py:39-41).  x (B,C,h,w) fp32 -> (B,CO,h,w) fp32.  Each operator runs on the split-bf16 MFMA kernels
+    (`smd_conv3x3z_mfma_*`, the padding done inside them) or MIOpen, as `_conv_route` says under `fwd_z` / `data_z` / `wgt_z` (`set_conv_route('mfma')`
+    pins the kernels); channel counts or sizes the kernels do not take go to MIOpen."""
+    return _Conv3x3Wide.apply(x, weight, 3, False, True)
 
 
 class _EluUpCatPad(torch.autograd.Function):

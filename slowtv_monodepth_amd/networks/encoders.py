@@ -55,6 +55,16 @@ class BatchNormAct2d(nn.BatchNorm2d):
         return super().train(mode)
 
 
+def _conv3x3(conv: nn.Conv2d, x):
+    """A block's 3x3 convolution: the stride-1 ones on the GPU in fp32 (the fused BatchNorm's gate) through `conv3x3_same` — split-bf16 MFMA kernels with the
+    zero padding inside them, or MIOpen, per operator and shape (`functional._conv_route`); anywhere else the module itself."""
+    if (conv.stride == (1, 1) and BatchNormAct2d.fused_enabled and x.is_cuda and x.dtype == torch.float32 and conv.weight.dtype == torch.float32
+            and not torch.is_autocast_enabled() and x.is_contiguous()):
+        from .. import functional as HF
+        return HF.conv3x3_same(x, conv.weight)
+    return conv(x)
+
+
 class BasicBlock(nn.Module):
     def __init__(self, cin, cout, stride):
         super().__init__()
@@ -66,8 +76,8 @@ class BasicBlock(nn.Module):
 
     def forward(self, x):
         idt = x if self.down is None else self.down(x)
-        x = self.bn1(self.conv1(x), relu=True)
-        return self.bn2(self.conv2(x), residual=idt, relu=True)
+        x = self.bn1(_conv3x3(self.conv1, x), relu=True)
+        return self.bn2(_conv3x3(self.conv2, x), residual=idt, relu=True)
 
 
 class Bottleneck(nn.Module):
@@ -84,7 +94,7 @@ class Bottleneck(nn.Module):
     def forward(self, x):
         idt = x if self.down is None else self.down(x)
         x = self.bn1(self.conv1(x), relu=True)
-        x = self.bn2(self.conv2(x), relu=True)
+        x = self.bn2(_conv3x3(self.conv2, x), relu=True)
         return self.bn3(self.conv3(x), residual=idt, relu=True)
 
 
