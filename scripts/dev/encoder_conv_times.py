@@ -2,7 +2,8 @@
 """The ResNet encoders' 3x3 stride-1 zero-padded convolutions (C = CO, cfg 2: 640 x 192, depth net b = 12, pose net b = 24): MIOpen's fp32 forward / data
 gradient / weight gradient (whatever the library runs inside the call, its layout transposes included) against the split-bf16 MFMA kernels with the padding
 inside them (`smd_conv3x3z_mfma_*`, raw C calls; the forward also with the weight pack every call pays).  HIP events, 20 calls each, the two sides
-interleaved per operator.  (GPU box.)
+interleaved per operator.  Then the decoder's coarse wide layers in their padded form (`smd_conv3x3_mfma_*`: input already padded, the data gradient
+on the padded input) against MIOpen's unpadded conv2d of the same padded tensor.  (GPU box.)
 usage: encoder_conv_times.py [--hw 192x640] [--b 12 24]"""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -54,5 +55,30 @@ for stage, C, div in (('layer1', 64, 4), ('layer2', 128, 8), ('layer3', 256, 16)
         k_f = timeit(fwd)
         k_d = timeit(lambda: call('smd_conv3x3z_mfma_bwd_data', gy.data_ptr(), wb.data_ptr(), gx.data_ptr(), ws.data_ptr(), nws, B, C, C, h, w, 3, stream()))
         k_w = timeit(lambda: call('smd_conv3x3z_mfma_bwd_weight', x.data_ptr(), gy.data_ptr(), gw.data_ptr(), ws.data_ptr(), nws, B, C, C, h, w, 3, stream()))
+        print(f'{stage:7s} {C:4d} {h:3d}x{w:<3d} {B:3d} | {t_f:10.1f} {t_d:7.1f} {t_w:7.1f} | {k_f:13.1f} {k_d:7.1f} {k_w:7.1f} | '
+              f'{t_f/k_f:9.2f} {t_d/k_d:5.2f} {t_w/k_w:5.2f} | {nws/2**20:.0f}', flush=True)
+
+print('# decoder coarse layers, padded form (xp = B x C x (h + 2) x (w + 2)); same columns')
+for stage, C, CO, div in (('dec4', 512, 256, 32), ('dec4', 512, 256, 16), ('dec3', 256, 128, 16), ('dec3', 256, 128, 8)):
+    h, w = H//div, W//div
+    for B in args.b:
+        gen = torch.Generator(device='cuda').manual_seed(C + CO + B + h)
+        xp = torch.randn(B, C, h + 2, w + 2, device='cuda', generator=gen)
+        wt = torch.randn(CO, C, 3, 3, device='cuda', generator=gen)/(3*C**0.5)
+        gy = torch.randn(B, CO, h, w, device='cuda', generator=gen)
+        t_f = timeit(lambda: torch.conv2d(xp, wt))
+        t_d = timeit(lambda: torch.ops.aten.convolution_backward(gy, xp, wt, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1, [True, False, False]))
+        t_w = timeit(lambda: torch.ops.aten.convolution_backward(gy, xp, wt, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1, [False, True, False]))
+        nb = _lib.lib.smd_conv3x3_mfma_packed_bytes(C, CO, 3)
+        wf = torch.empty(nb, device='cuda', dtype=torch.uint8); wb = torch.empty(nb, device='cuda', dtype=torch.uint8)
+        y = torch.empty_like(gy); gx = torch.empty_like(xp); gw = torch.empty_like(wt)
+        nws = _lib.lib.smd_conv3x3_mfma_workspace_bytes(B, C, CO, h, w); ws = torch.empty(max(nws, 256), device='cuda', dtype=torch.uint8)
+
+        def fwd():
+            call('smd_conv3x3_mfma_pack', wt.data_ptr(), wf.data_ptr(), wb.data_ptr(), C, CO, 3, stream())
+            call('smd_conv3x3_mfma_fwd', xp.data_ptr(), wf.data_ptr(), y.data_ptr(), ws.data_ptr(), nws, B, C, CO, h, w, 3, stream())
+        k_f = timeit(fwd)
+        k_d = timeit(lambda: call('smd_conv3x3_mfma_bwd_data', gy.data_ptr(), wb.data_ptr(), gx.data_ptr(), ws.data_ptr(), nws, B, C, CO, h, w, 3, stream()))
+        k_w = timeit(lambda: call('smd_conv3x3_mfma_bwd_weight', xp.data_ptr(), gy.data_ptr(), gw.data_ptr(), ws.data_ptr(), nws, B, C, CO, h, w, 3, stream()))
         print(f'{stage:7s} {C:4d} {h:3d}x{w:<3d} {B:3d} | {t_f:10.1f} {t_d:7.1f} {t_w:7.1f} | {k_f:13.1f} {k_d:7.1f} {k_w:7.1f} | '
               f'{t_f/k_f:9.2f} {t_d/k_d:5.2f} {t_w/k_w:5.2f} | {nws/2**20:.0f}', flush=True)

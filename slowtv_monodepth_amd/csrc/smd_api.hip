@@ -888,7 +888,7 @@ size_t smd_conv3x3z_mfma_workspace_bytes(int B, int C, int CO, int h, int w) {  
   if (!mfma_sizes_ok(B, C, CO, h, w)) return 0;
   smd::set_conv_two_tiles(knob("conv_two_tiles", 0));
   size_t n = std::max((size_t)64, smd::conv_mfma_z_split_elems(B, C, CO, h, w));
-  if (CO % 32 == 0) n = std::max(n, smd::conv_mfma_wgrad_partials(B, C, CO, h, w));
+  if (CO % 32 == 0) n = std::max(n, smd::conv_mfma_z_wgrad_partials(B, C, CO, h, w));
   return align256(n*sizeof(float));
 }
 int smd_conv3x3z_mfma_fwd(const float* x, const void* wp_fwd, float* y, void* workspace, size_t workspace_bytes,

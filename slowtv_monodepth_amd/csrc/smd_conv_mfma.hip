@@ -109,6 +109,16 @@ template <int TC> struct ConvTile {
   static constexpr int TRB = (TC == 64) ? 4 : 8;
   static constexpr int PW = TC + 2, PH = TRB + 2, NPIX = PW*PH;
 };
+// TC = 0: ROW-BAND tiles for narrow maps (the coarse levels: 24 x 80, 12 x 40, 6 x 20 and their padded-gradient forms).  A block's 256 pixels are R whole
+// output rows of one sample, or — where a whole image is at most 128 pixels — S whole samples (R = ho); the eight fragments are 32 CONSECUTIVE pixels of
+// the band in flattened order, so a fragment may cross row ends and sample boundaries.  The patch is the band's input rows with their halos, each row
+// wo + 2 wide, and each sample's rows stacked with their own two halo rows; a lane decodes its pixel once per block and reads tap (ky, kx) at
+// lane base + ky (wo + 2) + kx.  The rectangular tiles of 64 x 4 / 32 x 8 carry 47 % useful pixels at 12 x 40 and 6 x 20 and 62.5 % at 24 x 80; bands of
+// 240 pixels (6 rows, 2 samples, 3 rows) carry 94 %.  The patch buffer is sized for the largest band patch (420 pixels: 5 x 84 at 26 x 82), 79 KB for
+// two patches — still two blocks per CU.
+template <> struct ConvTile<0> {
+  static constexpr int TRB = 0, PW = 0, NPIX = 420;
+};
 
 // NM: channel tiles per block.  NM = 2 (knob conv_two_tiles, layers with a multiple of 64 output channels): EIGHT waves, waves 4 .. 7 multiply the same patch by
 // the next 32 output channels' weights — the patch is staged once for 64 channels (by all 512 lanes).  Built to halve what a block pulls through the CU's
@@ -117,9 +127,11 @@ template <int TC> struct ConvTile {
 template <int TC, int P, int OFF, typename TI, typename TO, int NM>
 __global__ __launch_bounds__(256*NM, 2/NM) void k_conv_mfma(const TI* __restrict__ in_, const uint4* __restrict__ wp, TO* __restrict__ out,
                                                    int CK, int M, int hi, int wi, int ho, int wo, int KS, int kc_per_split, size_t split_stride,
-                                                   unsigned gx, unsigned gy, unsigned gz) {
+                                                   unsigned gx, unsigned gy, unsigned gz, int S, int B) {
   using T = ConvTile<TC>;
-  constexpr int NPIX = T::NPIX, PW = T::PW, off = OFF, NPROD = n_products(P);
+  constexpr bool BAND = TC == 0;                                  // row-band tiles: gx = R (rows of a band, BR), gy = bands per sample, gz = groups of S samples
+  constexpr int NPIX = T::NPIX, off = OFF, NPROD = n_products(P);
+  const int PW = BAND ? wo + 2 : T::PW;
   constexpr bool ZERO = OFF != 0;                                 // reads outside the image are zeros (OFF = 0: every read of a stored output is inside)
   constexpr int kBuf = P*NPIX*2;
   __shared__ uint4 tile[2*kBuf];                                  // two patches, [piece][pixel][half]
@@ -130,16 +142,33 @@ __global__ __launch_bounds__(256*NM, 2/NM) void k_conv_mfma(const TI* __restrict
   // the halo rows / columns two tiles share, and the one patch the channel tiles of a pixel tile all read, come from HBM once (the natural order sends every
   // neighbour to another L2: 329 MB fetched for a 145 MB input at cfg 2's 96 -> 32 layer).
   const int MG = M/(32*NM);
-  const unsigned nblk = (unsigned)(MG*KS)*gx*gy*gz, per = (nblk + 7)/8;
+  const unsigned nblk = (unsigned)(MG*KS)*(BAND ? 1u : gx)*gy*gz, per = (nblk + 7)/8;
   const unsigned lid = (blockIdx.x & 7)*per + (blockIdx.x >> 3);
   if (lid >= nblk) return;
   const int mg = (int)(lid % MG)*NM + mt, ks = (lid/MG) % KS;     // mg: this wave's tile of 32 output channels
   const unsigned tl = lid/(MG*KS);
-  const int x0 = (int)(tl % gx)*TC, y0 = (int)((tl/gx) % gy)*T::TRB, b = (int)(tl/(gx*gy));
+  const int BR = BAND ? (int)gx : 0, SEGP = (BR + 2)*PW;            // (band: a sample's patch rows, R + 2 of PW pixels)
+  const int x0 = BAND ? 0 : (int)(tl % gx)*TC, y0 = BAND ? (int)(tl % gy)*BR : (int)((tl/gx) % gy)*T::TRB;
+  const int b = BAND ? (int)(tl/gy)*S : (int)(tl/(gx*gy));         // (band: the first of its S samples)
   const int KC = CK >> 4, kc0 = ks*kc_per_split, kc1 = min(KC, kc0 + kc_per_split);
   const size_t plane = (size_t)hi*wi;
   typedef typename RawOf<TI>::type R;
   const R* src = reinterpret_cast<const R*>(in_) + (size_t)b*CK*plane;
+  // band: this lane's pixel of fragment nt (the wave's fragments 2 wv, 2 wv + 1) -> its sample (0 .. S - 1 in the band), row and column; -1: none
+  auto band_pixel = [&](int nt, int& seg, int& ry, int& x) {
+    const int p = (2*wv + nt)*32 + j, spx = BR*wo;
+    seg = p/spx; const int q = p - seg*spx; ry = q/wo; x = q - ry*wo;
+    if (seg >= S || b + seg >= B || y0 + ry >= ho) seg = -1;
+  };
+  int lbase[2] = {0, 0};                                          // band: the lane's patch pixel at tap (0, 0)
+  if constexpr (BAND) {
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+      int seg, ry, x;
+      band_pixel(nt, seg, ry, x);
+      lbase[nt] = seg >= 0 ? (seg*(BR + 2) + ry)*PW + x : 0;
+    }
+  }
 
   // staging: an item = 8 channels of one patch pixel; its address inside a channel plane does not depend on the chunk
   constexpr int ITEMS = 2*NPIX, TRIPS = (ITEMS + NT - 1)/NT;
@@ -148,10 +177,19 @@ __global__ __launch_bounds__(256*NM, 2/NM) void k_conv_mfma(const TI* __restrict
   for (int t = 0; t < TRIPS; ++t) {
     const int item = min(t*NT + (int)threadIdx.x, ITEMS - 1);
     const int half = item >= NPIX ? 1 : 0, pix = item - half*NPIX;
-    const int r = pix/PW, cc = pix - r*PW;
-    const int yy = y0 + r - off, xx = x0 + cc - off;
-    if (ZERO) pofs[t] = (yy >= 0 && yy < hi && xx >= 0 && xx < wi) ? yy*wi + xx : -1;
-    else pofs[t] = min(yy, hi - 1)*wi + min(xx, wi - 1);         // (beyond the image: any valid address, those outputs are not stored)
+    if constexpr (BAND) {                                         // patch pixel -> (sample of the band, row, column); past the patch or the batch: zeros /
+      const int seg = pix/SEGP, rp = pix - seg*SEGP, r = rp/PW, cc = rp - r*PW;   //   any valid address (OFF = 0)
+      const int yy = y0 + r - off, xx = cc - off;
+      const bool in_b = seg < S && b + seg < B;
+      const int sofs = min(seg, B - 1 - b)*CK*(int)plane;        // (the host keeps B CK hi wi below 2^31 for band tiles)
+      if (ZERO) pofs[t] = (in_b && yy >= 0 && yy < hi && xx >= 0 && xx < wi) ? sofs + yy*wi + xx : -1;
+      else pofs[t] = sofs + min(yy, hi - 1)*wi + min(xx, wi - 1);
+    } else {
+      const int r = pix/PW, cc = pix - r*PW;
+      const int yy = y0 + r - off, xx = x0 + cc - off;
+      if (ZERO) pofs[t] = (yy >= 0 && yy < hi && xx >= 0 && xx < wi) ? yy*wi + xx : -1;
+      else pofs[t] = min(yy, hi - 1)*wi + min(xx, wi - 1);         // (beyond the image: any valid address, those outputs are not stored)
+    }
   }
   R v[TRIPS][8];
   auto request = [&](int kc) {                                    // every load of a chunk is issued before anything waits for one
@@ -210,7 +248,7 @@ __global__ __launch_bounds__(256*NM, 2/NM) void k_conv_mfma(const TI* __restrict
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
       const int r = (TC == 64) ? wv : 2*wv + nt, cb = (TC == 64) ? nt*32 : 0;
-      const int pix = (r + ky)*PW + cb + j + kx;
+      const int pix = BAND ? lbase[nt] + ky*PW + kx : (r + ky)*PW + cb + j + kx;
       const int slot = pix*2 + (g ^ ((pix >> 3) & 1));
 #pragma unroll
       for (int p = 0; p < P; ++p) dst[nt][p] = as_frag(tile[buf*kBuf + p*NPIX*2 + slot]);
@@ -269,13 +307,21 @@ __global__ __launch_bounds__(256*NM, 2/NM) void k_conv_mfma(const TI* __restrict
   float* dstf = reinterpret_cast<float*>(out) + (size_t)ks*split_stride;
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt) {
-    const int r = (TC == 64) ? wv : 2*wv + nt, cb = (TC == 64) ? nt*32 : 0;
-    const int y = y0 + r, x = x0 + cb + j;
-    if (y < ho && x < wo) {
+    int y, x, bo = b;
+    bool ok;
+    if constexpr (BAND) {
+      int seg, ry;
+      band_pixel(nt, seg, ry, x);
+      ok = seg >= 0; y = y0 + ry; bo = b + seg;
+    } else {
+      const int r = (TC == 64) ? wv : 2*wv + nt, cb = (TC == 64) ? nt*32 : 0;
+      y = y0 + r; x = x0 + cb + j; ok = y < ho && x < wo;
+    }
+    if (ok) {
 #pragma unroll
       for (int rr = 0; rr < 16; ++rr) {
         const int m = mg*32 + (rr & 3) + 8*(rr >> 2) + 4*g;
-        const size_t o = (((size_t)b*M + m)*ho + y)*wo + x;
+        const size_t o = (((size_t)bo*M + m)*ho + y)*wo + x;
         if (KS > 1) dstf[o] = acc[nt][rr] + lo[nt][rr];
         else store_out<TO>(out, o, acc[nt][rr] + lo[nt][rr]);
       }
@@ -607,9 +653,11 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_mfma(const TI* __restrict
 // ZP: xp is the UNPADDED input (B, C, h, w) of a zero-padded layer (the encoders' 3x3 stride-1 convolutions): column col of padded row r is input column
 // col - 1 of input row r - 1; columns outside the row carry the out-of-range offset and rows above / below the image an empty buffer resource — the DMA writes
 // zeros for both, so the block sees the zero-padded rows without a padded copy of the activation.
+// spb > 1 (the coarse layers, see wgrad_shape): a block walks the rows of spb samples one after the other into the same accumulators, switching the buffer
+// resources per row it requests; it leaves one set of partials for all of them.
 template <int P, bool ZP>
 __global__ __launch_bounds__(256, 2) void k_conv_wgrad_dma(const float* __restrict__ xp, const float* __restrict__ gy, float* __restrict__ partial,
-                                                        int C, int CO, int h, int w, int rows_per_block) {
+                                                        int B, int C, int CO, int h, int w, int rows_per_block, int spb) {
   constexpr int COB = 32, CB = 64, NW = 4, NPROD = n_products(P), CS = 36, D = 4;
   constexpr int XDW = CB*CS, GDW = COB*CS, NPX = XDW/64, NPG = GDW/64, NX = (NPX + NW - 1)/NW, NG = (NPG + NW - 1)/NW, NDMA = NX + NG, SLOT = XDW + GDW + 64;
   static_assert(XDW % 64 == 0 && GDW % 64 == 0 && (D - 2)*NDMA < 64 && D == 4, "DMA pieces and waits");
@@ -618,11 +666,15 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_dma(const float* __restri
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), j = lane & 31, g = lane >> 5;
   const int ct = wv & 1, ks = wv >> 1;
   const int CGRP = (C + CB - 1)/CB, COGRP = CO/COB;
-  const int cg = blockIdx.z % CGRP, cog = (blockIdx.z/CGRP) % COGRP, b = blockIdx.z/(CGRP*COGRP);
-  const int x0 = blockIdx.x*32, ybeg = blockIdx.y*rows_per_block, nrows = min(rows_per_block, h - ybeg), nsteps = nrows + 2;
+  const int cg = blockIdx.z % CGRP, cog = (blockIdx.z/CGRP) % COGRP, sg = blockIdx.z/(CGRP*COGRP);
+  const int x0 = blockIdx.x*32, ybeg = blockIdx.y*rows_per_block, nrows = min(rows_per_block, h - ybeg);
+  // ZP: the input rows -1 and h are zeros.  A block that starts at the top still fetches its step 0 (g_y row 0 is the later steps' ky = 1, 2 operand) but
+  // runs no MFMAs there; one that ends at the bottom drops its last step (input row h against g_y rows past the image and h - 1 x zeros) altogether.
+  const bool skip0 = ZP && ybeg == 0;
+  const int nsteps = nrows + 2 - ((ZP && ybeg + nrows == h) ? 1 : 0);
+  const int b0 = sg*spb, nsteps_all = min(spb, B - b0)*nsteps;    // samples b0 .. + spb - 1, one after the other: step s = sample s / nsteps, its step s % nsteps
   const int W = w + 2, H = h + 2;
-  const rsrc_t rs_x = ZP ? make_rsrc(xp + (size_t)b*C*h*w, (size_t)C*h*w*4) : make_rsrc(xp + (size_t)b*C*H*W, (size_t)C*H*W*4);   // (ZP: unpadded planes)
-  const rsrc_t rs_g = make_rsrc(gy + ((size_t)b*CO + (size_t)cog*COB)*h*w, (size_t)COB*h*w*4);
+  const size_t xsample = ZP ? (size_t)C*h*w : (size_t)C*H*W;       // (ZP: unpadded planes)
   [[maybe_unused]] const rsrc_t rs_0 = make_rsrc(xp, 0);          // (ZP: the rows above and below the image — every load out of range, zeros)
   const unsigned lds0 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)(__attribute__((address_space(3))) unsigned*)lds);
   auto dma = [&](const rsrc_t& rs, unsigned v, unsigned so, unsigned dst) {
@@ -645,8 +697,14 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_dma(const float* __restri
     const int k = n*NW + wv, d = k*64 + lane, co = d/CS, col = d - co*CS;
     tab[(NX + n)*64] = (k < NPG && col < 32 && x0 + col < w) ? (unsigned)((co*h)*w + x0 + col)*4u : 0x80000000u;
   }
-  auto issue = [&](int r) {
-    const unsigned base = lds0 + (unsigned)((r % D)*SLOT*4);
+  // the next step to issue, as (sample, step of that sample): issue() is called for steps 0, 1, 2, ... in order, once each
+  int is_b = b0, is_r = 0;
+  auto issue = [&](int q) {
+    const int r = is_r, b = is_b;
+    if (++is_r == nsteps) { is_r = 0; ++is_b; }
+    const unsigned base = lds0 + (unsigned)((q % D)*SLOT*4);
+    const rsrc_t rs_x = make_rsrc(xp + (size_t)b*xsample, xsample*4);
+    const rsrc_t rs_g = make_rsrc(gy + ((size_t)b*CO + (size_t)cog*COB)*h*w, (size_t)COB*h*w*4);
     rsrc_t rx = rs_x;
     unsigned sx;
     if constexpr (ZP) {                                           // input row ybeg + r - 1; rows -1 and h are the zero rows
@@ -675,14 +733,19 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_dma(const float* __restri
 #pragma unroll
     for (int p = 0; p < P; ++p) A[r][p] = as_frag(uint4{0u, 0u, 0u, 0u});
 
+  // step i of the block (step il of its sample): input row il against g_y rows il - ky.  A sample's last two steps carry zero g_y fragments (a0 past the
+  // block's rows), so the next sample's first two steps find zeros as the "rows before" (a1, a2) — the ring needs no reset between samples.
+  int st_r = 0;
   auto step = [&](int i, bf16x8 (&a0)[P], const bf16x8 (&a1)[P], const bf16x8 (&a2)[P]) {
-    const int after = min(D - 2, nsteps - 1 - i);
+    const int il = st_r;
+    if (++st_r == nsteps) st_r = 0;
+    const int after = min(D - 2, nsteps_all - 1 - i);
     if (after >= 2) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2*NDMA) : "memory");
     else if (after == 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NDMA) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if (i + D - 1 < nsteps) issue(i + D - 1);
+    if (i + D - 1 < nsteps_all) issue(i + D - 1);
     const float* slot = reinterpret_cast<const float*>(lds) + (i % D)*SLOT;
     const float* xr = slot + (ct*32 + j)*CS + ks*16 + g*8;
     const float* gr = slot + XDW + j*CS + ks*16 + g*8;
@@ -699,8 +762,9 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_dma(const float* __restri
       Bx[1][p] = as_frag(uint4{__builtin_amdgcn_alignbit(px[1][p], px[0][p], 16), __builtin_amdgcn_alignbit(px[2][p], px[1][p], 16),
                                __builtin_amdgcn_alignbit(px[3][p], px[2][p], 16), __builtin_amdgcn_alignbit(px[4][p], px[3][p], 16)});
       Bx[2][p] = as_frag(uint4{px[1][p], px[2][p], px[3][p], px[4][p]});
-      a0[p] = as_frag(i < nrows ? uint4{pg[0][p], pg[1][p], pg[2][p], pg[3][p]} : uint4{0u, 0u, 0u, 0u});
+      a0[p] = as_frag(il < nrows ? uint4{pg[0][p], pg[1][p], pg[2][p], pg[3][p]} : uint4{0u, 0u, 0u, 0u});
     }
+    if (skip0 && il == 0) return;                                 // (wave-uniform)
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky) {
       const bf16x8 (&a)[P] = ky == 0 ? a0 : ky == 1 ? a1 : a2;
@@ -711,11 +775,11 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_dma(const float* __restri
     }
   };
 #pragma unroll
-  for (int r = 0; r < D - 1; ++r) issue(r);
-  for (int i = 0; i < nsteps; i += 3) {
+  for (int r = 0; r < D - 1; ++r) if (r < nsteps_all) issue(r);   // (ZP: h = 1 leaves two steps)
+  for (int i = 0; i < nsteps_all; i += 3) {
     step(i, A[0], A[2], A[1]);
-    if (i + 1 < nsteps) step(i + 1, A[1], A[0], A[2]);
-    if (i + 2 < nsteps) step(i + 2, A[2], A[1], A[0]);
+    if (i + 1 < nsteps_all) step(i + 1, A[1], A[0], A[2]);
+    if (i + 2 < nsteps_all) step(i + 2, A[2], A[1], A[0]);
   }
   __syncthreads();
   float* red = reinterpret_cast<float*>(lds);
@@ -731,7 +795,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_dma(const float* __restri
     for (int t = 0; t < 9; ++t)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[t][r] += red[(ct*144 + t*16 + r)*64 + lane];
-    const size_t blk = ((size_t)b*gridDim.y + blockIdx.y)*gridDim.x + blockIdx.x;
+    const size_t blk = ((size_t)sg*gridDim.y + blockIdx.y)*gridDim.x + blockIdx.x;
     const int c = (cg*2 + ct)*32 + j;
     if (c < C) {
 #pragma unroll
@@ -1042,13 +1106,30 @@ __global__ __launch_bounds__(256) void k_conv_wgrad_finalize2(const double* __re
 static unsigned wgrad_slices(unsigned T) { return T < 64 ? 1u : std::min(32u, T/16); }
 
 // ---- launch shapes ----
-static void wgrad_shape(int B, int C, int CO, int h, int w, dim3& grid, int& rows) {
-  const int strips = ceil_div(w, 32), base = strips*B*ceil_div(C, 64)*(CO/32);
+// spb: samples per block.  multi (the fp32 LDS-DMA form): where every block already takes a whole sample's rows and one block per sample would need more
+// than one generation (the coarse layers: 256 - 512 channels at 12 x 40 / 6 x 20), a block walks the rows of several samples, one after the other, into the
+// same accumulators — the partial sums (9 CO C floats each, written and read back by the finalize) then number strips x sample groups instead of
+// strips x B.  Only groupings that still fill both block slots of every CU (>= 512 blocks) are taken: a lone block on a CU runs its rows hardly faster
+// than a pair does (measured: 288 blocks of two samples at 24 x 80 b = 24, 141 us against 116 for 576 blocks of one).  Among those, the fewest
+// (blocks per CU x (steps per block + the block's epilogue, about four steps)).
+static void wgrad_shape(int B, int C, int CO, int h, int w, dim3& grid, int& rows, int& spb, bool multi) {
+  const int cgs = ceil_div(C, 64)*(CO/32), strips = ceil_div(w, 32), base = strips*B*cgs;
   const int groups = std::max(1, std::min(512/std::max(base, 1), ceil_div(h, 12)));  // two blocks per CU: about one generation of equal blocks where the layer allows; at least
                                                                                       // twelve rows per block (a block runs two steps more than it has rows, then reduces and writes 9 x 32 x 64 sums)
   rows = ceil_div(h, groups);
-  grid = dim3(strips, ceil_div(h, rows), B*ceil_div(C, 64)*(CO/32));
+  spb = 1;
+  if (multi && rows == h && base > 512) {
+    const long long per = (long long)strips*cgs;
+    long long best = -1;
+    for (int s = 1; s <= B; ++s) {
+      const long long nsg = ceil_div(B, s), cost = ceil_div(nsg*per, 256ll)*(s*(h + 2) + 4);
+      if (s > 1 && nsg*per < 512) break;
+      if (best < 0 || cost < best) { best = cost; spb = s; }
+    }
+  }
+  grid = dim3(strips, ceil_div(h, rows), ceil_div(B, spb)*cgs);
 }
+static void wgrad_shape(int B, int C, int CO, int h, int w, dim3& grid, int& rows) { int spb; wgrad_shape(B, C, CO, h, w, grid, rows, spb, false); }
 static void wgrad16_shape(int B, int C, int h, int w, dim3& grid, int& rows) {
   const int strips = ceil_div(w, 64);
   const long long units = (long long)strips*B, slots = C == 16 ? 1024 : 768;   // strips of 64 columns; ONE generation of blocks (four / three per CU), at least twelve rows per block
@@ -1056,13 +1137,20 @@ static void wgrad16_shape(int B, int C, int h, int w, dim3& grid, int& rows) {
   rows = ceil_div(h, groups);
   grid = dim3(strips, ceil_div(h, rows), B);
 }
-// floats of workspace: the blocks' partial sums, then the finalize's fp64 slices
-size_t conv_mfma_wgrad_partials(int B, int C, int CO, int h, int w) {
-  dim3 grid; int rows;
-  if (CO == 16) wgrad16_shape(B, C, h, w, grid, rows); else wgrad_shape(B, C, CO, h, w, grid, rows);
-  const size_t T = (size_t)grid.x*grid.y*B, n = (size_t)9*CO*C;
-  return T*n + 2*(size_t)wgrad_slices((unsigned)T)*n;           // (T n is even: n = 9 CO C with CO even)
+// the number of partial-sum sets the weight gradient leaves (multi: the fp32 form whose blocks walk several samples)
+static unsigned wgrad_sets(int B, int C, int CO, int h, int w, bool multi) {
+  dim3 grid; int rows, spb = 1;
+  if (CO == 16) wgrad16_shape(B, C, h, w, grid, rows); else wgrad_shape(B, C, CO, h, w, grid, rows, spb, multi);
+  return grid.x*grid.y*(unsigned)ceil_div(B, spb);
 }
+static size_t wgrad_floats(unsigned T, int C, int CO) {
+  const size_t n = (size_t)9*CO*C;
+  const unsigned G = wgrad_slices(T);                             // (G = 1: the finalize writes g_w directly, no fp64 slices)
+  return (size_t)T*n + (G > 1 ? 2*(size_t)G*n : 0);              // (T n is even: n = 9 CO C with CO even)
+}
+// floats of workspace: the blocks' partial sums, then the finalize's fp64 slices (the padded form's bfloat16 path keeps one sample per block: the larger size)
+size_t conv_mfma_wgrad_partials(int B, int C, int CO, int h, int w) { return wgrad_floats(wgrad_sets(B, C, CO, h, w, false), C, CO); }
+size_t conv_mfma_z_wgrad_partials(int B, int C, int CO, int h, int w) { return wgrad_floats(wgrad_sets(B, C, CO, h, w, true), C, CO); }
 static size_t thin_packed_elems(int C, int pieces) { return (size_t)(C >> 4)*5*pieces*512; }
 size_t conv_mfma_packed_elems(int C, int CO, int pieces) { return std::max((size_t)CO*C*9*pieces, CO == 16 ? thin_packed_elems(C, pieces) : (size_t)0); }
 
@@ -1105,14 +1193,53 @@ hipError_t launch_conv_mfma_pack(const float* w, void* wp_fwd, void* wp_bwd, int
 static int g_conv_two_tiles = 0;
 void set_conv_two_tiles(int v) { g_conv_two_tiles = v; }
 static bool conv_two_tiles() { return g_conv_two_tiles != 0; }
-struct ConvShape { int TC, TRB, NM, KS, kcs; unsigned gx, gy, gz; dim3 grid; size_t out_elems; };
+struct ConvShape { int TC, TRB, NM, KS, kcs, S; unsigned gx, gy, gz; dim3 grid; size_t out_elems; };
+// Row-band tiles (TC = 0): BR rows of one sample, or S whole samples (BR = ho) where an image has at most 128 pixels; the patch (S (BR + 2) (wo + 2) pixels)
+// must fit ConvTile<0>::NPIX.  Returns the useful share of the band blocks' 256 pixels, 0 where no band fits.
+static double band_shape(int B, int CK, int ho, int wo, int& BR, int& S) {
+  constexpr int NP = ConvTile<0>::NPIX;
+  const int PW = wo + 2;
+  if (3*PW > NP || (long long)B*CK*(ho + 2)*PW >= (1ll << 31)) return 0.0;   // (the kernel's patch offsets are int)
+  if (ho*wo <= 128) {
+    BR = ho; S = std::min(256/(ho*wo), B);
+    while (S > 1 && S*(ho + 2)*PW > NP) --S;
+  } else {
+    S = 1; BR = std::min(ho, 256/wo);
+    while (BR > 0 && (BR + 2)*PW > NP) --BR;
+    if (BR == 0) return 0.0;
+  }
+  return (double)B*ho*wo/((double)ceil_div(ho, BR)*ceil_div(B, S)*256.0);
+}
 static ConvShape conv_shape(int B, int CK, int M, int ho, int wo) {
   ConvShape s;
-  s.TC = wo >= 48 ? 64 : 32; s.TRB = wo >= 48 ? 4 : 8;
+  s.TC = wo >= 48 ? 64 : 32; s.TRB = wo >= 48 ? 4 : 8; s.S = 1;
+  const int KC = CK >> 4;
+  {
+    // band tiles where the rectangular ones waste clearly more (under 90 % useful, and the band at least 5 points better); their K split is chosen by
+    // whole generations of the 512 block slots (256 CUs x 2): the fewest (generations x (chunks per split + one for the block's prologue / epilogue)),
+    // plus the split partials' round trip through memory (~25 MB per chunk's time), instead of the rectangular tiles' "under 1.5 blocks per CU" rule
+    const double rect = (double)B*ho*wo/((double)ceil_div(wo, s.TC)*s.TC*ceil_div(ho, s.TRB)*s.TRB*B);
+    int BR = 0, S = 1;
+    const double band = rect < 0.9 ? band_shape(B, CK, ho, wo, BR, S) : 0.0;
+    if (band > rect + 0.05) {
+      s.TC = 0; s.TRB = BR; s.S = S; s.NM = 1;
+      s.gx = BR; s.gy = ceil_div(ho, BR); s.gz = ceil_div(B, S);
+      s.out_elems = (size_t)B*M*ho*wo;
+      const long long base = (long long)s.gy*s.gz*(M/32);
+      double best = -1.0;
+      for (int kcs = std::min(2, KC); kcs <= KC; ++kcs) {
+        const int KS = ceil_div(KC, kcs);
+        if (ceil_div(KC, KS) != kcs) continue;                    // (the same split count with fewer chunks per split)
+        const double cost = (double)ceil_div(base*KS, 512ll)*(kcs + 1) + (KS > 1 ? (2.0*KS + 1.0)*s.out_elems*4.0/25e6 : 0.0);
+        if (best < 0.0 || cost < best - 1e-9) { best = cost; s.kcs = kcs; s.KS = KS; }
+      }
+      s.grid = dim3(8*(unsigned)ceil_div(base*s.KS, 8ll));
+      return s;
+    }
+  }
   const long long tiles = (long long)ceil_div(wo, s.TC)*ceil_div(ho, s.TRB)*B;
   s.NM = (M % 64 == 0 && tiles*(M/64) >= 256 && conv_two_tiles()) ? 2 : 1;   // two channel tiles over one patch where that still leaves a block per CU
   const long long base = tiles*(M/(32*s.NM));
-  const int KC = CK >> 4;
   int ks = 1;
   if (base < 384) ks = (int)std::min<long long>(std::max(KC/2, 1), (512 + base - 1)/base);   // under 1.5 blocks per CU: split K, at least two chunks per split
   s.kcs = ceil_div(KC, ks); s.KS = ceil_div(KC, s.kcs);
@@ -1132,11 +1259,12 @@ static void launch_conv_form(const void* in, const void* wp, void* out, float* s
   const uint4* wq = (const uint4*)wp;
   const T* i_ = (const T*)in;
   T* dst = s.KS > 1 ? reinterpret_cast<T*>(split_ws) : (T*)out;    // (the kernel writes a split's partial output as fp32 whatever T)
-  if (s.NM == 2) {
-    if (s.TC == 64) hipLaunchKernelGGL((k_conv_mfma<64, P, OFF, T, T, 2>), s.grid, dim3(512), 0, st, i_, wq, dst, CK, M, hi, wi, ho, wo, s.KS, s.kcs, s.out_elems, s.gx, s.gy, s.gz);
-    else hipLaunchKernelGGL((k_conv_mfma<32, P, OFF, T, T, 2>), s.grid, dim3(512), 0, st, i_, wq, dst, CK, M, hi, wi, ho, wo, s.KS, s.kcs, s.out_elems, s.gx, s.gy, s.gz);
-  } else if (s.TC == 64) hipLaunchKernelGGL((k_conv_mfma<64, P, OFF, T, T, 1>), s.grid, dim3(256), 0, st, i_, wq, dst, CK, M, hi, wi, ho, wo, s.KS, s.kcs, s.out_elems, s.gx, s.gy, s.gz);
-  else hipLaunchKernelGGL((k_conv_mfma<32, P, OFF, T, T, 1>), s.grid, dim3(256), 0, st, i_, wq, dst, CK, M, hi, wi, ho, wo, s.KS, s.kcs, s.out_elems, s.gx, s.gy, s.gz);
+  if (s.TC == 0) hipLaunchKernelGGL((k_conv_mfma<0, P, OFF, T, T, 1>), s.grid, dim3(256), 0, st, i_, wq, dst, CK, M, hi, wi, ho, wo, s.KS, s.kcs, s.out_elems, s.gx, s.gy, s.gz, s.S, B);
+  else if (s.NM == 2) {
+    if (s.TC == 64) hipLaunchKernelGGL((k_conv_mfma<64, P, OFF, T, T, 2>), s.grid, dim3(512), 0, st, i_, wq, dst, CK, M, hi, wi, ho, wo, s.KS, s.kcs, s.out_elems, s.gx, s.gy, s.gz, 1, B);
+    else hipLaunchKernelGGL((k_conv_mfma<32, P, OFF, T, T, 2>), s.grid, dim3(512), 0, st, i_, wq, dst, CK, M, hi, wi, ho, wo, s.KS, s.kcs, s.out_elems, s.gx, s.gy, s.gz, 1, B);
+  } else if (s.TC == 64) hipLaunchKernelGGL((k_conv_mfma<64, P, OFF, T, T, 1>), s.grid, dim3(256), 0, st, i_, wq, dst, CK, M, hi, wi, ho, wo, s.KS, s.kcs, s.out_elems, s.gx, s.gy, s.gz, 1, B);
+  else hipLaunchKernelGGL((k_conv_mfma<32, P, OFF, T, T, 1>), s.grid, dim3(256), 0, st, i_, wq, dst, CK, M, hi, wi, ho, wo, s.KS, s.kcs, s.out_elems, s.gx, s.gy, s.gz, 1, B);
   if (s.KS > 1) {
     const size_t n4 = s.out_elems/4;                              // (B M ho wo is a multiple of 4: M is a multiple of 32)
     hipLaunchKernelGGL((k_conv_split_sum<T>), dim3((unsigned)((n4 + 255)/256)), dim3(256), 0, st, split_ws, (T*)out, n4, s.KS);
@@ -1187,14 +1315,13 @@ static void launch_wgrad(const void* xp_, const void* gy_, float* partial, int B
     }
     return;
   }
-  wgrad_shape(B, C, CO, h, w, grid, rows);
-  if constexpr (std::is_same<T, float>::value) hipLaunchKernelGGL((k_conv_wgrad_dma<P, false>), grid, dim3(256), 0, st, xp, gy, partial, C, CO, h, w, rows);
+  int spb;
+  wgrad_shape(B, C, CO, h, w, grid, rows, spb, std::is_same<T, float>::value);
+  if constexpr (std::is_same<T, float>::value) hipLaunchKernelGGL((k_conv_wgrad_dma<P, false>), grid, dim3(256), 0, st, xp, gy, partial, B, C, CO, h, w, rows, spb);
   else hipLaunchKernelGGL((k_conv_wgrad_mfma<P, T>), grid, dim3(256), 0, st, xp, gy, partial, C, CO, h, w, rows);
 }
-static hipError_t wgrad_finalize(float* g_w, float* partial, int B, int C, int CO, int h, int w, hipStream_t st) {
-  dim3 grid; int rows;
-  if (CO == 16) wgrad16_shape(B, C, h, w, grid, rows); else wgrad_shape(B, C, CO, h, w, grid, rows);
-  const unsigned T = grid.x*grid.y*(unsigned)B, G = wgrad_slices(T);
+static hipError_t wgrad_finalize(float* g_w, float* partial, int B, int C, int CO, int h, int w, bool multi, hipStream_t st) {
+  const unsigned T = wgrad_sets(B, C, CO, h, w, multi), G = wgrad_slices(T);
   const int n = CO*C*9;
   double* slice = reinterpret_cast<double*>(partial + (size_t)T*n);
   if (G == 1) hipLaunchKernelGGL(k_conv_wgrad_finalize<true>, dim3(ceil_div(n, 64), 1), dim3(256), 0, st, partial, T, 1u, CO, C, slice, g_w);
@@ -1208,7 +1335,7 @@ hipError_t launch_conv_mfma_bwd_wgt(const void* xp, const void* gy, float* g_w, 
 #define SMD_CALL(P, T) launch_wgrad<P, T>(xp, gy, partial, B, C, CO, h, w, st)
   SMD_BY_PIECES(pieces, SMD_CALL);
 #undef SMD_CALL
-  return wgrad_finalize(g_w, partial, B, C, CO, h, w, st);
+  return wgrad_finalize(g_w, partial, B, C, CO, h, w, pieces != 1, st);
 }
 
 // ---- zero-padded "same" layers (the ResNet encoders' 3x3 stride-1 convolutions, padding 1): x (B, C, h, w) -> y (B, CO, h, w), g_y -> g_x (B, C, h, w),
@@ -1234,14 +1361,14 @@ hipError_t launch_conv_mfma_z_bwd_data(const float* gy, const void* wp_bwd, floa
 #undef SMD_CALL
   return hipGetLastError();
 }
-// g_w (CO, C, 3, 3): CO % 32 == 0, any C >= 1; the same launch shape and workspace as the padded form
+// g_w (CO, C, 3, 3): CO % 32 == 0, any C >= 1; the launch shape of the padded form's fp32 path
 hipError_t launch_conv_mfma_z_bwd_wgt(const float* x, const float* gy, float* g_w, float* partial, int B, int C, int CO, int h, int w, int pieces, hipStream_t st) {
-  dim3 grid; int rows;
-  wgrad_shape(B, C, CO, h, w, grid, rows);
-#define SMD_CALL(P) hipLaunchKernelGGL((k_conv_wgrad_dma<P, true>), grid, dim3(256), 0, st, x, gy, partial, C, CO, h, w, rows)
+  dim3 grid; int rows, spb;
+  wgrad_shape(B, C, CO, h, w, grid, rows, spb, true);
+#define SMD_CALL(P) hipLaunchKernelGGL((k_conv_wgrad_dma<P, true>), grid, dim3(256), 0, st, x, gy, partial, B, C, CO, h, w, rows, spb)
   SMD_BY_PIECES_F32(pieces, SMD_CALL);
 #undef SMD_CALL
-  return wgrad_finalize(g_w, partial, B, C, CO, h, w, st);
+  return wgrad_finalize(g_w, partial, B, C, CO, h, w, true, st);
 }
 
 }  // namespace smd

@@ -273,6 +273,7 @@ hipError_t launch_conv_thin_bwd_data(const float* gy, const float* wgt, float* g
 size_t conv_mfma_packed_elems(int C, int CO, int pieces);
 void set_conv_two_tiles(int v);     // launch-shape knob of the forward / data-gradient form (smd_api.hip: conv_two_tiles)
 size_t conv_mfma_wgrad_partials(int B, int C, int CO, int h, int w);
+size_t conv_mfma_z_wgrad_partials(int B, int C, int CO, int h, int w);
 hipError_t launch_conv_mfma_pack(const float* w, void* wp_fwd, void* wp_bwd, int C, int CO, int pieces, hipStream_t st);
 size_t conv_mfma_fwd_split_elems(int B, int C, int CO, int h, int w);     // floats of K-split partial outputs the forward / the data gradient wants (0: none)
 size_t conv_mfma_bwd_split_elems(int B, int C, int CO, int h, int w);

@@ -942,23 +942,26 @@ def conv_routes() -> dict:
 
 
 def _conv_static_rule(op, B, C, CO, h, w):
-    """Stand-in where nothing may be timed (graph capture): the shapes that won on an MI355X at cfg 2 (profiles/r06_decoder_convs.txt; the zero-padded
-    encoder layers, `*_z`: profiles/r07_encoder_convs.txt)."""
+    """Stand-in where nothing may be timed (graph capture): the shapes that won on an MI355X at cfg 2 (profiles/r06_decoder_convs.txt; the coarse levels
+    on the row-band tiles, 512 -> 256 at 6 x 20 / 12 x 40 and 256 -> 128 at 12 x 40 / 24 x 80: profiles/r08_coarse_convs.txt; the zero-padded encoder
+    layers, `*_z`: see `_conv_static_rule_z`)."""
     px = B*h*w
     if op.endswith('_bf16'): return CO == 16           # (bf16 tensors: MIOpen's bf16 kernels serve the wide layers; the thin stage is the stencil-like case)
     if op.endswith('_z'): return _conv_static_rule_z(op[:-2], B, C, CO, h, w)
     if CO == 16: return op != 'wgt'
-    if op == 'fwd': return px >= 20000 and C*CO <= 128*64
-    if op == 'data': return px >= 5000 and C <= 256
-    return px >= 20000 and CO <= 64
+    coarse = w <= 80 and C >= 256                      # (row-band tiles: 1.18-1.59 x forward, 1.09-1.74 x data gradient, 0.92-1.37 x weight gradient)
+    if op == 'fwd': return (px >= 20000 and C*CO <= 128*64) or (coarse and px >= 1000)
+    if op == 'data': return (px >= 5000 and C <= 256) or (coarse and px >= 1000)
+    return (px >= 20000 and CO <= 64) or (coarse and px >= 2400)
 
 
 def _conv_static_rule_z(op, B, C, CO, h, w):
-    """The zero-padded encoder layers (C = CO): the kernels win 1.4-1.8 x at 64 channels and 48 x 160, 1.2-1.3 x at 128 channels and 24 x 80 with b = 24, and
-    only the weight gradient there with b = 12; from 256 channels on they are even with MIOpen or behind it (profiles/r07_encoder_convs.txt)."""
+    """The zero-padded encoder layers (C = CO; profiles/r08_coarse_convs.txt): the data gradient wins at every stage (1.4-1.7 x); the forward and the
+    weight gradient win 1.13-1.6 x from 64 to 256 channels and at 512 channels with b = 24 (6 x 20, 2880 pixels), and are even with MIOpen at 512
+    channels with b = 12 (1440 pixels)."""
     px = B*h*w
-    if op == 'wgt': return px >= 20000 and CO <= 128
-    return px >= 40000 and C <= 128 and CO <= 128
+    if op == 'data': return px >= 1000
+    return px >= (2400 if max(C, CO) >= 512 else 1000)
 
 
 def _conv_route(op, B, C, CO, h, w, run_mfma, run_ref):
