@@ -298,6 +298,47 @@ int smd_conv3x3_head_fwd(const void* xp, const float* weight, const float* bias,
 int smd_conv3x3_head_bwd(const void* xp, const float* weight, const float* y, const float* g_y, void* g_xp, float* g_weight, float* g_bias,
                          void* workspace, size_t workspace_bytes, int B, int C, int h, int w, int act, void* stream);
 
+/* Output heads with a few output channels: the predictive-mask decoder (additive to ABI 8; reference: src/networks/depth.py:12, 108-114 —
+ * `MonodepthDecoder(out_ch=num_ch_mask, out_act=MASKS[mask_name])`, MASKS = {'explainability': 'sigmoid', 'uncertainty': 'relu'}; the heads themselves
+ * src/networks/decoders/monodepth.py:52, 86-87 — `self.act(self.out[i](x))` with `conv3x3(num_ch_dec[i], out_ch)`):
+ * y (B,n,h,w) = act(conv3x3(xp; weight (n,C,3,3)) + bias (n) or NULL), 1 <= n <= 4, xp (B,C,h+2,w+2) the reflection-padded activation smd_elu_pad_fwd
+ * leaves.  The padded activation is read once for all n channels (n accumulators per output row).  act: SMD_HEADN_NONE / _SIGMOID / _RELU, ored with
+ * SMD_HEADN_X_BF16 when xp and g_xp are bfloat16 (the decoder under bf16 autocast); weights, bias, y, g_y and every sum stay fp32.
+ * Backward, from g_y and the saved y (gp = g_y * act'(y); relu: y > 0): _bwd_data -> g_xp (B,C,h+2,w+2), summed over the n channels per padded position;
+ * _bwd_wgt -> g_weight (n,C,3,3) and g_bias (n) or NULL, per-block partial sums in the workspace and a fixed-order fp64 final sum.  Deterministic. */
+#define SMD_HEADN_NONE 0
+#define SMD_HEADN_SIGMOID 1
+#define SMD_HEADN_RELU 2
+#define SMD_HEADN_X_BF16 4
+size_t smd_conv3x3_headn_workspace_bytes(int B, int C, int n, int h, int w);
+int smd_conv3x3_headn_fwd(const void* xp, const float* weight, const float* bias, float* y, int B, int C, int n, int h, int w, int act, void* stream);
+int smd_conv3x3_headn_bwd_data(const float* weight, const float* y, const float* g_y, void* g_xp, int B, int C, int n, int h, int w, int act, void* stream);
+int smd_conv3x3_headn_bwd_wgt(const void* xp, const float* y, const float* g_y, float* g_weight, float* g_bias, void* workspace, size_t workspace_bytes,
+                              int B, int C, int n, int h, int w, int act, void* stream);
+
+/* Multi-scale, multi-channel bilinear up-sampling (additive to ABI 8).  Replaces, per scale, `ops.interpolate_like(mask, imgs, mode='bilinear')`
+ * (src/core/trainer.py:323-324, src/tools/ops.py:311-314; F.interpolate with align_corners=False) and the `torch.stack` of src/core/handlers.py:47:
+ *   x[s] (b,n,hs[s],ws[s]) (host array of S device pointers)  ->  out (S,b,n,h,w), one launch.
+ * Backward: g_out (S,b,n,h,w) -> g_x[s] (b,n,hs,ws), overwritten: the exact adjoint, a gather per source pixel (no atomics), one launch.
+ * b*n <= 65535.  (K0 above is the one-channel form that also converts to depth.) */
+int smd_upsample_stack_fwd(const float* const* x, const int* hs, const int* ws, int S, int b, int n, int h, int w, float* out, void* stream);
+int smd_upsample_stack_bwd(const int* hs, const int* ws, int S, int b, int n, int h, int w, const float* g_out, float* const* g_x, void* stream);
+
+/* Mean over scales of per-scale means (additive to ABI 8): loss = mean_s( mean(f(x[s])) ) for S tensors of numel[s] elements each, one launch.  Replaces
+ * `handlers.disp_mask` / `handlers.disp_occ` (src/core/handlers.py:314-347) around `MaskReg` (src/regularizers/mask.py:29 —
+ * `F.binary_cross_entropy(x, ones_like(x))`, i.e. f(x) = -max(log x, -100) with ATen's clamp) and `OccReg` (src/regularizers/occlusion.py:39 — f(x) = sign * x).
+ * mode: SMD_MEAN_BCE_ONES, SMD_MEAN_IDENTITY, SMD_MEAN_NEGATE.  Per-block partial sums in fp32; the block that arrives last adds them in fp64 in block order.
+ * workspace: smd_scale_mean_workspace_bytes() bytes whose first 4 bytes, the arrival counter, must be ZERO on entry; the forward leaves them zero, so a
+ * buffer cleared once can be kept and reused by calls that are ordered on one stream.
+ * Backward: g_x[s] = g_loss[0] * f'(x[s]) / (S * numel[s]), one launch; for SMD_MEAN_BCE_ONES f'(x) = (x - 1) / max((1 - x) x, 1e-12), ATen's
+ * binary_cross_entropy_backward (x may be NULL for the two linear modes). */
+#define SMD_MEAN_BCE_ONES 0
+#define SMD_MEAN_IDENTITY 1
+#define SMD_MEAN_NEGATE 2
+size_t smd_scale_mean_workspace_bytes(const long long* numel, int S);
+int smd_scale_mean_fwd(const float* const* x, const long long* numel, int S, int mode, float* loss, void* workspace, size_t workspace_bytes, void* stream);
+int smd_scale_mean_bwd(const float* const* x, const long long* numel, int S, int mode, const float* g_loss, float* const* g_x, void* stream);
+
 /* The decoder's thin up-convolutions (ABI 7, round 5; reference: src/networks/decoders/monodepth.py:45-50, 80-84 — `ConvELU(cin, 16)`; the bias and the ELU
  * are the next glue kernel's): y (B,16,h,w) = conv3x3(xp (B,C,h+2,w+2); weight (16,C,3,3)), bias-free, C = 16 or 32 (anything else: SMD_E_UNSUPPORTED),
  * on the matrix cores in fp32 (v_mfma_f32_16x16x4_f32: exact f32 products, f32 accumulation; the order of the sum differs from ATen's).

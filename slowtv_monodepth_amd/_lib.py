@@ -12,7 +12,7 @@ from pathlib import Path
 
 import torch  # noqa: F401  MUST precede the CDLL below: the library binds to the HIP runtime torch has already loaded
 
-__all__ = ['lib', 'call', 'set_knob', 'reset_knobs', 'knob_epoch', 'lib_path', 'FLAGS', 'REGR_FLAGS', 'SEL_MASKED', 'ptr_array', 'int_array', 'HotpathError', 'Unsupported']
+__all__ = ['lib', 'call', 'set_knob', 'reset_knobs', 'knob_epoch', 'lib_path', 'FLAGS', 'REGR_FLAGS', 'SEL_MASKED', 'ptr_array', 'int_array', 'i64_array', 'HotpathError', 'Unsupported']
 
 _HERE = Path(__file__).resolve().parent
 lib_path = Path(os.environ.get('SMD_HOTPATH_LIB', _HERE/'libsmd_hotpath.so'))
@@ -67,6 +67,15 @@ PROTOTYPES = {
     'smd_recon_reduce_fwd': (_i, [_vp]*4 + [_u64] + [_vp]*4 + [_sz] + [_i]*5 + [_vp]),
     'smd_recon_reduce_bwd': (_i, [_vp]*7 + [_i]*5 + [_vp]),
     'smd_decoder_glue_workspace_bytes': (_sz, [_i]*4),
+    'smd_conv3x3_headn_workspace_bytes': (_sz, [_i]*5),
+    'smd_conv3x3_headn_fwd': (_i, [_vp]*4 + [_i]*6 + [_vp]),
+    'smd_conv3x3_headn_bwd_data': (_i, [_vp]*4 + [_i]*6 + [_vp]),
+    'smd_conv3x3_headn_bwd_wgt': (_i, [_vp]*6 + [_sz] + [_i]*6 + [_vp]),
+    'smd_upsample_stack_fwd': (_i, [_vp]*3 + [_i]*5 + [_vp, _vp]),
+    'smd_upsample_stack_bwd': (_i, [_vp]*2 + [_i]*5 + [_vp]*3),
+    'smd_scale_mean_workspace_bytes': (_sz, [_vp, _i]),
+    'smd_scale_mean_fwd': (_i, [_vp]*2 + [_i]*2 + [_vp]*2 + [_sz, _vp]),
+    'smd_scale_mean_bwd': (_i, [_vp]*2 + [_i]*2 + [_vp]*3),
     'smd_conv3x3_thin_workspace_bytes': (_sz, [_i]*4),
     'smd_conv3x3_thin_fwd': (_i, [_vp]*3 + [_i]*4 + [_vp]),
     'smd_conv3x3_thin_bwd': (_i, [_vp]*6 + [_sz] + [_i]*4 + [_vp]),
@@ -173,3 +182,7 @@ def ptr_array(ptrs):
 
 def int_array(vals):
     return (C.c_int*len(vals))(*[int(v) for v in vals])
+
+
+def i64_array(vals):
+    return (C.c_longlong*len(vals))(*[int(v) for v in vals])

@@ -802,6 +802,98 @@ int smd_conv3x3_head_bwd(const void* xp, const float* weight, const float* y, co
   if (g_weight && workspace_bytes < smd_conv3x3_head_workspace_bytes(B, C, h, w)) return fail(SMD_E_WORKSPACE, "workspace too small");
   return check_launch(smd::launch_conv_head_bwd(xp, (act & SMD_HEAD_X_BF16) != 0, weight, y, g_y, g_xp, g_weight, g_bias, (float*)workspace, B, C, h, w, act & 1, (hipStream_t)stream), "conv3x3_head_bwd");
 }
+static bool headn_args_ok(int B, int C, int n, int h, int w, int act) {
+  const int a = act & 3;
+  return n >= 1 && n <= 4 && head_sizes_ok(B, C, h, w) && (act & ~(3 | SMD_HEADN_X_BF16)) == 0 && a != 3 && dec_sizes_ok((long long)B*n, h, w);
+}
+size_t smd_conv3x3_headn_workspace_bytes(int B, int C, int n, int h, int w) {
+  if (!headn_args_ok(B, C, n, h, w, 0)) return 0;
+  return align256(smd::conv_headn_partials(B, C, n, h, w)*sizeof(float));
+}
+int smd_conv3x3_headn_fwd(const void* xp, const float* weight, const float* bias, float* y, int B, int C, int n, int h, int w, int act, void* stream) {
+  if (!xp || !weight || !y) return fail(SMD_E_INVALID, "null pointer");
+  if (!headn_args_ok(B, C, n, h, w, act)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d n=%d h=%d w=%d act=%d (1 <= n <= 4)", B, C, n, h, w, act);
+  return check_launch(smd::launch_conv_headn_fwd(xp, (act & SMD_HEADN_X_BF16) != 0, weight, bias, y, B, C, n, h, w, act & 3, (hipStream_t)stream), "conv3x3_headn_fwd");
+}
+int smd_conv3x3_headn_bwd_data(const float* weight, const float* y, const float* g_y, void* g_xp, int B, int C, int n, int h, int w, int act, void* stream) {
+  if (!weight || !y || !g_y || !g_xp) return fail(SMD_E_INVALID, "null pointer");
+  if (!headn_args_ok(B, C, n, h, w, act)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d n=%d h=%d w=%d act=%d (1 <= n <= 4)", B, C, n, h, w, act);
+  return check_launch(smd::launch_conv_headn_bwd(nullptr, (act & SMD_HEADN_X_BF16) != 0, weight, y, g_y, g_xp, nullptr, nullptr, nullptr, B, C, n, h, w, act & 3,
+                                                 (hipStream_t)stream), "conv3x3_headn_bwd_data");
+}
+int smd_conv3x3_headn_bwd_wgt(const void* xp, const float* y, const float* g_y, float* g_weight, float* g_bias, void* workspace, size_t workspace_bytes,
+                              int B, int C, int n, int h, int w, int act, void* stream) {
+  if (!xp || !y || !g_y || !g_weight || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (!headn_args_ok(B, C, n, h, w, act)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d n=%d h=%d w=%d act=%d (1 <= n <= 4)", B, C, n, h, w, act);
+  if (workspace_bytes < smd_conv3x3_headn_workspace_bytes(B, C, n, h, w)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return check_launch(smd::launch_conv_headn_bwd(xp, (act & SMD_HEADN_X_BF16) != 0, nullptr, y, g_y, nullptr, g_weight, g_bias, (float*)workspace, B, C, n, h, w, act & 3,
+                                                 (hipStream_t)stream), "conv3x3_headn_bwd_wgt");
+}
+
+// Predictive-mask post-process and regularisers (smd_masks.hip)
+static int up_stack_check(int S, int b, int n, int h, int w) {
+  if (b < 1 || n < 1 || h < 1 || w < 1 || (long long)b*n > 65535 || (long long)h*w >= (1ll << 30)) return fail(SMD_E_INVALID, "invalid sizes b=%d n=%d h=%d w=%d (b*n <= 65535)", b, n, h, w);
+  if ((long long)S*b*n*h*w >= (1ll << 40)) return fail(SMD_E_INVALID, "output too large");
+  return SMD_OK;
+}
+int smd_upsample_stack_fwd(const float* const* x, const int* hs, const int* ws, int S, int b, int n, int h, int w, float* out, void* stream) {
+  if (!x || !out) return fail(SMD_E_INVALID, "null pointer");
+  if (int rc = up_stack_check(S, b, n, h, w)) return rc;
+  smd::ScaleSet sc;
+  if (int rc = fill_scales(sc, x, nullptr, hs, ws, nullptr, S)) return rc;
+  for (int s = 0; s < S; ++s) {
+    if (!x[s]) return fail(SMD_E_INVALID, "null input pointer for scale %d", s);
+    if ((long long)hs[s]*ws[s] >= (1ll << 30)) return fail(SMD_E_INVALID, "scale %d too large", s);
+  }
+  return check_launch(smd::launch_upsample_stack_fwd(sc, b*n, h, w, out, (hipStream_t)stream), "upsample_stack_fwd");
+}
+int smd_upsample_stack_bwd(const int* hs, const int* ws, int S, int b, int n, int h, int w, const float* g_out, float* const* g_x, void* stream) {
+  if (!g_out || !g_x) return fail(SMD_E_INVALID, "null pointer");
+  if (int rc = up_stack_check(S, b, n, h, w)) return rc;
+  smd::ScaleSet sc;
+  if (int rc = fill_scales(sc, nullptr, g_x, hs, ws, nullptr, S)) return rc;
+  long long blocks = 0;
+  for (int s = 0; s < S; ++s) {
+    if (!g_x[s]) return fail(SMD_E_INVALID, "null gradient pointer for scale %d", s);
+    if ((long long)hs[s]*ws[s] >= (1ll << 30)) return fail(SMD_E_INVALID, "scale %d too large", s);
+    blocks += ((long long)hs[s]*ws[s] + 255)/256;
+  }
+  if (blocks >= (1ll << 31)) return fail(SMD_E_INVALID, "too many source pixels");
+  return check_launch(smd::launch_upsample_stack_bwd(sc, b*n, h, w, g_out, (hipStream_t)stream), "upsample_stack_bwd");
+}
+static int fill_means(smd::MeanSet& ms, const float* const* x, float* const* g, const long long* numel, int S, int mode) {
+  if (S < 1 || S > SMD_MAX_SCALES) return fail(SMD_E_INVALID, "S=%d outside [1, %d]", S, SMD_MAX_SCALES);
+  if (!numel) return fail(SMD_E_INVALID, "null size array");
+  if (mode < SMD_MEAN_BCE_ONES || mode > SMD_MEAN_NEGATE) return fail(SMD_E_INVALID, "invalid mode %d", mode);
+  memset(&ms, 0, sizeof(ms));
+  ms.S = S;
+  for (int s = 0; s < S; ++s) {
+    if (numel[s] < 1) return fail(SMD_E_INVALID, "scale %d is empty", s);
+    ms.p[s] = x ? x[s] : nullptr; ms.g[s] = g ? g[s] : nullptr; ms.n[s] = numel[s];
+  }
+  if (smd::scale_mean_blocks(ms) < 1) return fail(SMD_E_INVALID, "too many elements");
+  return SMD_OK;
+}
+size_t smd_scale_mean_workspace_bytes(const long long* numel, int S) {
+  smd::MeanSet ms;
+  if (fill_means(ms, nullptr, nullptr, numel, S, 0)) return 0;
+  return 256 + align256((size_t)ms.first_block[SMD_MAX_SCALES]*sizeof(float));
+}
+int smd_scale_mean_fwd(const float* const* x, const long long* numel, int S, int mode, float* loss, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!x || !loss || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  smd::MeanSet ms;
+  if (int rc = fill_means(ms, x, nullptr, numel, S, mode)) return rc;
+  for (int s = 0; s < S; ++s) if (!x[s]) return fail(SMD_E_INVALID, "null input pointer for scale %d", s);
+  if (workspace_bytes < smd_scale_mean_workspace_bytes(numel, S)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return check_launch(smd::launch_scale_mean_fwd(ms, mode, (float*)((char*)workspace + 256), (unsigned*)workspace, loss, (hipStream_t)stream), "scale_mean_fwd");
+}
+int smd_scale_mean_bwd(const float* const* x, const long long* numel, int S, int mode, const float* g_loss, float* const* g_x, void* stream) {
+  if (!g_loss || !g_x || (mode == SMD_MEAN_BCE_ONES && !x)) return fail(SMD_E_INVALID, "null pointer");
+  smd::MeanSet ms;
+  if (int rc = fill_means(ms, x, g_x, numel, S, mode)) return rc;
+  for (int s = 0; s < S; ++s) if (!g_x[s] || (mode == SMD_MEAN_BCE_ONES && !x[s])) return fail(SMD_E_INVALID, "null pointer for scale %d", s);
+  return check_launch(smd::launch_scale_mean_bwd(ms, mode, g_loss, (hipStream_t)stream), "scale_mean_bwd");
+}
 static bool thin_sizes_ok(int B, int C, int h, int w) { return (C == 16 || C == 32) && head_sizes_ok(B, C, h, w) && dec_sizes_ok((long long)B*16, h, w) && B < 65536 && h + 2 < 4*65536; }
 size_t smd_conv3x3_thin_workspace_bytes(int B, int C, int h, int w) {
   if (!thin_sizes_ok(B, C, h, w)) return 0;

@@ -265,6 +265,24 @@ size_t conv_head_partials(int B, int C, int h, int w);
 hipError_t launch_conv_head_fwd(const void* xp, int x_bf16, const float* wgt, const float* bias, float* y, int B, int C, int h, int w, int act, hipStream_t st);
 hipError_t launch_conv_head_bwd(const void* xp, int x_bf16, const float* wgt, const float* y, const float* gy, void* g_xp, float* g_w, float* g_bias, float* partial,
                                 int B, int C, int h, int w, int act, hipStream_t st);
+// smd_conv_headn.hip: heads with 1..4 output channels (the predictive-mask decoder); act 0 identity, 1 sigmoid, 2 relu
+size_t conv_headn_partials(int B, int C, int N, int h, int w);
+hipError_t launch_conv_headn_fwd(const void* xp, int x_bf16, const float* wgt, const float* bias, float* y, int B, int C, int N, int h, int w, int act, hipStream_t st);
+hipError_t launch_conv_headn_bwd(const void* xp, int x_bf16, const float* wgt, const float* y, const float* gy, void* g_xp, float* g_w, float* g_bias, float* partial,
+                                 int B, int C, int N, int h, int w, int act, hipStream_t st);
+// smd_masks.hip: multi-scale, multi-channel bilinear up-sampling into a scale-major stack, and the mean over scales of per-scale means
+hipError_t launch_upsample_stack_fwd(const ScaleSet& sc, int planes, int h, int w, float* out, hipStream_t st);
+hipError_t launch_upsample_stack_bwd(const ScaleSet& sc, int planes, int h, int w, const float* g_out, hipStream_t st);
+struct MeanSet {   // S tensors of n[s] elements, passed by value; first_block: the launch's block prefix table (filled by the launcher)
+  const float* p[SMD_MAX_SCALES];
+  float* g[SMD_MAX_SCALES];
+  long long n[SMD_MAX_SCALES];
+  int first_block[SMD_MAX_SCALES + 1];
+  int S;
+};
+int scale_mean_blocks(MeanSet& ms);
+hipError_t launch_scale_mean_fwd(MeanSet ms, int mode, float* partial, unsigned* counter, float* loss, hipStream_t st);
+hipError_t launch_scale_mean_bwd(MeanSet ms, int mode, const float* g_loss, hipStream_t st);
 hipError_t launch_conv_thin_fwd(const float* xp, const float* wgt, float* y, int B, int C, int h, int w, hipStream_t st);
 size_t conv_thin_partials(int B, int C, int h, int w);
 hipError_t launch_conv_thin_bwd_wgt(const float* xp, const float* gy, float* g_w, float* partial, int B, int C, int h, int w, hipStream_t st);

@@ -16,7 +16,7 @@ from . import _lib
 from ._lib import FLAGS, REGR_FLAGS, SEL_MASKED, int_array, ptr_array
 from ._lib import call as _raw_call
 
-__all__ = ['conv3x3_mfma', 'conv3x3_wide', 'conv3x3_same', 'set_conv_route', 'conv_routes', 'loss_path_fused', 'crop_resize', 'disp_to_depth', 'image_recon_prep', 'PreparedFrames', 'image_recon_fused', 'image_recon_fused_disp', 'disp_smooth_fused', 'view_synth', 'photo_error', 'recon_reduce',
+__all__ = ['conv3x3_headn', 'upsample_stack', 'scale_mean', 'conv3x3_mfma', 'conv3x3_wide', 'conv3x3_same', 'set_conv_route', 'conv_routes', 'loss_path_fused', 'crop_resize', 'disp_to_depth', 'image_recon_prep', 'PreparedFrames', 'image_recon_fused', 'image_recon_fused_disp', 'disp_smooth_fused', 'view_synth', 'photo_error', 'recon_reduce',
            'lane_shift_selftest', 'recon_flags', 'regression_loss', 'elu_pad', 'elu_up_cat_pad', 'batch_norm_act', 'max_pool3x3s2', 'dwconv7x7', 'layer_norm_cf', 'pose_matrices', 'intrinsics', 'inv_intrinsics']
 
 
@@ -879,6 +879,141 @@ def conv3x3_head(xp, weight, bias=None, act: str | None = 'sigmoid'):
     output heads (src/networks/decoders/monodepth.py:52, 86-87).  xp (B,C,h+2,w+2) fp32 or bf16, weight (1,C,3,3), bias (1) or None -> (B,1,h,w) fp32; act 'sigmoid' | None."""
     if act not in ('sigmoid', 'none', None): raise ValueError(f"act must be 'sigmoid' or None, got {act!r}")
     return _Conv3x3Head.apply(xp, weight, bias, 1 if act == 'sigmoid' else 0)
+
+
+_HEADN_ACT = {None: 0, 'none': 0, 'sigmoid': 1, 'relu': 2}
+
+
+class _Conv3x3HeadN(torch.autograd.Function):
+    """`act(conv3x3(xp, weight (n,C,3,3)) + bias)`, 1 <= n <= 4, on an already reflection-padded input (`smd_conv3x3_headn_*`): the mask decoder's output heads.
+    The padded activation is read once for all n channels.  xp may be bfloat16; the output, the weights' gradient and every sum stay fp32."""
+    @staticmethod
+    def forward(ctx, xp, weight, bias, act):
+        xp = _check_fb('xp', xp)
+        if xp.ndim != 4 or xp.shape[2] < 4 or xp.shape[3] < 4: raise ValueError(f'expected a padded (B,C,h+2,w+2) with h, w >= 2, got {tuple(xp.shape)}')
+        B, C, H, W = xp.shape
+        if not isinstance(weight, torch.Tensor) or weight.ndim != 4 or not 1 <= weight.shape[0] <= 4:
+            raise ValueError(f'conv3x3_headn serves 1 to 4 output channels, got a weight of shape {tuple(getattr(weight, "shape", ()))}')
+        n = weight.shape[0]
+        weight = _check('weight', weight, (n, C, 3, 3))
+        if bias is not None: bias = _check('bias', bias, (n,))
+        y = torch.empty((B, n, H - 2, W - 2), device=xp.device, dtype=torch.float32)
+        act = int(act) | (4 if xp.dtype == _BF else 0)            # SMD_HEADN_X_BF16
+        call('smd_conv3x3_headn_fwd', xp.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(), B, C, n, H - 2, W - 2, act, _stream())
+        ctx.save_for_backward(xp, weight, y); ctx.act, ctx.has_bias = act, bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        xp, weight, y = ctx.saved_tensors
+        dev = _on(xp)
+        B, C, H, W = xp.shape
+        n = weight.shape[0]
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        g_y = _check('grad(y)', g_y.float(), (B, n, H - 2, W - 2))
+        g_xp = g_w = g_b = None
+        if need_x:
+            g_xp = torch.empty_like(xp)
+            call('smd_conv3x3_headn_bwd_data', weight.data_ptr(), y.data_ptr(), g_y.data_ptr(), g_xp.data_ptr(), B, C, n, H - 2, W - 2, ctx.act, _stream())
+        if need_w or need_b:
+            g_w = torch.empty_like(weight)
+            g_b = torch.empty(n, device=dev, dtype=torch.float32) if need_b else None
+            nbytes = _lib.lib.smd_conv3x3_headn_workspace_bytes(B, C, n, H - 2, W - 2)
+            ws = torch.empty(max(nbytes, 256), device=dev, dtype=torch.uint8)
+            call('smd_conv3x3_headn_bwd_wgt', xp.data_ptr(), y.data_ptr(), g_y.data_ptr(), g_w.data_ptr(), g_b.data_ptr() if g_b is not None else None,
+                 ws.data_ptr(), nbytes, B, C, n, H - 2, W - 2, ctx.act, _stream())
+        return g_xp, (g_w if need_w else None), g_b, None
+
+
+def conv3x3_headn(xp, weight, bias=None, act: str | None = 'sigmoid'):
+    """`act(F.conv2d(xp, weight, bias))` for 1 to 4 output channels and an input that is already reflection-padded (`elu_pad`'s output): the output heads of
+    the predictive-mask decoder (src/networks/depth.py:108-114, src/networks/decoders/monodepth.py:52, 86-87).
+    xp (B,C,h+2,w+2) fp32 or bf16, weight (n,C,3,3), bias (n) or None -> (B,n,h,w) fp32; act 'sigmoid' | 'relu' | None."""
+    if act not in _HEADN_ACT: raise ValueError(f"act must be 'sigmoid', 'relu' or None, got {act!r}")
+    return _Conv3x3HeadN.apply(xp, weight, bias, _HEADN_ACT[act])
+
+
+class _UpsampleStack(torch.autograd.Function):
+    """`smd_upsample_stack_*`: S tensors (b,n,hs,ws) -> the scale-major stack (S,b,n,h,w), bilinear, align_corners=False; one launch each way."""
+    @staticmethod
+    def forward(ctx, size, *xs):
+        h, w = size
+        xs = [_check(f'x[{i}]', x) for i, x in enumerate(xs)]
+        b, n = xs[0].shape[:2]
+        for x in xs:
+            if x.ndim != 4 or tuple(x.shape[:2]) != (b, n): raise ValueError(f'every scale must be (b,n,hs,ws) with b={b}, n={n}, got {tuple(x.shape)}')
+        S, hs, ws = len(xs), [x.shape[2] for x in xs], [x.shape[3] for x in xs]
+        out = torch.empty((S, b, n, h, w), device=xs[0].device, dtype=torch.float32)
+        call('smd_upsample_stack_fwd', ptr_array([x.data_ptr() for x in xs]), int_array(hs), int_array(ws), S, b, n, h, w, out.data_ptr(), _stream())
+        ctx.meta, ctx.dev = (hs, ws, S, b, n, h, w), xs[0].device
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        hs, ws, S, b, n, h, w = ctx.meta
+        g_out = _check('grad(out)', g_out, (S, b, n, h, w))
+        _on(g_out)
+        gs = [torch.empty((b, n, hs[s], ws[s]), device=g_out.device, dtype=torch.float32) for s in range(S)]
+        call('smd_upsample_stack_bwd', int_array(hs), int_array(ws), S, b, n, h, w, g_out.data_ptr(), ptr_array([g.data_ptr() for g in gs]), _stream())
+        return (None, *gs)
+
+
+def upsample_stack(xs, size):
+    """xs: sequence of (b,n,hs,ws) -> (S,b,n,h,w): `F.interpolate(x, size, mode='bilinear', align_corners=False)` of every scale, stacked scale-major, in one launch
+    (`ops.interpolate_like` per scale, src/core/trainer.py:323-324).  CPU tensors take the torch expression (host-logic tests; the training path is on the GPU)."""
+    xs, size = list(xs), tuple(int(v) for v in size)
+    if not xs: raise ValueError('no scales given')
+    if not xs[0].is_cuda: return torch.stack([torch.nn.functional.interpolate(x, size=size, mode='bilinear', align_corners=False) for x in xs])
+    return _UpsampleStack.apply(size, *xs)
+
+
+_MEAN_MODES = {'bce_ones': 0, 'identity': 1, 'negate': 2}
+_mean_ws = {}    # (device, stream) -> workspace whose arrival counter is zero between calls (the kernel leaves it so)
+
+
+def _scale_mean_ws(dev, nbytes):
+    key = (dev, _stream())
+    ws = _mean_ws.get(key)
+    if ws is None or ws.numel() < nbytes: ws = _mean_ws[key] = torch.zeros(max(nbytes, 4096), device=dev, dtype=torch.uint8)
+    return ws
+
+
+class _ScaleMean(torch.autograd.Function):
+    """`smd_scale_mean_*`: mean over the tensors of the mean of f(x) over each tensor's elements."""
+    @staticmethod
+    def forward(ctx, mode, *xs):
+        xs = [_check(f'x[{i}]', x) for i, x in enumerate(xs)]
+        numel = _lib.i64_array([x.numel() for x in xs])
+        nbytes = _lib.lib.smd_scale_mean_workspace_bytes(numel, len(xs))
+        if nbytes == 0: raise ValueError(f'scale_mean serves 1 to {_lib.MAX_SCALES} non-empty tensors')
+        ws = _scale_mean_ws(xs[0].device, nbytes)
+        loss = torch.empty((), device=xs[0].device, dtype=torch.float32)
+        call('smd_scale_mean_fwd', ptr_array([x.data_ptr() for x in xs]), numel, len(xs), mode, loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+        ctx.save_for_backward(*xs); ctx.mode = mode
+        return loss
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        xs = ctx.saved_tensors
+        _on(xs[0])
+        g_loss = g_loss.float().contiguous()
+        gs = [torch.empty_like(x) for x in xs]
+        call('smd_scale_mean_bwd', ptr_array([x.data_ptr() for x in xs]), _lib.i64_array([x.numel() for x in xs]), len(xs), ctx.mode, g_loss.data_ptr(),
+             ptr_array([g.data_ptr() for g in gs]), _stream())
+        return (None, *gs)
+
+
+def scale_mean(xs, mode: str):
+    """mean_s(mean(f(x_s))) over a sequence of tensors of any sizes, in one launch (`handlers.disp_mask` / `disp_occ`, src/core/handlers.py:314-347).
+    mode 'bce_ones': f = binary cross-entropy against ones (`MaskReg`, src/regularizers/mask.py:29); 'identity' / 'negate': f(x) = x / -x (`OccReg`,
+    src/regularizers/occlusion.py:39).  CPU tensors take the torch expression."""
+    if mode not in _MEAN_MODES: raise ValueError(f'mode must be one of {tuple(_MEAN_MODES)}, got {mode!r}')
+    xs = list(xs)
+    if not xs: raise ValueError('no tensors given')
+    if not xs[0].is_cuda:
+        if mode == 'bce_ones': return torch.stack([torch.nn.functional.binary_cross_entropy(x, torch.ones_like(x)) for x in xs]).mean()
+        return torch.stack([(x.mean() if mode == 'identity' else -x.mean()) for x in xs]).mean()
+    return _ScaleMean.apply(_MEAN_MODES[mode], *xs)
 
 
 class _Conv3x3Thin(torch.autograd.Function):

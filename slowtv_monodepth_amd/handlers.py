@@ -16,7 +16,7 @@ import torch
 
 from . import functional as F
 
-__all__ = ['image_recon', 'disp_smooth', 'feat_recon', 'autoenc_recon', 'stereo_const', 'depth_regr', 'ScaleDict', 'LazyDepths']
+__all__ = ['image_recon', 'disp_smooth', 'disp_mask', 'disp_occ', 'feat_recon', 'autoenc_recon', 'stereo_const', 'depth_regr', 'ScaleDict', 'LazyDepths']
 
 
 class ScaleDict(dict):
@@ -111,7 +111,10 @@ def _image_recon_generic(crit, depths, imgs, supp_imgs, Ts, Ks, K_inv, noise, wa
     if K_inv is None: K_inv = torch.linalg.inv(Ks) if Ks.requires_grad else F.inv_intrinsics(Ks)
     n, S, b, dep, tgt, src, T, K, Ki = _expand_views(depths, imgs, supp_imgs, Ts, Ks, K_inv)
     warp = F.view_synth(src.flatten(0, 1), dep[None].expand(n, *dep.shape).flatten(0, 1), T, K, Ki)[0].unflatten(0, (n, S*b))
-    mask = torch.stack(list(masks.values())).flatten(0, 1) if masks is not None else None    # (S*b,n,h,w), handlers.py:47
+    mask = None
+    if masks is not None:                                                                    # (S*b,n,h,w), handlers.py:47
+        stacked = getattr(masks, 'stacked', None)                                            # (a `ScaleDict` over `upsample_stack`'s output: no copy)
+        mask = (stacked if stacked is not None else torch.stack(list(masks.values()))).flatten(0, 1)
     loss, ld = crit(warp, tgt, source=src, mask=mask, noise=noise)
     out = {}
     if crit.use_automask: out['automask'] = ld['automask'].unflatten(0, (S, b))[0]
@@ -201,3 +204,24 @@ def disp_smooth(crit, disps: dict, imgs: torch.Tensor, *, want_aux: bool = True,
     if getattr(crit, 'use_blur', False): loss, dg, ig = F.disp_smooth_blurred(disps, imgs, use_edges=crit.use_edges, want_aux=want_aux)
     else: loss, dg, ig = F.disp_smooth_fused(disps, imgs, use_edges=crit.use_edges, want_aux=want_aux, use_laplacian=getattr(crit, 'use_laplacian', False), prepared=prepared)
     return loss, ({'disp_grad': dg, 'image_grad': ig} if want_aux and dg is not None else {})
+
+
+def _scale_mean_or_crit(crit, xs: dict, cls, mode: str):
+    """mean over the scales of `crit(x_s)`: one `scale_mean` launch when the criterion is the registered class (a subclass may compute something else)."""
+    if type(crit) is cls: return F.scale_mean([v.float() for v in xs.values()], mode), {}
+    ls = {k: crit(v) for k, v in xs.items()}
+    return torch.stack([v[0] for v in ls.values()]).mean(), next(iter(ls.values()))[1]
+
+
+def disp_occ(crit, disps: dict):
+    """Occlusion regularisation of the raw (not up-sampled) multi-scale disparities: mean_s(crit(disp_s)) (src/core/handlers.py:314-329).
+    :return: (loss, {})"""
+    from .regularizers import OccReg
+    return _scale_mean_or_crit(crit, disps, OccReg, 'negate' if getattr(crit, 'invert', False) else 'identity')
+
+
+def disp_mask(crit, masks: dict):
+    """Predictive-mask regularisation of the raw (not up-sampled) multi-scale masks: mean_s(crit(mask_s)) (src/core/handlers.py:332-347).
+    :return: (loss, {})"""
+    from .regularizers import MaskReg
+    return _scale_mean_or_crit(crit, masks, MaskReg, 'bce_ones')

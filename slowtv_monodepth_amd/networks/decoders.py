@@ -82,6 +82,9 @@ class MonodepthDecoder(nn.Module):
                 m = self.out[str(i)]
                 if self.out_ch == 1 and isinstance(self.act, (nn.Sigmoid, nn.Identity)):   # a one-channel head is a stencil: smd_conv3x3_head_* (fp32 or bf16 activation in, fp32 out)
                     out[i] = HF.conv3x3_head(xp, m.weight.float(), m.bias.float() if m.bias is not None else None, 'sigmoid' if isinstance(self.act, nn.Sigmoid) else None)
+                elif 1 <= self.out_ch <= 4 and isinstance(self.act, (nn.Sigmoid, nn.ReLU, nn.Identity)):   # a few channels (or one with relu) are still a stencil: smd_conv3x3_headn_* (the mask decoder)
+                    act = 'sigmoid' if isinstance(self.act, nn.Sigmoid) else ('relu' if isinstance(self.act, nn.ReLU) else None)
+                    out[i] = HF.conv3x3_headn(xp, m.weight.float(), m.bias.float() if m.bias is not None else None, act)
                 else:
                     out[i] = self.act(F.conv2d(xp, m.weight, m.bias))
         return out

@@ -35,6 +35,21 @@ class HipLossBackend:
         depth_up, disp_up = F.disp_to_depth([disps[k].float() for k in keys], size, min_depth, max_depth, want_disp_up=want_disp_up)
         return ScaleDict.from_stack(keys, disp_up), ScaleDict.from_stack(keys, depth_up)
 
+    def upsample_masks(self, masks: dict, size):
+        """`fwd['mask']` {s: (b,n,hs,ws)} -> `fwd['mask_up']` {s: (b,n,h,w)}, views of ONE scale-major stack written by one launch (`functional.upsample_stack`)."""
+        from . import functional as F
+        from .handlers import ScaleDict
+        keys = list(masks.keys())
+        return ScaleDict.from_stack(keys, F.upsample_stack([masks[k].float() for k in keys], size))
+
+    def disp_occ(self, crit, disps):
+        from . import handlers
+        return handlers.disp_occ(crit, disps)
+
+    def disp_mask(self, crit, masks):
+        from . import handlers
+        return handlers.disp_mask(crit, masks)
+
     def image_recon(self, crit, synth, depths, masks, imgs, supp_imgs, Ts, Ks, want_warp=True, K_inv=None, prepared=None):
         from . import handlers
         self.last_sel, self.last_path = None, 'handlers: image_recon + disp_smooth as separate autograd nodes'
@@ -162,6 +177,14 @@ class MonoDepthModule(nn.Module):
         for k, (net_key, what) in needs.items():
             if k in self.losses and (net_key is None or net_key not in self.nets):
                 raise NotImplementedError(f'loss "{k}" needs {what}, which this package does not build; the handler `handlers.{k}` can be called directly')
+        # Predictive masks: the criterion that consumes them and the decoder that produces them must be configured together (reference cfg/default.yaml
+        # sets `net.depth.mask_name` and `loss.img_recon.mask_name` side by side); refuse a half here instead of a shape error inside the loss.
+        depth_mask = getattr(self.nets['depth'], 'mask_name', None) if 'depth' in self.nets else None
+        crit_mask = getattr(self.losses['img_recon'], 'mask_name', None) if 'img_recon' in self.losses else None
+        if 'img_recon' in self.losses and depth_mask != crit_mask:
+            raise ValueError(f'net.depth.mask_name ({depth_mask!r}) and loss.img_recon.mask_name ({crit_mask!r}) must agree: the mask decoder produces what the masked criterion consumes')
+        if 'disp_mask' in self.losses and not depth_mask:
+            raise ValueError('loss "disp_mask" needs a depth network with `mask_name` (fwd["mask"])')
         self.synth = None
         self.scales = self.nets['depth'].out_scales
         self.n_scales = len(self.scales)
@@ -262,6 +285,13 @@ class MonoDepthModule(nn.Module):
         disp_up, fwd['depth_up'] = self.backend.postprocess(fwd['disp'], tuple(x['imgs'].shape[-2:]), self.min_depth, self.max_depth,
                                                             want_disp_up=self.want_aux)
         if disp_up is not None: fwd['disp_up'] = disp_up   # only the image logger reads the un-scaled up-sampled disparity
+        if fwd.get('mask') is not None:   # predictive masks, one channel per support frame (src/core/trainer.py:323-324)
+            n_mask, n_supp = next(iter(fwd['mask'].values())).shape[1], len(x['supp_idxs'])
+            if n_mask not in (1, n_supp):
+                raise ValueError(f'the mask decoder emits {n_mask} channels (net.depth.num_ch_mask) for {n_supp} support frames: they must match')
+            fn = getattr(self.backend, 'upsample_masks', None)
+            if fn is not None: fwd['mask_up'] = fn(fwd['mask'], tuple(x['imgs'].shape[-2:]))
+            else: fwd['mask_up'] = {k: torch.nn.functional.interpolate(v, size=tuple(x['imgs'].shape[-2:]), mode='bilinear', align_corners=False) for k, v in fwd['mask'].items()}
         # a stereo support (index 0) brings its known pose with the batch instead of a predicted one (src/core/trainer.py:347)
         leaves, Ts_all = fwd.get('_pose_leaves'), fwd.get('_Ts_all')
         if (leaves is not None and Ts_all is not None and [int(i) for i in x['supp_idxs']] == list(leaves[3])
@@ -307,6 +337,13 @@ class MonoDepthModule(nn.Module):
                     from . import handlers
                     l, ld = handlers.stereo_const(crit, self.synth, fwd['disp_up'], fwd['depth_up'], fwd['disp_stereo_up'], fwd['depth_stereo_up'],
                                                   y['T_stereo'], fwd.get('K', y['K']))
+                elif k == 'disp_occ':        # occlusion regularisation of the raw disparities, src/core/trainer.py:450-452
+                    from . import handlers
+                    l, ld = getattr(self.backend, 'disp_occ', handlers.disp_occ)(crit, fwd['disp'])
+                elif k == 'disp_mask':       # predictive-mask regularisation, src/core/trainer.py:455-458
+                    if 'mask' not in fwd: raise KeyError('Missing masks in predictions.')
+                    from . import handlers
+                    l, ld = getattr(self.backend, 'disp_mask', handlers.disp_mask)(crit, fwd['mask'])
                 else:
                     raise ValueError(f'Missing loss key: "{k}"')
             loss = loss + self.weights[k]*l
