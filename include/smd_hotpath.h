@@ -388,6 +388,20 @@ int smd_conv3x3z_mfma_bwd_data(const float* g_y, const void* wp_bwd, float* g_x,
 int smd_conv3x3z_mfma_bwd_weight(const float* x, const float* g_y, float* g_weight, void* workspace, size_t workspace_bytes,
                                  int B, int C, int CO, int h, int w, int pieces, void* stream);
 
+/* The ResNet stem (ABI 8; reference: timm's `conv1 = nn.Conv2d(in_chans, 64, 7, stride=2, padding=3, bias=False)` of the encoders built at
+ * src/networks/depth.py:95-98, src/networks/pose.py:39-41): y (B,64,Ho,Wo) = conv2d(x (B,C,H,W), weight (64,C,7,7), stride 2, padding 3), Ho = (H - 1)/2 + 1,
+ * Wo = (W - 1)/2 + 1, fp32 NCHW in and out, zero padding inside the kernels, on the split-bf16 matrix-core form of smd_conv3x3_mfma_* (three pieces, six
+ * products: fp32-class results).  smd_conv7x7s2_pack writes the forward's weight fragments (smd_conv7x7s2_packed_bytes(C, CO) bytes; part of every forward);
+ * smd_conv7x7s2_bwd_weight leaves g_weight (64,C,7,7) from x and g_y through per-block sums and a fixed-order fp64 second stage in a workspace of
+ * smd_conv7x7s2_workspace_bytes.  No data gradient (the input is the image).  Served: CO == 64 with C == 3 or 6, any B, H, W >= 1 within one sample's x and
+ * y under 2 G elements; both queries return 0 for anything else and the calls SMD_E_UNSUPPORTED / SMD_E_INVALID, nothing launched.  Deterministic. */
+size_t smd_conv7x7s2_packed_bytes(int C, int CO);
+size_t smd_conv7x7s2_workspace_bytes(int B, int C, int CO, int H, int W);
+int smd_conv7x7s2_pack(const float* weight, void* wp, int C, int CO, void* stream);
+int smd_conv7x7s2_fwd(const float* x, const void* wp, float* y, int B, int C, int CO, int H, int W, void* stream);
+int smd_conv7x7s2_bwd_weight(const float* x, const float* g_y, float* g_weight, void* workspace, size_t workspace_bytes,
+                             int B, int C, int CO, int H, int W, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Producer side of the path: training-mode BatchNorm2d of the ResNet encoders fused with the residual add and ReLU
  * that follow it (timm resnet blocks built at src/networks/depth.py:95-98, src/networks/pose.py:39-41;

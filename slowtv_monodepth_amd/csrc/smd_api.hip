@@ -1010,6 +1010,36 @@ int smd_conv3x3z_mfma_bwd_weight(const float* x, const float* g_y, float* g_weig
   if (workspace_bytes < smd_conv3x3z_mfma_workspace_bytes(B, C, CO, h, w)) return fail(SMD_E_WORKSPACE, "workspace too small");
   return check_launch(smd::launch_conv_mfma_z_bwd_wgt(x, g_y, g_weight, (float*)workspace, B, C, CO, h, w, pieces, (hipStream_t)stream), "conv3x3z_mfma_bwd_weight");
 }
+// the ResNet stem: conv2d(x (B,C,H,W), weight (64,C,7,7), stride 2, padding 3), C = 3 | 6 (smd_conv_stem.hip)
+static bool stem_sizes_ok(int B, int C, int H, int W) {
+  if (B < 1 || B > 65535 || C < 1 || H < 1 || W < 1) return false;
+  const long long ho = (H - 1)/2 + 1, wo = (W - 1)/2 + 1;
+  return (long long)C*H*W < (1ll << 31) && 64*ho*wo < (1ll << 31) && (ho + 3)/4 <= 65535;
+}
+size_t smd_conv7x7s2_packed_bytes(int C, int CO) { return smd::conv_stem_served(C, CO) ? smd::conv_stem_packed_bytes(C) : 0; }
+size_t smd_conv7x7s2_workspace_bytes(int B, int C, int CO, int H, int W) {
+  if (!smd::conv_stem_served(C, CO) || !stem_sizes_ok(B, C, H, W)) return 0;
+  return align256(smd::conv_stem_wgrad_floats(B, C, H, W)*sizeof(float));
+}
+int smd_conv7x7s2_pack(const float* weight, void* wp, int C, int CO, void* stream) {
+  if (!weight || !wp) return fail(SMD_E_INVALID, "null pointer");
+  if (!smd::conv_stem_served(C, CO)) return fail(SMD_E_UNSUPPORTED, "the stem kernels serve CO == 64 with C == 3 | 6, not C=%d CO=%d", C, CO);
+  return check_launch(smd::launch_conv_stem_pack(weight, wp, C, (hipStream_t)stream), "conv7x7s2_pack");
+}
+int smd_conv7x7s2_fwd(const float* x, const void* wp, float* y, int B, int C, int CO, int H, int W, void* stream) {
+  if (!x || !wp || !y) return fail(SMD_E_INVALID, "null pointer");
+  if (!smd::conv_stem_served(C, CO)) return fail(SMD_E_UNSUPPORTED, "the stem kernels serve CO == 64 with C == 3 | 6, not C=%d CO=%d", C, CO);
+  if (!stem_sizes_ok(B, C, H, W)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d H=%d W=%d", B, C, H, W);
+  return check_launch(smd::launch_conv_stem_fwd(x, wp, y, B, C, H, W, (hipStream_t)stream), "conv7x7s2_fwd");
+}
+int smd_conv7x7s2_bwd_weight(const float* x, const float* g_y, float* g_weight, void* workspace, size_t workspace_bytes,
+                             int B, int C, int CO, int H, int W, void* stream) {
+  if (!x || !g_y || !g_weight || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (!smd::conv_stem_served(C, CO)) return fail(SMD_E_UNSUPPORTED, "the stem kernels serve CO == 64 with C == 3 | 6, not C=%d CO=%d", C, CO);
+  if (!stem_sizes_ok(B, C, H, W)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d H=%d W=%d", B, C, H, W);
+  if (workspace_bytes < smd_conv7x7s2_workspace_bytes(B, C, CO, H, W)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return check_launch(smd::launch_conv_stem_bwd_wgt(x, g_y, g_weight, (float*)workspace, B, C, H, W, (hipStream_t)stream), "conv7x7s2_bwd_weight");
+}
 int smd_elu_up_cat_pad_fwd(const void* a, const float* bias, const void* skip, void* out, int B, int Ca, int Cs, int h, int w, int dtypes, void* stream) {
   if (!a || !out || (Cs > 0 && !skip)) return fail(SMD_E_INVALID, "null pointer");
   if (B < 1 || Ca < 1 || Cs < 0 || h < 1 || w < 1 || !dec_sizes_ok((long long)B*(Ca + Cs), 2*h, 2*w))

@@ -303,6 +303,13 @@ size_t conv_mfma_z_split_elems(int B, int C, int CO, int h, int w);           //
 hipError_t launch_conv_mfma_z_fwd(const float* x, const void* wp_fwd, float* y, float* split_ws, int B, int C, int CO, int h, int w, int pieces, hipStream_t st);
 hipError_t launch_conv_mfma_z_bwd_data(const float* gy, const void* wp_bwd, float* g_x, float* split_ws, int B, int C, int CO, int h, int w, int pieces, hipStream_t st);
 hipError_t launch_conv_mfma_z_bwd_wgt(const float* x, const float* gy, float* g_w, float* partial, int B, int C, int CO, int h, int w, int pieces, hipStream_t st);
+// smd_conv_stem.hip: the ResNet stem (7x7, stride 2, padding 3, 64 output channels; C = 3 | 6) on the split-bf16 matrix-core form, fp32 NCHW tensors
+bool conv_stem_served(int C, int CO);
+size_t conv_stem_packed_bytes(int C);
+size_t conv_stem_wgrad_floats(int B, int C, int H, int W);                    // the blocks' partial sets + the finalize's fp64 slices
+hipError_t launch_conv_stem_pack(const float* w, void* wp, int C, hipStream_t st);
+hipError_t launch_conv_stem_fwd(const float* x, const void* wp, float* y, int B, int C, int H, int W, hipStream_t st);
+hipError_t launch_conv_stem_bwd_wgt(const float* x, const float* gy, float* g_w, float* partial, int B, int C, int H, int W, hipStream_t st);
 size_t decoder_bias_partials(int B, int C, int h, int w);
 hipError_t launch_elu_pad_fwd(const void* x, const float* bias, void* out, int B, int C, int h, int w, int apply_elu, int dt, hipStream_t st);
 hipError_t launch_elu_pad_bwd(const void* x, const float* bias, const void* g_out, void* g_x, float* g_bias, float* ws, int B, int C, int h, int w,

@@ -1083,6 +1083,7 @@ def _conv_static_rule(op, B, C, CO, h, w):
     px = B*h*w
     if op.endswith('_bf16'): return CO == 16           # (bf16 tensors: MIOpen's bf16 kernels serve the wide layers; the thin stage is the stencil-like case)
     if op.endswith('_z'): return _conv_static_rule_z(op[:-2], B, C, CO, h, w)
+    if op.endswith('_s'): return px >= 20000           # (the 7x7 stride-2 stems, h x w the INPUT size: profiles/stem_convs.txt)
     if CO == 16: return op != 'wgt'
     coarse = w <= 80 and C >= 256                      # (row-band tiles: 1.18-1.59 x forward, 1.09-1.74 x data gradient, 0.92-1.37 x weight gradient)
     if op == 'fwd': return (px >= 20000 and C*CO <= 128*64) or (coarse and px >= 1000)
@@ -1273,6 +1274,63 @@ def conv3x3_same(x, weight):
     (`smd_conv3x3z_mfma_*`, the padding done inside them) or MIOpen, as `_conv_route` says under `fwd_z` / `data_z` / `wgt_z` (`set_conv_route('mfma')`
     pins the kernels); channel counts or sizes the kernels do not take go to MIOpen."""
     return _Conv3x3Wide.apply(x, weight, 3, False, True)
+
+
+class _Conv7x7s2Stem(torch.autograd.Function):
+    """`F.conv2d(x, weight (64,C,7,7), stride=2, padding=3)`, the ResNet stem: forward and weight gradient on the split-bf16 MFMA kernels
+    (`smd_conv7x7s2_*`, C = 3 | 6) or MIOpen, as `_conv_route` says under `fwd_s` / `wgt_s`; shapes the kernels do not serve go to MIOpen.  The input is
+    normally the image; a data gradient, where asked for, is ATen's."""
+    @staticmethod
+    def forward(ctx, x, weight):
+        x = _check('x', x)
+        if x.ndim != 4: raise ValueError(f'expected (B,C,H,W), got {tuple(x.shape)}')
+        B, C, H, W = x.shape
+        if weight.ndim != 4 or tuple(weight.shape[1:]) != (C, 7, 7): raise ValueError(f'weight: expected (CO,{C},7,7), got {tuple(weight.shape)}')
+        CO = weight.shape[0]
+        weight = _check('weight', weight, (CO, C, 7, 7))
+        ho, wo = (H - 1)//2 + 1, (W - 1)//2 + 1
+        served = _lib.lib.smd_conv7x7s2_workspace_bytes(B, C, CO, H, W) > 0
+        y = torch.empty((B, CO, ho, wo), device=x.device, dtype=torch.float32)
+
+        def run_mfma():                                     # the pack included: every call pays it
+            wp = torch.empty(_lib.lib.smd_conv7x7s2_packed_bytes(C, CO), device=x.device, dtype=torch.uint8)
+            call('smd_conv7x7s2_pack', weight.data_ptr(), wp.data_ptr(), C, CO, _stream())
+            call('smd_conv7x7s2_fwd', x.data_ptr(), wp.data_ptr(), y.data_ptr(), B, C, CO, H, W, _stream())
+        run_ref = lambda: torch.conv2d(x, weight, None, 2, 3)
+        if not (served and _routed('fwd_s', B, C, CO, H, W, False, run_mfma, run_ref) and _ran(False, run_mfma)): y = run_ref()
+        ctx.save_for_backward(x, weight)
+        ctx.served = served
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        x, weight = ctx.saved_tensors
+        dev = _on(x)
+        B, C, H, W = x.shape
+        CO = weight.shape[0]
+        need_x, need_w = ctx.needs_input_grad
+        g_y = _check('grad(y)', g_y, (B, CO, (H - 1)//2 + 1, (W - 1)//2 + 1))
+        cb = lambda mask: torch.ops.aten.convolution_backward(g_y, x, weight, None, [2, 2], [3, 3], [1, 1], False, [0, 0], 1, mask)
+        g_x = cb([True, False, False])[0] if need_x else None
+        g_w = None
+        if need_w:
+            g_w = torch.empty_like(weight)
+
+            def run_wgt():
+                nws = _lib.lib.smd_conv7x7s2_workspace_bytes(B, C, CO, H, W)
+                ws = torch.empty(max(nws, 256), device=dev, dtype=torch.uint8)
+                call('smd_conv7x7s2_bwd_weight', x.data_ptr(), g_y.data_ptr(), g_w.data_ptr(), ws.data_ptr(), nws, B, C, CO, H, W, _stream())
+            ref_wgt = lambda: cb([False, True, False])[1]
+            if not (ctx.served and _routed('wgt_s', B, C, CO, H, W, False, run_wgt, ref_wgt) and _ran(False, run_wgt)): g_w = ref_wgt()
+        return g_x, g_w
+
+
+def conv7x7s2_stem(x, weight):
+    """`F.conv2d(x, weight (CO,C,7,7), stride=2, padding=3)`, bias-free: the ResNet encoders' stem (`conv1` of the timm ResNets built at
+    src/networks/depth.py:95-98, src/networks/pose.py:39-41).  x (B,C,H,W) fp32 -> (B,CO,(H-1)//2+1,(W-1)//2+1) fp32.  CO = 64 with C = 3 or 6: forward and
+    weight gradient on the split-bf16 MFMA kernels (`smd_conv7x7s2_*`) or MIOpen, per operator and shape (`_conv_route`, ops `fwd_s` / `wgt_s`;
+    `set_conv_route('mfma')` pins the kernels); any other channel count goes to MIOpen."""
+    return _Conv7x7s2Stem.apply(x, weight)
 
 
 class _EluUpCatPad(torch.autograd.Function):

@@ -65,6 +65,16 @@ def _conv3x3(conv: nn.Conv2d, x):
     return conv(x)
 
 
+def _stem(conv: nn.Conv2d, x):
+    """The 7x7 stride-2 stem under the gate of `_conv3x3`: through `conv7x7s2_stem` (split-bf16 MFMA kernels or MIOpen, per operator and shape);
+    anywhere else the module itself."""
+    if (BatchNormAct2d.fused_enabled and x.is_cuda and x.dtype == torch.float32 and conv.weight.dtype == torch.float32
+            and not torch.is_autocast_enabled() and x.is_contiguous()):
+        from .. import functional as HF
+        return HF.conv7x7s2_stem(x, conv.weight)
+    return conv(x)
+
+
 class BasicBlock(nn.Module):
     def __init__(self, cin, cout, stride):
         super().__init__()
@@ -119,7 +129,7 @@ class ResNetFeatures(nn.Module):
             if isinstance(m, nn.Conv2d): nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
 
     def forward(self, x):
-        x = self.bn1(self.conv1(x), relu=True)
+        x = self.bn1(_stem(self.conv1, x), relu=True)
         feats = [x]
         if BatchNormAct2d.fused_enabled and x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled() and x.is_contiguous():
             from .. import functional as HF
