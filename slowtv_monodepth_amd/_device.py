@@ -1,0 +1,54 @@
+"""Which device's stream a launch goes to, and the operand checks every operator starts with.  Private: `functional` and `conv_ops` import it."""
+from __future__ import annotations
+
+import threading
+
+import torch
+
+from ._lib import call as _raw_call
+
+# Device of the operands of the operator this THREAD is executing: launches go to ITS current stream.  Thread-local, and set at
+# the top of every forward (by `_check`) AND every backward (by `_on`): autograd runs the backward of each device on its own
+# thread and has already made that device current there, so a process-wide "last validated device" would send the backward of
+# one GPU's graph to another GPU's stream as soon as two devices are used in one process.  Exactly ONE such object exists (every
+# module imports it from here): with a second, one module's `_check` and another's `_stream()` would disagree about the device.
+_tls = threading.local()
+
+
+def _on(t: torch.Tensor) -> torch.device:
+    """Declare `t`'s device the device of the operator being executed on this thread (call first in every backward)."""
+    _tls.device = t.device
+    return t.device
+
+
+def call(name: str, *args):
+    """Launch with the operands' device current (the library launches on the calling thread's current HIP device)."""
+    dev = getattr(_tls, 'device', None)
+    if dev is not None and dev.index is not None and dev.index != torch.cuda.current_device():
+        with torch.cuda.device(dev): return _raw_call(name, *args)
+    return _raw_call(name, *args)
+
+
+def _stream() -> int:
+    """The HIP stream of the operands' device.  (Not simply `torch.cuda.current_stream()`: with tensors on a GPU that is not the
+    process's current device that would be a stream of another device.)"""
+    dev = getattr(_tls, 'device', None)
+    return torch.cuda.current_stream(dev if dev is not None else torch.cuda.current_device()).cuda_stream
+
+
+def _check(name: str, t: torch.Tensor, shape=None) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor): raise TypeError(f'{name} must be a Tensor, got {type(t)}')
+    if not t.is_cuda: raise RuntimeError(f'{name} must live on the GPU: the view-synthesis hot path has no CPU implementation')
+    _tls.device = t.device
+    if t.dtype != torch.float32: raise TypeError(f'{name} must be float32 (the loss path is fp32 only), got {t.dtype}')
+    if shape is not None and tuple(t.shape) != tuple(shape): raise ValueError(f'{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}')
+    return t.contiguous()
+
+
+def _check_fb(name: str, t: torch.Tensor, shape=None) -> torch.Tensor:
+    """Like `_check`, for the operators that also take bfloat16 tensors at an autocast boundary."""
+    if not isinstance(t, torch.Tensor): raise TypeError(f'{name} must be a Tensor, got {type(t)}')
+    if not t.is_cuda: raise RuntimeError(f'{name} must live on the GPU')
+    if t.dtype not in (torch.float32, torch.bfloat16): raise TypeError(f'{name} must be float32 or bfloat16, got {t.dtype}')
+    if shape is not None and tuple(t.shape) != tuple(shape): raise ValueError(f'{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}')
+    return t.contiguous()

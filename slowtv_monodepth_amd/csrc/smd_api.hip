@@ -921,94 +921,71 @@ static bool mfma_sizes_ok(int B, int C, int CO, int h, int w) {   // grid dimens
   return B >= 1 && C >= 1 && CO >= 1 && C <= 4096 && CO <= 4096 && h >= 1 && w >= 1 && h < 32768 && w < 32768 && (long long)(h + 2)*(w + 2) < (1ll << 30) &&
          (long long)B*((C + 31)/32)*((CO + 31)/32) < 65536 && (long long)C*(h + 2)*(w + 2) < (1ll << 29) && (long long)CO*h*w < (1ll << 29);
 }
-static bool mfma_fwd_served(int C, int CO) { return (C % 16 == 0 && CO % 32 == 0) || (CO == 16 && (C == 16 || C == 32)); }
-static bool mfma_wgt_served(int C, int CO) { return CO % 32 == 0 || (CO == 16 && (C == 16 || C == 32)); }
-static bool mfma_data_served(int C, int CO) { return (CO % 16 == 0 && C % 32 == 0) || (C == 16 && CO == 16); }
+using smd::ConvOp;
+static bool conv_two_tiles() { return knob("conv_two_tiles", 0) != 0; }   // read ONCE per entry point: its size check and its launch get the same value
 size_t smd_conv3x3_mfma_packed_bytes(int C, int CO, int pieces) {
   if (C < 1 || CO < 1 || pieces < 1 || pieces > 3) return 0;
   return align256(smd::conv_mfma_packed_elems(C, CO, pieces)*2);
 }
-size_t smd_conv3x3_mfma_workspace_bytes(int B, int C, int CO, int h, int w) {   // one size for the three operators
+static size_t mfma_workspace_bytes(bool zpad, int B, int C, int CO, int h, int w, bool two_tiles) {   // one size for the three operators
   if (!mfma_sizes_ok(B, C, CO, h, w)) return 0;
-  smd::set_conv_two_tiles(knob("conv_two_tiles", 0));
-  size_t n = 64;
-  if (mfma_fwd_served(C, CO)) n = std::max(n, smd::conv_mfma_fwd_split_elems(B, C, CO, h, w));
-  if (mfma_data_served(C, CO)) n = std::max(n, smd::conv_mfma_bwd_split_elems(B, C, CO, h, w));
-  if (mfma_wgt_served(C, CO)) n = std::max(n, smd::conv_mfma_wgrad_partials(B, C, CO, h, w));
+  size_t n = std::max({(size_t)64, smd::conv_mfma_split_elems(ConvOp::Fwd, zpad, B, C, CO, h, w, two_tiles), smd::conv_mfma_split_elems(ConvOp::Data, zpad, B, C, CO, h, w, two_tiles)});
+  if (smd::conv_mfma_served(ConvOp::Wgt, zpad, C, CO)) n = std::max(n, smd::conv_mfma_wgrad_partials(zpad, B, C, CO, h, w));
   return align256(n*sizeof(float));
+}
+size_t smd_conv3x3_mfma_workspace_bytes(int B, int C, int CO, int h, int w) { return mfma_workspace_bytes(false, B, C, CO, h, w, conv_two_tiles()); }
+size_t smd_conv3x3z_mfma_workspace_bytes(int B, int C, int CO, int h, int w) { return mfma_workspace_bytes(true, B, C, CO, h, w, conv_two_tiles()); }
+static int mfma_unserved(ConvOp op, bool zpad, int C, int CO) {   // (what IS served: smd::conv_mfma_served, include/smd_hotpath.h)
+  const char* name[] = {"forward", "data gradient", "weight gradient"};
+  return fail(SMD_E_UNSUPPORTED, "the %s%s does not serve C=%d CO=%d", zpad ? "zero-padded " : "", name[(int)op], C, CO);
+}
+// What the six launches check after their pointers, in this order: pieces, sizes (SMD_E_INVALID), channels (SMD_E_UNSUPPORTED), workspace (SMD_E_WORKSPACE).
+static int mfma_check(ConvOp op, bool zpad, size_t workspace_bytes, int B, int C, int CO, int h, int w, int pieces, bool two_tiles) {
+  if (zpad && pieces != 2 && pieces != 3) return fail(SMD_E_UNSUPPORTED, "the zero-padded forms take float tensors: pieces 2 or 3, not %d", pieces);
+  if (pieces < 1 || pieces > 3) return fail(SMD_E_UNSUPPORTED, "pieces must be 1 (bfloat16 tensors), 2 or 3 (float tensors), not %d", pieces);
+  if (!mfma_sizes_ok(B, C, CO, h, w)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d CO=%d h=%d w=%d", B, C, CO, h, w);
+  if (!smd::conv_mfma_served(op, zpad, C, CO)) return mfma_unserved(op, zpad, C, CO);
+  if (workspace_bytes < mfma_workspace_bytes(zpad, B, C, CO, h, w, two_tiles)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return SMD_OK;
 }
 int smd_conv3x3_mfma_pack(const float* weight, void* wp_fwd, void* wp_bwd, int C, int CO, int pieces, void* stream) {
   if (!weight || (!wp_fwd && !wp_bwd)) return fail(SMD_E_INVALID, "null pointer");
   if (pieces < 1 || pieces > 3) return fail(SMD_E_UNSUPPORTED, "pieces must be 1 (bfloat16 tensors), 2 or 3 (float tensors), not %d", pieces);
   if (C < 1 || CO < 1 || C > 4096 || CO > 4096) return fail(SMD_E_INVALID, "invalid sizes C=%d CO=%d", C, CO);
-  if (wp_fwd && !mfma_fwd_served(C, CO)) return fail(SMD_E_UNSUPPORTED, "the forward form serves C %% 16 == 0 with CO %% 32 == 0, or CO == 16 with C == 16 | 32, not C=%d CO=%d", C, CO);
-  if (wp_bwd && !mfma_data_served(C, CO)) return fail(SMD_E_UNSUPPORTED, "the data-gradient form serves CO %% 16 == 0 with C %% 32 == 0, or C == CO == 16, not C=%d CO=%d", C, CO);
+  if (wp_fwd && !smd::conv_mfma_served(ConvOp::Fwd, false, C, CO)) return mfma_unserved(ConvOp::Fwd, false, C, CO);
+  if (wp_bwd && !smd::conv_mfma_served(ConvOp::Data, false, C, CO)) return mfma_unserved(ConvOp::Data, false, C, CO);
   return check_launch(smd::launch_conv_mfma_pack(weight, wp_fwd, wp_bwd, C, CO, pieces, (hipStream_t)stream), "conv3x3_mfma_pack");
 }
-int smd_conv3x3_mfma_fwd(const void* xp, const void* wp_fwd, void* y, void* workspace, size_t workspace_bytes,
-                         int B, int C, int CO, int h, int w, int pieces, void* stream) {
-  if (!xp || !wp_fwd || !y || !workspace) return fail(SMD_E_INVALID, "null pointer");
-  if (pieces < 1 || pieces > 3) return fail(SMD_E_UNSUPPORTED, "pieces must be 1 (bfloat16 tensors), 2 or 3 (float tensors), not %d", pieces);
-  if (!mfma_sizes_ok(B, C, CO, h, w)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d CO=%d h=%d w=%d", B, C, CO, h, w);
-  if (!mfma_fwd_served(C, CO)) return fail(SMD_E_UNSUPPORTED, "the forward serves C %% 16 == 0 with CO %% 32 == 0, or CO == 16 with C == 16 | 32, not C=%d CO=%d", C, CO);
-  if (workspace_bytes < smd_conv3x3_mfma_workspace_bytes(B, C, CO, h, w)) return fail(SMD_E_WORKSPACE, "workspace too small");
-  smd::set_conv_two_tiles(knob("conv_two_tiles", 0));
-  return check_launch(smd::launch_conv_mfma_fwd(xp, wp_fwd, y, (float*)workspace, B, C, CO, h, w, pieces, (hipStream_t)stream), "conv3x3_mfma_fwd");
+// One body for the padded (smd_conv3x3_mfma_*) and zero-padded (smd_conv3x3z_mfma_*: unpadded x / g_x, fp32 only) forward (x -> y) and data gradient (g_y -> g_x)
+static int mfma_form(ConvOp op, bool zpad, const void* in, const void* wp, void* out, void* workspace, size_t workspace_bytes, int B, int C, int CO, int h, int w, int pieces, void* stream, const char* what) {
+  if (!in || !wp || !out || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  const bool two_tiles = conv_two_tiles();
+  if (int rc = mfma_check(op, zpad, workspace_bytes, B, C, CO, h, w, pieces, two_tiles)) return rc;
+  const auto launch = op == ConvOp::Fwd ? smd::launch_conv_mfma_fwd : smd::launch_conv_mfma_bwd_data;
+  return check_launch(launch(in, wp, out, (float*)workspace, zpad, B, C, CO, h, w, pieces, two_tiles, (hipStream_t)stream), what);
 }
-int smd_conv3x3_mfma_bwd_data(const void* g_y, const void* wp_bwd, void* g_xp, void* workspace, size_t workspace_bytes,
-                              int B, int C, int CO, int h, int w, int pieces, void* stream) {
-  if (!g_y || !wp_bwd || !g_xp || !workspace) return fail(SMD_E_INVALID, "null pointer");
-  if (pieces < 1 || pieces > 3) return fail(SMD_E_UNSUPPORTED, "pieces must be 1 (bfloat16 tensors), 2 or 3 (float tensors), not %d", pieces);
-  if (!mfma_sizes_ok(B, C, CO, h, w)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d CO=%d h=%d w=%d", B, C, CO, h, w);
-  if (!mfma_data_served(C, CO)) return fail(SMD_E_UNSUPPORTED, "the data gradient serves CO %% 16 == 0 with C %% 32 == 0, or C == CO == 16, not C=%d CO=%d", C, CO);
-  if (workspace_bytes < smd_conv3x3_mfma_workspace_bytes(B, C, CO, h, w)) return fail(SMD_E_WORKSPACE, "workspace too small");
-  smd::set_conv_two_tiles(knob("conv_two_tiles", 0));
-  return check_launch(smd::launch_conv_mfma_bwd_data(g_y, wp_bwd, g_xp, (float*)workspace, B, C, CO, h, w, pieces, (hipStream_t)stream), "conv3x3_mfma_bwd_data");
-}
-int smd_conv3x3_mfma_bwd_weight(const void* xp, const void* g_y, float* g_weight, void* workspace, size_t workspace_bytes,
-                                int B, int C, int CO, int h, int w, int pieces, void* stream) {
-  if (!xp || !g_y || !g_weight || !workspace) return fail(SMD_E_INVALID, "null pointer");
-  if (pieces < 1 || pieces > 3) return fail(SMD_E_UNSUPPORTED, "pieces must be 1 (bfloat16 tensors), 2 or 3 (float tensors), not %d", pieces);
-  if (!mfma_sizes_ok(B, C, CO, h, w)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d CO=%d h=%d w=%d", B, C, CO, h, w);
-  if (!mfma_wgt_served(C, CO)) return fail(SMD_E_UNSUPPORTED, "the weight gradient serves CO %% 32 == 0, or CO == 16 with C == 16 | 32, not C=%d CO=%d", C, CO);
-  if (workspace_bytes < smd_conv3x3_mfma_workspace_bytes(B, C, CO, h, w)) return fail(SMD_E_WORKSPACE, "workspace too small");
-  return check_launch(smd::launch_conv_mfma_bwd_wgt(xp, g_y, g_weight, (float*)workspace, B, C, CO, h, w, pieces, (hipStream_t)stream), "conv3x3_mfma_bwd_weight");
-}
-// the zero-padded "same" forms (the encoders' 3x3 stride-1 convolutions): unpadded x and g_x, fp32 tensors only
-static bool mfmaz_pieces_ok(int pieces) { return pieces == 2 || pieces == 3; }
-size_t smd_conv3x3z_mfma_workspace_bytes(int B, int C, int CO, int h, int w) {   // one size for the three operators
-  if (!mfma_sizes_ok(B, C, CO, h, w)) return 0;
-  smd::set_conv_two_tiles(knob("conv_two_tiles", 0));
-  size_t n = std::max((size_t)64, smd::conv_mfma_z_split_elems(B, C, CO, h, w));
-  if (CO % 32 == 0) n = std::max(n, smd::conv_mfma_z_wgrad_partials(B, C, CO, h, w));
-  return align256(n*sizeof(float));
-}
-int smd_conv3x3z_mfma_fwd(const float* x, const void* wp_fwd, float* y, void* workspace, size_t workspace_bytes,
-                          int B, int C, int CO, int h, int w, int pieces, void* stream) {
-  if (!x || !wp_fwd || !y || !workspace) return fail(SMD_E_INVALID, "null pointer");
-  if (!mfmaz_pieces_ok(pieces)) return fail(SMD_E_UNSUPPORTED, "the zero-padded forms take float tensors: pieces 2 or 3, not %d", pieces);
-  if (!mfma_sizes_ok(B, C, CO, h, w)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d CO=%d h=%d w=%d", B, C, CO, h, w);
-  if (C % 16 || CO % 32) return fail(SMD_E_UNSUPPORTED, "the zero-padded forward serves C %% 16 == 0 with CO %% 32 == 0, not C=%d CO=%d", C, CO);
-  if (workspace_bytes < smd_conv3x3z_mfma_workspace_bytes(B, C, CO, h, w)) return fail(SMD_E_WORKSPACE, "workspace too small");
-  return check_launch(smd::launch_conv_mfma_z_fwd(x, wp_fwd, y, (float*)workspace, B, C, CO, h, w, pieces, (hipStream_t)stream), "conv3x3z_mfma_fwd");
-}
-int smd_conv3x3z_mfma_bwd_data(const float* g_y, const void* wp_bwd, float* g_x, void* workspace, size_t workspace_bytes,
-                               int B, int C, int CO, int h, int w, int pieces, void* stream) {
-  if (!g_y || !wp_bwd || !g_x || !workspace) return fail(SMD_E_INVALID, "null pointer");
-  if (!mfmaz_pieces_ok(pieces)) return fail(SMD_E_UNSUPPORTED, "the zero-padded forms take float tensors: pieces 2 or 3, not %d", pieces);
-  if (!mfma_sizes_ok(B, C, CO, h, w)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d CO=%d h=%d w=%d", B, C, CO, h, w);
-  if (CO % 16 || C % 32) return fail(SMD_E_UNSUPPORTED, "the zero-padded data gradient serves CO %% 16 == 0 with C %% 32 == 0, not C=%d CO=%d", C, CO);
-  if (workspace_bytes < smd_conv3x3z_mfma_workspace_bytes(B, C, CO, h, w)) return fail(SMD_E_WORKSPACE, "workspace too small");
-  return check_launch(smd::launch_conv_mfma_z_bwd_data(g_y, wp_bwd, g_x, (float*)workspace, B, C, CO, h, w, pieces, (hipStream_t)stream), "conv3x3z_mfma_bwd_data");
-}
-int smd_conv3x3z_mfma_bwd_weight(const float* x, const float* g_y, float* g_weight, void* workspace, size_t workspace_bytes,
-                                 int B, int C, int CO, int h, int w, int pieces, void* stream) {
+static int mfma_bwd_weight(bool zpad, const void* x, const void* g_y, float* g_weight, void* workspace, size_t workspace_bytes, int B, int C, int CO, int h, int w, int pieces, void* stream) {
   if (!x || !g_y || !g_weight || !workspace) return fail(SMD_E_INVALID, "null pointer");
-  if (!mfmaz_pieces_ok(pieces)) return fail(SMD_E_UNSUPPORTED, "the zero-padded forms take float tensors: pieces 2 or 3, not %d", pieces);
-  if (!mfma_sizes_ok(B, C, CO, h, w)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d CO=%d h=%d w=%d", B, C, CO, h, w);
-  if (CO % 32) return fail(SMD_E_UNSUPPORTED, "the zero-padded weight gradient serves CO %% 32 == 0, not C=%d CO=%d", C, CO);
-  if (workspace_bytes < smd_conv3x3z_mfma_workspace_bytes(B, C, CO, h, w)) return fail(SMD_E_WORKSPACE, "workspace too small");
-  return check_launch(smd::launch_conv_mfma_z_bwd_wgt(x, g_y, g_weight, (float*)workspace, B, C, CO, h, w, pieces, (hipStream_t)stream), "conv3x3z_mfma_bwd_weight");
+  if (int rc = mfma_check(ConvOp::Wgt, zpad, workspace_bytes, B, C, CO, h, w, pieces, conv_two_tiles())) return rc;
+  return check_launch(smd::launch_conv_mfma_bwd_wgt(x, g_y, g_weight, (float*)workspace, zpad, B, C, CO, h, w, pieces, (hipStream_t)stream), zpad ? "conv3x3z_mfma_bwd_weight" : "conv3x3_mfma_bwd_weight");
+}
+int smd_conv3x3_mfma_fwd(const void* xp, const void* wp_fwd, void* y, void* workspace, size_t workspace_bytes, int B, int C, int CO, int h, int w, int pieces, void* stream) {
+  return mfma_form(ConvOp::Fwd, false, xp, wp_fwd, y, workspace, workspace_bytes, B, C, CO, h, w, pieces, stream, "conv3x3_mfma_fwd");
+}
+int smd_conv3x3_mfma_bwd_data(const void* g_y, const void* wp_bwd, void* g_xp, void* workspace, size_t workspace_bytes, int B, int C, int CO, int h, int w, int pieces, void* stream) {
+  return mfma_form(ConvOp::Data, false, g_y, wp_bwd, g_xp, workspace, workspace_bytes, B, C, CO, h, w, pieces, stream, "conv3x3_mfma_bwd_data");
+}
+int smd_conv3x3_mfma_bwd_weight(const void* xp, const void* g_y, float* g_weight, void* workspace, size_t workspace_bytes, int B, int C, int CO, int h, int w, int pieces, void* stream) {
+  return mfma_bwd_weight(false, xp, g_y, g_weight, workspace, workspace_bytes, B, C, CO, h, w, pieces, stream);
+}
+int smd_conv3x3z_mfma_fwd(const float* x, const void* wp_fwd, float* y, void* workspace, size_t workspace_bytes, int B, int C, int CO, int h, int w, int pieces, void* stream) {
+  return mfma_form(ConvOp::Fwd, true, x, wp_fwd, y, workspace, workspace_bytes, B, C, CO, h, w, pieces, stream, "conv3x3z_mfma_fwd");
+}
+int smd_conv3x3z_mfma_bwd_data(const float* g_y, const void* wp_bwd, float* g_x, void* workspace, size_t workspace_bytes, int B, int C, int CO, int h, int w, int pieces, void* stream) {
+  return mfma_form(ConvOp::Data, true, g_y, wp_bwd, g_x, workspace, workspace_bytes, B, C, CO, h, w, pieces, stream, "conv3x3z_mfma_bwd_data");
+}
+int smd_conv3x3z_mfma_bwd_weight(const float* x, const float* g_y, float* g_weight, void* workspace, size_t workspace_bytes, int B, int C, int CO, int h, int w, int pieces, void* stream) {
+  return mfma_bwd_weight(true, x, g_y, g_weight, workspace, workspace_bytes, B, C, CO, h, w, pieces, stream);
 }
 // the ResNet stem: conv2d(x (B,C,H,W), weight (64,C,7,7), stride 2, padding 3), C = 3 | 6 (smd_conv_stem.hip)
 static bool stem_sizes_ok(int B, int C, int H, int W) {

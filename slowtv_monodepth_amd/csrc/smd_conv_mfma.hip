@@ -1130,8 +1130,7 @@ static size_t wgrad_floats(unsigned T, int C, int CO) {
   return (size_t)T*n + (G > 1 ? 2*(size_t)G*n : 0);              // (T n is even: n = 9 CO C with CO even)
 }
 // floats of workspace: the blocks' partial sums, then the finalize's fp64 slices (the padded form's bfloat16 path keeps one sample per block: the larger size)
-size_t conv_mfma_wgrad_partials(int B, int C, int CO, int h, int w) { return wgrad_floats(wgrad_sets(B, C, CO, h, w, false), C, CO); }
-size_t conv_mfma_z_wgrad_partials(int B, int C, int CO, int h, int w) { return wgrad_floats(wgrad_sets(B, C, CO, h, w, true), C, CO); }
+size_t conv_mfma_wgrad_partials(bool zpad, int B, int C, int CO, int h, int w) { return wgrad_floats(wgrad_sets(B, C, CO, h, w, zpad), C, CO); }
 static size_t thin_packed_elems(int C, int pieces) { return (size_t)(C >> 4)*5*pieces*512; }
 size_t conv_mfma_packed_elems(int C, int CO, int pieces) { return std::max((size_t)CO*C*9*pieces, CO == 16 ? thin_packed_elems(C, pieces) : (size_t)0); }
 
@@ -1171,9 +1170,6 @@ hipError_t launch_conv_mfma_pack(const float* w, void* wp_fwd, void* wp_bwd, int
 }
 
 // Launch shape of the forward / data-gradient form: tile columns, channel tiles per block, K splits (each split a whole number of 16-channel chunks).
-static int g_conv_two_tiles = 0;
-void set_conv_two_tiles(int v) { g_conv_two_tiles = v; }
-static bool conv_two_tiles() { return g_conv_two_tiles != 0; }
 struct ConvShape { int TC, TRB, NM, KS, kcs, S; unsigned gx, gy, gz; dim3 grid; size_t out_elems; };
 // Row-band tiles (TC = 0): BR rows of one sample, or S whole samples (BR = ho) where an image has at most 128 pixels; the patch (S (BR + 2) (wo + 2) pixels)
 // must fit ConvTile<0>::NPIX.  Returns the useful share of the band blocks' 256 pixels, 0 where no band fits.
@@ -1191,7 +1187,7 @@ static double band_shape(int B, int CK, int ho, int wo, int& BR, int& S) {
   }
   return (double)B*ho*wo/((double)ceil_div(ho, BR)*ceil_div(B, S)*256.0);
 }
-static ConvShape conv_shape(int B, int CK, int M, int ho, int wo) {
+static ConvShape conv_shape(int B, int CK, int M, int ho, int wo, bool two_tiles) {
   ConvShape s;
   s.TC = wo >= 48 ? 64 : 32; s.TRB = wo >= 48 ? 4 : 8; s.S = 1;
   const int KC = CK >> 4;
@@ -1219,7 +1215,7 @@ static ConvShape conv_shape(int B, int CK, int M, int ho, int wo) {
     }
   }
   const long long tiles = (long long)ceil_div(wo, s.TC)*ceil_div(ho, s.TRB)*B;
-  s.NM = (M % 64 == 0 && tiles*(M/64) >= 256 && conv_two_tiles()) ? 2 : 1;   // two channel tiles over one patch where that still leaves a block per CU
+  s.NM = (M % 64 == 0 && tiles*(M/64) >= 256 && two_tiles) ? 2 : 1;   // two channel tiles over one patch where that still leaves a block per CU
   const long long base = tiles*(M/(32*s.NM));
   int ks = 1;
   if (base < 384) ks = (int)std::min<long long>(std::max(KC/2, 1), (512 + base - 1)/base);   // under 1.5 blocks per CU: split K, at least two chunks per split
@@ -1229,14 +1225,17 @@ static ConvShape conv_shape(int B, int CK, int M, int ho, int wo) {
   s.out_elems = (size_t)B*M*ho*wo;
   return s;
 }
-size_t conv_mfma_split_elems(int B, int CK, int M, int ho, int wo) {
-  const ConvShape s = conv_shape(B, CK, M, ho, wo);
+// forward: CK = C, M = CO; data gradient: CK = CO, M = C, the output the padded size; the thin stage's 16-channel kernels (fwd CO = 16; data C = CO = 16) never split
+size_t conv_mfma_split_elems(ConvOp op, bool zpad, int B, int C, int CO, int h, int w, bool two_tiles) {
+  if (op == ConvOp::Wgt || !conv_mfma_served(op, zpad, C, CO) || (CO == 16 && (op == ConvOp::Fwd || C == 16))) return 0;
+  const int e = zpad ? 0 : 2;
+  const ConvShape s = op == ConvOp::Fwd ? conv_shape(B, C, CO, h, w, two_tiles) : conv_shape(B, CO, C, h + e, w + e, two_tiles);
   return s.KS > 1 ? (size_t)s.KS*s.out_elems : 0;
 }
 
 template <int P, int OFF, typename T>
-static void launch_conv_form(const void* in, const void* wp, void* out, float* split_ws, int B, int CK, int M, int hi, int wi, int ho, int wo, hipStream_t st) {
-  const ConvShape s = conv_shape(B, CK, M, ho, wo);
+static void launch_conv_form(const void* in, const void* wp, void* out, float* split_ws, int B, int CK, int M, int hi, int wi, int ho, int wo, bool two_tiles, hipStream_t st) {
+  const ConvShape s = conv_shape(B, CK, M, ho, wo, two_tiles);
   const uint4* wq = (const uint4*)wp;
   const T* i_ = (const T*)in;
   T* dst = s.KS > 1 ? reinterpret_cast<T*>(split_ws) : (T*)out;    // (the kernel writes a split's partial output as fp32 whatever T)
@@ -1252,32 +1251,39 @@ static void launch_conv_form(const void* in, const void* wp, void* out, float* s
   }
 }
 
-// y (B, CO, h, w) = conv3x3(xp (B, C, h + 2, w + 2)): C % 16 == 0, CO % 32 == 0
-size_t conv_mfma_fwd_split_elems(int B, int C, int CO, int h, int w) { return CO % 32 ? 0 : conv_mfma_split_elems(B, C, CO, h, w); }
-size_t conv_mfma_bwd_split_elems(int B, int C, int CO, int h, int w) { return C % 32 ? 0 : conv_mfma_split_elems(B, CO, C, h + 2, w + 2); }
-hipError_t launch_conv_mfma_fwd(const void* xp, const void* wp_fwd, void* y, float* split_ws, int B, int C, int CO, int h, int w, int pieces, hipStream_t st) {
-  if (CO == 16) {
-#define SMD_CALL(P, T) launch_conv16<P, T>(xp, wp_fwd, y, B, C, false, h + 2, w + 2, h, w, st)
+#define SMD_BY_PIECES_F32(pieces, CALL) do { if ((pieces) == 3) { CALL(3); } else { CALL(2); } } while (0)   // the zero-padded forms: fp32 tensors only
+// y (B, CO, h, w) = conv3x3(xp (B, C, h + 2, w + 2)), or zpad: conv2d(x (B, C, h, w), padding = 1); what is served: conv_mfma_served (smd_kernels.h)
+hipError_t launch_conv_mfma_fwd(const void* x, const void* wp_fwd, void* y, float* split_ws, bool zpad, int B, int C, int CO, int h, int w, int pieces, bool two_tiles, hipStream_t st) {
+  if (zpad) {
+#define SMD_CALL(P) launch_conv_form<P, 1, float>(x, wp_fwd, y, split_ws, B, C, CO, h, w, h, w, two_tiles, st)
+    SMD_BY_PIECES_F32(pieces, SMD_CALL);
+#undef SMD_CALL
+  } else if (CO == 16) {
+#define SMD_CALL(P, T) launch_conv16<P, T>(x, wp_fwd, y, B, C, false, h + 2, w + 2, h, w, st)
     SMD_BY_PIECES(pieces, SMD_CALL);
 #undef SMD_CALL
-    return hipGetLastError();
-  }
-#define SMD_CALL(P, T) launch_conv_form<P, 0, T>(xp, wp_fwd, y, split_ws, B, C, CO, h + 2, w + 2, h, w, st)
-  SMD_BY_PIECES(pieces, SMD_CALL);
+  } else {
+#define SMD_CALL(P, T) launch_conv_form<P, 0, T>(x, wp_fwd, y, split_ws, B, C, CO, h + 2, w + 2, h, w, two_tiles, st)
+    SMD_BY_PIECES(pieces, SMD_CALL);
 #undef SMD_CALL
+  }
   return hipGetLastError();
 }
-// g_xp (B, C, h + 2, w + 2) from g_y (B, CO, h, w): CO % 16 == 0, C % 32 == 0
-hipError_t launch_conv_mfma_bwd_data(const void* gy, const void* wp_bwd, void* g_xp, float* split_ws, int B, int C, int CO, int h, int w, int pieces, hipStream_t st) {
-  if (CO == 16 && C == 16) {
-#define SMD_CALL(P, T) launch_conv16<P, T>(gy, wp_bwd, g_xp, B, 16, true, h, w, h + 2, w + 2, st)
+// g_xp (B, C, h + 2, w + 2) from g_y (B, CO, h, w), or zpad: g_x (B, C, h, w)
+hipError_t launch_conv_mfma_bwd_data(const void* gy, const void* wp_bwd, void* g_x, float* split_ws, bool zpad, int B, int C, int CO, int h, int w, int pieces, bool two_tiles, hipStream_t st) {
+  if (zpad) {
+#define SMD_CALL(P) launch_conv_form<P, 1, float>(gy, wp_bwd, g_x, split_ws, B, CO, C, h, w, h, w, two_tiles, st)
+    SMD_BY_PIECES_F32(pieces, SMD_CALL);
+#undef SMD_CALL
+  } else if (CO == 16 && C == 16) {
+#define SMD_CALL(P, T) launch_conv16<P, T>(gy, wp_bwd, g_x, B, 16, true, h, w, h + 2, w + 2, st)
     SMD_BY_PIECES(pieces, SMD_CALL);
 #undef SMD_CALL
-    return hipGetLastError();
-  }
-#define SMD_CALL(P, T) launch_conv_form<P, 2, T>(gy, wp_bwd, g_xp, split_ws, B, CO, C, h, w, h + 2, w + 2, st)
-  SMD_BY_PIECES(pieces, SMD_CALL);
+  } else {
+#define SMD_CALL(P, T) launch_conv_form<P, 2, T>(gy, wp_bwd, g_x, split_ws, B, CO, C, h, w, h + 2, w + 2, two_tiles, st)
+    SMD_BY_PIECES(pieces, SMD_CALL);
 #undef SMD_CALL
+  }
   return hipGetLastError();
 }
 // g_w (CO, C, 3, 3) fp32: CO % 32 == 0, any C >= 1 (channel tiles past C are computed on clamped reads and not stored); or CO == 16 with C == 16 | 32
@@ -1312,44 +1318,19 @@ static hipError_t wgrad_finalize(float* g_w, float* partial, int B, int C, int C
   }
   return hipGetLastError();
 }
-hipError_t launch_conv_mfma_bwd_wgt(const void* xp, const void* gy, float* g_w, float* partial, int B, int C, int CO, int h, int w, int pieces, hipStream_t st) {
+hipError_t launch_conv_mfma_bwd_wgt(const void* xp, const void* gy, float* g_w, float* partial, bool zpad, int B, int C, int CO, int h, int w, int pieces, hipStream_t st) {
+  if (zpad) {
+    dim3 grid; int rows, spb;
+    wgrad_shape(B, C, CO, h, w, grid, rows, spb, true);
+#define SMD_CALL(P) hipLaunchKernelGGL((k_conv_wgrad_dma<P, true>), grid, dim3(256), 0, st, (const float*)xp, (const float*)gy, partial, B, C, CO, h, w, rows, spb)
+    SMD_BY_PIECES_F32(pieces, SMD_CALL);
+#undef SMD_CALL
+  } else {
 #define SMD_CALL(P, T) launch_wgrad<P, T>(xp, gy, partial, B, C, CO, h, w, st)
-  SMD_BY_PIECES(pieces, SMD_CALL);
+    SMD_BY_PIECES(pieces, SMD_CALL);
 #undef SMD_CALL
-  return wgrad_finalize(g_w, partial, B, C, CO, h, w, pieces != 1, st);
-}
-
-// ---- zero-padded "same" layers (the ResNet encoders' 3x3 stride-1 convolutions, padding 1): x (B, C, h, w) -> y (B, CO, h, w), g_y -> g_x (B, C, h, w),
-// g_w from x and g_y — no padded copy of any tensor.  fp32 tensors only (`pieces` 3, or the experiment's 2); the same operand images as the padded forms.
-#define SMD_BY_PIECES_F32(pieces, CALL) do { if ((pieces) == 3) { CALL(3); } else { CALL(2); } } while (0)
-size_t conv_mfma_z_split_elems(int B, int C, int CO, int h, int w) {
-  size_t n = 0;
-  if (C % 16 == 0 && CO % 32 == 0) n = std::max(n, conv_mfma_split_elems(B, C, CO, h, w));
-  if (CO % 16 == 0 && C % 32 == 0) n = std::max(n, conv_mfma_split_elems(B, CO, C, h, w));
-  return n;
-}
-// y = conv2d(x, w, padding = 1): C % 16 == 0, CO % 32 == 0
-hipError_t launch_conv_mfma_z_fwd(const float* x, const void* wp_fwd, float* y, float* split_ws, int B, int C, int CO, int h, int w, int pieces, hipStream_t st) {
-#define SMD_CALL(P) launch_conv_form<P, 1, float>(x, wp_fwd, y, split_ws, B, C, CO, h, w, h, w, st)
-  SMD_BY_PIECES_F32(pieces, SMD_CALL);
-#undef SMD_CALL
-  return hipGetLastError();
-}
-// g_x (B, C, h, w) from g_y (B, CO, h, w): CO % 16 == 0, C % 32 == 0
-hipError_t launch_conv_mfma_z_bwd_data(const float* gy, const void* wp_bwd, float* g_x, float* split_ws, int B, int C, int CO, int h, int w, int pieces, hipStream_t st) {
-#define SMD_CALL(P) launch_conv_form<P, 1, float>(gy, wp_bwd, g_x, split_ws, B, CO, C, h, w, h, w, st)
-  SMD_BY_PIECES_F32(pieces, SMD_CALL);
-#undef SMD_CALL
-  return hipGetLastError();
-}
-// g_w (CO, C, 3, 3): CO % 32 == 0, any C >= 1; the launch shape of the padded form's fp32 path
-hipError_t launch_conv_mfma_z_bwd_wgt(const float* x, const float* gy, float* g_w, float* partial, int B, int C, int CO, int h, int w, int pieces, hipStream_t st) {
-  dim3 grid; int rows, spb;
-  wgrad_shape(B, C, CO, h, w, grid, rows, spb, true);
-#define SMD_CALL(P) hipLaunchKernelGGL((k_conv_wgrad_dma<P, true>), grid, dim3(256), 0, st, x, gy, partial, B, C, CO, h, w, rows, spb)
-  SMD_BY_PIECES_F32(pieces, SMD_CALL);
-#undef SMD_CALL
-  return wgrad_finalize(g_w, partial, B, C, CO, h, w, true, st);
+  }
+  return wgrad_finalize(g_w, partial, B, C, CO, h, w, zpad || pieces != 1, st);
 }
 
 }  // namespace smd

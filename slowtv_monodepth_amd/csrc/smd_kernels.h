@@ -287,22 +287,24 @@ hipError_t launch_conv_thin_fwd(const float* xp, const float* wgt, float* y, int
 size_t conv_thin_partials(int B, int C, int h, int w);
 hipError_t launch_conv_thin_bwd_wgt(const float* xp, const float* gy, float* g_w, float* partial, int B, int C, int h, int w, hipStream_t st);
 hipError_t launch_conv_thin_bwd_data(const float* gy, const float* wgt, float* g_xp, int B, int C, int h, int w, hipStream_t st);
-// smd_conv_mfma.hip: the wide decoder convolutions on the bf16 matrix cores, fp32 operands split into `pieces` bf16 pieces (3: fp32-class results)
+// smd_conv_mfma.hip: 3x3 convolutions on the bf16 matrix cores, fp32 operands split into `pieces` bf16 pieces (3: fp32-class results).  zpad = false: the
+// decoder's layers on a reflection-padded xp (B, C, h + 2, w + 2), fp32 or (pieces 1) bfloat16; zpad = true: the encoders' zero-padded "same" layers on the
+// unpadded x / g_x, fp32 only.  two_tiles: the knob conv_two_tiles, read once per entry point (smd_api.hip) for its size query and its launch alike.
+enum class ConvOp { Fwd, Data, Wgt };
+// THE statement of which channel counts each operator's kernels serve (thin: the decoder's last stage on the 16-channel kernels)
+inline bool conv_mfma_served(ConvOp op, bool zpad, int C, int CO) {
+  const bool thin = !zpad && CO == 16 && (C == 16 || C == 32);
+  if (op == ConvOp::Fwd) return (C % 16 == 0 && CO % 32 == 0) || thin;
+  if (op == ConvOp::Data) return (CO % 16 == 0 && C % 32 == 0) || (thin && C == 16);
+  return CO % 32 == 0 || thin;
+}
 size_t conv_mfma_packed_elems(int C, int CO, int pieces);
-void set_conv_two_tiles(int v);     // launch-shape knob of the forward / data-gradient form (smd_api.hip: conv_two_tiles)
-size_t conv_mfma_wgrad_partials(int B, int C, int CO, int h, int w);
-size_t conv_mfma_z_wgrad_partials(int B, int C, int CO, int h, int w);
+size_t conv_mfma_wgrad_partials(bool zpad, int B, int C, int CO, int h, int w);
+size_t conv_mfma_split_elems(ConvOp op, bool zpad, int B, int C, int CO, int h, int w, bool two_tiles);   // floats of K-split partial outputs (0: none, or not served)
 hipError_t launch_conv_mfma_pack(const float* w, void* wp_fwd, void* wp_bwd, int C, int CO, int pieces, hipStream_t st);
-size_t conv_mfma_fwd_split_elems(int B, int C, int CO, int h, int w);     // floats of K-split partial outputs the forward / the data gradient wants (0: none)
-size_t conv_mfma_bwd_split_elems(int B, int C, int CO, int h, int w);
-hipError_t launch_conv_mfma_fwd(const void* xp, const void* wp_fwd, void* y, float* split_ws, int B, int C, int CO, int h, int w, int pieces, hipStream_t st);
-hipError_t launch_conv_mfma_bwd_data(const void* gy, const void* wp_bwd, void* g_xp, float* split_ws, int B, int C, int CO, int h, int w, int pieces, hipStream_t st);
-hipError_t launch_conv_mfma_bwd_wgt(const void* xp, const void* gy, float* g_w, float* partial, int B, int C, int CO, int h, int w, int pieces, hipStream_t st);
-// the zero-padded "same" forms (the encoders' 3x3 stride-1 layers): unpadded x / g_x, fp32 only (pieces 3 or 2)
-size_t conv_mfma_z_split_elems(int B, int C, int CO, int h, int w);           // floats of K-split partial outputs the forward / the data gradient want
-hipError_t launch_conv_mfma_z_fwd(const float* x, const void* wp_fwd, float* y, float* split_ws, int B, int C, int CO, int h, int w, int pieces, hipStream_t st);
-hipError_t launch_conv_mfma_z_bwd_data(const float* gy, const void* wp_bwd, float* g_x, float* split_ws, int B, int C, int CO, int h, int w, int pieces, hipStream_t st);
-hipError_t launch_conv_mfma_z_bwd_wgt(const float* x, const float* gy, float* g_w, float* partial, int B, int C, int CO, int h, int w, int pieces, hipStream_t st);
+hipError_t launch_conv_mfma_fwd(const void* x, const void* wp_fwd, void* y, float* split_ws, bool zpad, int B, int C, int CO, int h, int w, int pieces, bool two_tiles, hipStream_t st);
+hipError_t launch_conv_mfma_bwd_data(const void* gy, const void* wp_bwd, void* g_x, float* split_ws, bool zpad, int B, int C, int CO, int h, int w, int pieces, bool two_tiles, hipStream_t st);
+hipError_t launch_conv_mfma_bwd_wgt(const void* x, const void* gy, float* g_w, float* partial, bool zpad, int B, int C, int CO, int h, int w, int pieces, hipStream_t st);
 // smd_conv_stem.hip: the ResNet stem (7x7, stride 2, padding 3, 64 output channels; C = 3 | 6) on the split-bf16 matrix-core form, fp32 NCHW tensors
 bool conv_stem_served(int C, int CO);
 size_t conv_stem_packed_bytes(int C);

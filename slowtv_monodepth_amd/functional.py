@@ -8,53 +8,17 @@ CPU tensors are rejected.
 from __future__ import annotations
 
 import os
-import threading
 
 import torch
 
 from . import _lib
+from ._device import _check, _check_fb, _on, _stream, call
 from ._lib import FLAGS, REGR_FLAGS, SEL_MASKED, int_array, ptr_array
-from ._lib import call as _raw_call
+from .conv_ops import conv3x3_mfma, conv3x3_same, conv3x3_thin, conv3x3_wide, conv7x7s2_stem   # re-exported, like the routing below
+from .conv_routing import _conv_route, conv_routes, set_conv_route
 
 __all__ = ['conv3x3_headn', 'upsample_stack', 'scale_mean', 'conv3x3_mfma', 'conv3x3_wide', 'conv3x3_same', 'set_conv_route', 'conv_routes', 'loss_path_fused', 'crop_resize', 'disp_to_depth', 'image_recon_prep', 'PreparedFrames', 'image_recon_fused', 'image_recon_fused_disp', 'disp_smooth_fused', 'view_synth', 'photo_error', 'recon_reduce',
            'lane_shift_selftest', 'recon_flags', 'regression_loss', 'elu_pad', 'elu_up_cat_pad', 'batch_norm_act', 'max_pool3x3s2', 'dwconv7x7', 'layer_norm_cf', 'pose_matrices', 'intrinsics', 'inv_intrinsics']
-
-
-# Device of the operands of the operator this THREAD is executing: launches go to ITS current stream.  Thread-local, and set at
-# the top of every forward (by `_check`) AND every backward (by `_on`): autograd runs the backward of each device on its own
-# thread and has already made that device current there, so a process-wide "last validated device" would send the backward of
-# one GPU's graph to another GPU's stream as soon as two devices are used in one process.
-_tls = threading.local()
-
-
-def _on(t: torch.Tensor) -> torch.device:
-    """Declare `t`'s device the device of the operator being executed on this thread (call first in every backward)."""
-    _tls.device = t.device
-    return t.device
-
-
-def call(name: str, *args):
-    """Launch with the operands' device current (the library launches on the calling thread's current HIP device)."""
-    dev = getattr(_tls, 'device', None)
-    if dev is not None and dev.index is not None and dev.index != torch.cuda.current_device():
-        with torch.cuda.device(dev): return _raw_call(name, *args)
-    return _raw_call(name, *args)
-
-
-def _stream() -> int:
-    """The HIP stream of the operands' device.  (Not simply `torch.cuda.current_stream()`: with tensors on a GPU that is not the
-    process's current device that would be a stream of another device.)"""
-    dev = getattr(_tls, 'device', None)
-    return torch.cuda.current_stream(dev if dev is not None else torch.cuda.current_device()).cuda_stream
-
-
-def _check(name: str, t: torch.Tensor, shape=None) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor): raise TypeError(f'{name} must be a Tensor, got {type(t)}')
-    if not t.is_cuda: raise RuntimeError(f'{name} must live on the GPU: the view-synthesis hot path has no CPU implementation')
-    _tls.device = t.device
-    if t.dtype != torch.float32: raise TypeError(f'{name} must be float32 (the loss path is fp32 only), got {t.dtype}')
-    if shape is not None and tuple(t.shape) != tuple(shape): raise ValueError(f'{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}')
-    return t.contiguous()
 
 
 def recon_flags(loss_name: str = 'ssim', use_min: bool = False, use_automask: bool = False) -> int:
@@ -794,15 +758,6 @@ def _glue_ws(B, C, h, w, device):
     return torch.empty(nbytes, device=device, dtype=torch.uint8), nbytes
 
 
-def _check_fb(name: str, t: torch.Tensor, shape=None) -> torch.Tensor:
-    """Like `_check`, for the operators that also take bfloat16 tensors at an autocast boundary."""
-    if not isinstance(t, torch.Tensor): raise TypeError(f'{name} must be a Tensor, got {type(t)}')
-    if not t.is_cuda: raise RuntimeError(f'{name} must live on the GPU')
-    if t.dtype not in (torch.float32, torch.bfloat16): raise TypeError(f'{name} must be float32 or bfloat16, got {t.dtype}')
-    if shape is not None and tuple(t.shape) != tuple(shape): raise ValueError(f'{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}')
-    return t.contiguous()
-
-
 _BF = torch.bfloat16
 
 
@@ -1014,323 +969,6 @@ def scale_mean(xs, mode: str):
         if mode == 'bce_ones': return torch.stack([torch.nn.functional.binary_cross_entropy(x, torch.ones_like(x)) for x in xs]).mean()
         return torch.stack([(x.mean() if mode == 'identity' else -x.mean()) for x in xs]).mean()
     return _ScaleMean.apply(_MEAN_MODES[mode], *xs)
-
-
-class _Conv3x3Thin(torch.autograd.Function):
-    """`F.conv2d(xp, weight (16,C,3,3))` on an already reflection-padded input on the f32 MFMA (`smd_conv3x3_thin_*`: `v_mfma_f32_16x16x4_f32`, operands staged
-    through LDS): the decoder's last stage in its round-5 form (round 6: `conv3x3_wide` routes between this and the split-bf16 form per operator)."""
-    @staticmethod
-    def forward(ctx, xp, weight):
-        xp = _check('xp', xp)
-        if xp.ndim != 4 or xp.shape[2] < 4 or xp.shape[3] < 4: raise ValueError(f'expected a padded (B,C,h+2,w+2) with h, w >= 2, got {tuple(xp.shape)}')
-        B, C, H, W = xp.shape
-        weight = _check('weight', weight, (16, C, 3, 3))
-        y = torch.empty((B, 16, H - 2, W - 2), device=xp.device, dtype=torch.float32)
-        call('smd_conv3x3_thin_fwd', xp.data_ptr(), weight.data_ptr(), y.data_ptr(), B, C, H - 2, W - 2, _stream())
-        ctx.save_for_backward(xp, weight)
-        return y
-
-    @staticmethod
-    def backward(ctx, g_y):
-        xp, weight = ctx.saved_tensors
-        dev = _on(xp)
-        B, C, H, W = xp.shape
-        need_x, need_w = ctx.needs_input_grad
-        g_y = _check('grad(y)', g_y, (B, 16, H - 2, W - 2))
-        g_xp = g_w = None
-        if need_x: g_xp = torch.empty_like(xp)
-        if need_w: g_w = torch.empty_like(weight)
-        if need_x or need_w:
-            nbytes = _lib.lib.smd_conv3x3_thin_workspace_bytes(B, C, H - 2, W - 2) if need_w else 0
-            ws = torch.empty(max(nbytes, 256), device=dev, dtype=torch.uint8) if need_w else None
-            call('smd_conv3x3_thin_bwd', xp.data_ptr(), weight.data_ptr(), g_y.data_ptr(), g_xp.data_ptr() if need_x else None, g_w.data_ptr() if need_w else None,
-                 ws.data_ptr() if ws is not None else None, nbytes, B, C, H - 2, W - 2, _stream())
-        return g_xp, g_w
-
-
-def conv3x3_thin(xp, weight):
-    """`F.conv2d(xp, weight)` for sixteen output channels and an input that is already reflection-padded: the thin up-convolution of the decoder's last
-    stage (src/networks/decoders/monodepth.py:45-50, 80-84), bias-free (the next glue kernel adds it).  xp (B,C,h+2,w+2), weight (16,C,3,3) -> (B,16,h,w);
-    C = 16 or 32 (`_lib.Unsupported` otherwise)."""
-    return _Conv3x3Thin.apply(xp, weight)
-
-
-# ---- the wide decoder convolutions: split-bf16 MFMA kernels (smd_conv3x3_mfma_*) or MIOpen, per operator and shape --------------------------------
-# Which of the two serves an (operator, shape) pair is decided by a same-box A/B the first time the pair is seen: both run on the call's own tensors,
-# interleaved, a few times each; the faster one is cached for the process (VERDICT r5 item 1: "only where a same-box A/B against MIOpen wins").
-# `set_conv_route('mfma' | 'miopen')` pins the choice (tests, profiles); inside a HIP-graph capture nothing is timed and a static rule stands in.
-_CONV_ROUTE_MODE = 'auto'
-_CONV_ROUTES: dict = {}
-
-
-def set_conv_route(mode: str = 'auto'):
-    """'auto' (A/B on first use), 'mfma' or 'miopen' for every wide decoder convolution; clears the cached decisions."""
-    global _CONV_ROUTE_MODE
-    if mode not in ('auto', 'mfma', 'miopen'): raise ValueError(mode)
-    _CONV_ROUTE_MODE = mode
-    _CONV_ROUTES.clear()
-
-
-def conv_routes() -> dict:
-    """The decisions taken so far: {(op, B, C, CO, h, w): (use_mfma, us_mfma, us_miopen)}."""
-    return dict(_CONV_ROUTES)
-
-
-def _conv_static_rule(op, B, C, CO, h, w):
-    """Stand-in where nothing may be timed (graph capture): the shapes that won on an MI355X at cfg 2 (profiles/r06_decoder_convs.txt; the coarse levels
-    on the row-band tiles, 512 -> 256 at 6 x 20 / 12 x 40 and 256 -> 128 at 12 x 40 / 24 x 80: profiles/r08_coarse_convs.txt; the zero-padded encoder
-    layers, `*_z`: see `_conv_static_rule_z`)."""
-    px = B*h*w
-    if op.endswith('_bf16'): return CO == 16           # (bf16 tensors: MIOpen's bf16 kernels serve the wide layers; the thin stage is the stencil-like case)
-    if op.endswith('_z'): return _conv_static_rule_z(op[:-2], B, C, CO, h, w)
-    if op.endswith('_s'): return px >= 20000           # (the 7x7 stride-2 stems, h x w the INPUT size: profiles/stem_convs.txt)
-    if CO == 16: return op != 'wgt'
-    coarse = w <= 80 and C >= 256                      # (row-band tiles: 1.18-1.59 x forward, 1.09-1.74 x data gradient, 0.92-1.37 x weight gradient)
-    if op == 'fwd': return (px >= 20000 and C*CO <= 128*64) or (coarse and px >= 1000)
-    if op == 'data': return (px >= 5000 and C <= 256) or (coarse and px >= 1000)
-    return (px >= 20000 and CO <= 64) or (coarse and px >= 2400)
-
-
-def _conv_static_rule_z(op, B, C, CO, h, w):
-    """The zero-padded encoder layers (C = CO; profiles/r08_coarse_convs.txt): the data gradient wins at every stage (1.4-1.7 x); the forward and the
-    weight gradient win 1.13-1.6 x from 64 to 256 channels and at 512 channels with b = 24 (6 x 20, 2880 pixels), and are even with MIOpen at 512
-    channels with b = 12 (1440 pixels)."""
-    px = B*h*w
-    if op == 'data': return px >= 1000
-    return px >= (2400 if max(C, CO) >= 512 else 1000)
-
-
-def _conv_route(op, B, C, CO, h, w, run_mfma, run_ref):
-    if _CONV_ROUTE_MODE != 'auto': return _CONV_ROUTE_MODE == 'mfma'
-    key = (op, B, C, CO, h, w)
-    r = _CONV_ROUTES.get(key)
-    if r is None:
-        if torch.cuda.is_current_stream_capturing(): return _conv_static_rule(op, B, C, CO, h, w)
-        for _ in range(2): run_mfma(); run_ref()
-        ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(5)]
-        for e in ev:                     # interleaved: a box's clocks drift over the first milliseconds, whatever is timed first looks slower
-            e[0].record(); run_mfma(); e[1].record(); run_ref(); e[2].record()
-        torch.cuda.synchronize()
-        t_m = sorted(e[0].elapsed_time(e[1]) for e in ev)[2]*1e3
-        t_r = sorted(e[1].elapsed_time(e[2]) for e in ev)[2]*1e3
-        r = _CONV_ROUTES[key] = (t_m < 0.97*t_r, t_m, t_r)
-    return r[0]
-
-
-def _mfma_pack(weight, C, CO, pieces, want_fwd, want_bwd):
-    nbytes = _lib.lib.smd_conv3x3_mfma_packed_bytes(C, CO, pieces)
-    wf = torch.empty(max(nbytes, 256), device=weight.device, dtype=torch.uint8) if want_fwd else None
-    wb = torch.empty(max(nbytes, 256), device=weight.device, dtype=torch.uint8) if want_bwd else None
-    call('smd_conv3x3_mfma_pack', weight.data_ptr(), wf.data_ptr() if wf is not None else None, wb.data_ptr() if wb is not None else None, C, CO, pieces, _stream())
-    return wf, wb
-
-
-def _mfma_ws_bytes(B, C, CO, h, w, zpad):
-    return (_lib.lib.smd_conv3x3z_mfma_workspace_bytes if zpad else _lib.lib.smd_conv3x3_mfma_workspace_bytes)(B, C, CO, h, w)
-
-
-def _mfma_ws(B, C, CO, h, w, dev, zpad=False):
-    nws = _mfma_ws_bytes(B, C, CO, h, w, zpad)
-    return torch.empty(max(nws, 256), device=dev, dtype=torch.uint8), nws
-
-
-def _routed(op, B, C, CO, h, w, force, run_mfma, run_ref):
-    """Whether the MFMA kernels serve this operator: always under `force` (their errors propagate); otherwise as `_conv_route` says, and where the kernel
-    path turns the shape down — sizes its workspace query refuses (0), `Unsupported` or `ValueError` from a call — the reference serves it instead."""
-    if force: return True
-    try:
-        return _conv_route(op, B, C, CO, h, w, run_mfma, run_ref)
-    except (_lib.Unsupported, ValueError):
-        _CONV_ROUTES[(op, B, C, CO, h, w)] = (False, float('nan'), float('nan'))
-        return False
-
-
-def _ran(force, run_mfma):
-    """Run the MFMA kernels; False where the kernel path turned the call down (`Unsupported`, `ValueError`) and the caller takes the reference instead
-    (under `force` the error propagates)."""
-    if force: run_mfma(); return True
-    try:
-        run_mfma(); return True
-    except (_lib.Unsupported, ValueError):
-        return False
-
-
-class _Conv3x3Wide(torch.autograd.Function):
-    """`F.conv2d(xp, weight (CO,C,3,3))` on an already reflection-padded input; each of the three operators (forward, data gradient, weight gradient) runs
-    on the bf16 matrix cores (`smd_conv3x3_mfma_*`) or through the alternative — MIOpen, or for the 16-channel last stage in fp32 the f32-MFMA kernels
-    `smd_conv3x3_thin_*` — as `_conv_route` says (`force`: always the MFMA kernels).  fp32 tensors: every operand split into three bf16 pieces, fp32-class
-    results.  bfloat16 tensors (the decoder under bf16 autocast): one piece, bf16 in and out, the weights as their bf16 rounding (what autocast hands a bf16
-    convolution), fp32 accumulation and an fp32 weight gradient.
-    `zpad`: the zero-padded "same" layer instead, `F.conv2d(x, weight, padding=1)` on the UNPADDED x (the encoders' 3x3 stride-1 convolutions; fp32 only;
-    `smd_conv3x3z_mfma_*`, zero padding inside the kernels), its operators routed under op names of their own (`fwd_z`, `data_z`, `wgt_z`)."""
-    @staticmethod
-    def forward(ctx, xp, weight, pieces, force, zpad=False):
-        xp = _check_fb('xp', xp)
-        if zpad and xp.dtype != torch.float32: raise TypeError(f'the zero-padded convolution takes float32 tensors, got {xp.dtype}')
-        if xp.ndim != 4 or (not zpad and (xp.shape[2] < 3 or xp.shape[3] < 3)):
-            raise ValueError(f'expected {"(B,C,h,w)" if zpad else "a padded (B,C,h+2,w+2)"}, got {tuple(xp.shape)}')
-        B, C, H, W = xp.shape
-        if weight.ndim != 4 or tuple(weight.shape[1:]) != (C, 3, 3): raise ValueError(f'weight: expected (CO,{C},3,3), got {tuple(weight.shape)}')
-        CO = weight.shape[0]
-        weight = _check('weight', weight, (CO, C, 3, 3))
-        h, w, dev = (H, W, xp.device) if zpad else (H - 2, W - 2, xp.device)
-        bf = xp.dtype == _BF
-        if bf: pieces = 1
-        thin = CO == 16 and C in (16, 32) and not zpad      # the last stage
-        fwd_ok = (C % 16 == 0 and CO % 32 == 0) or thin
-        if force and not fwd_ok:
-            raise _lib.Unsupported(f'the MFMA forward serves C % 16 == 0 with CO % 32 == 0{"" if zpad else ", or CO = 16 with C = 16 | 32"}, not C={C} CO={CO}')
-        if not force and _mfma_ws_bytes(B, C, CO, h, w, zpad) == 0: fwd_ok = False   # (sizes the kernels do not take: the reference serves every operator)
-        bwd_form = (CO % 16 == 0 and C % 32 == 0) or (C == 16 and CO == 16 and not zpad)   # the data gradient's own operand order (what the backward kernel serves)
-        y = torch.empty((B, CO, h, w), device=dev, dtype=xp.dtype)
-        packed = {}
-
-        def run_mfma():                                     # the pack included: production pays it on every call, so the A/B times it too
-            packed['wf'], packed['wb'] = _mfma_pack(weight, C, CO, pieces, True, bwd_form)
-            ws, nws = _mfma_ws(B, C, CO, h, w, dev, zpad)
-            call('smd_conv3x3z_mfma_fwd' if zpad else 'smd_conv3x3_mfma_fwd', xp.data_ptr(), packed['wf'].data_ptr(), y.data_ptr(), ws.data_ptr(), nws,
-                 B, C, CO, h, w, pieces, _stream())
-
-        def run_ref():
-            if zpad: return torch.conv2d(xp, weight, None, 1, 1)
-            if bf: return torch.conv2d(xp, weight.to(_BF))
-            if thin: call('smd_conv3x3_thin_fwd', xp.data_ptr(), weight.data_ptr(), y.data_ptr(), B, C, h, w, _stream()); return y
-            return torch.conv2d(xp, weight)
-        op = 'fwd_z' if zpad else 'fwd_bf16' if bf else 'fwd'
-        use = fwd_ok and _routed(op, B, C, CO, h, w, force, run_mfma, run_ref)
-        if not (use and _ran(force, run_mfma)): y = run_ref()
-        ctx.save_for_backward(xp, weight, packed.get('wb'))
-        ctx.pieces, ctx.force, ctx.zpad, ctx.served = pieces, force, zpad, force or _mfma_ws_bytes(B, C, CO, h, w, zpad) > 0
-        return y
-
-    @staticmethod
-    def backward(ctx, g_y):
-        xp, weight, wp_bwd = ctx.saved_tensors
-        dev = _on(xp)
-        B, C, H, W = xp.shape
-        zpad = ctx.zpad
-        CO, pieces, force = weight.shape[0], ctx.pieces, ctx.force
-        h, w = (H, W) if zpad else (H - 2, W - 2)
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        bf = xp.dtype == _BF
-        g_y = _check_fb('grad(y)', g_y.to(xp.dtype), (B, CO, h, w))
-        g_xp = g_w = None
-        thin = CO == 16 and C in (16, 32) and not zpad
-        w_ref = weight.to(_BF) if bf else weight
-        pad = [1, 1] if zpad else [0, 0]
-        cb = lambda mask: torch.ops.aten.convolution_backward(g_y, xp, w_ref, None, [1, 1], pad, [1, 1], False, [0, 0], 1, mask)
-        sfx = '_z' if zpad else '_bf16' if bf else ''
-
-        def thin_bwd(want_x, want_w):                       # the f32-MFMA kernels of the last stage (smd_conv3x3_thin_bwd; fp32 tensors only)
-            gx_ = torch.empty_like(xp) if want_x else None
-            gw_ = torch.empty_like(weight) if want_w else None
-            nb = _lib.lib.smd_conv3x3_thin_workspace_bytes(B, C, h, w) if want_w else 0
-            ws_ = torch.empty(max(nb, 256), device=dev, dtype=torch.uint8) if want_w else None
-            call('smd_conv3x3_thin_bwd', xp.data_ptr(), weight.data_ptr(), g_y.data_ptr(), gx_.data_ptr() if want_x else None, gw_.data_ptr() if want_w else None,
-                 ws_.data_ptr() if want_w else None, nb, B, C, h, w, _stream())
-            return gx_, gw_
-        if need_x:
-            g_xp = torch.empty_like(xp)
-            packed = {'wb': wp_bwd}
-
-            def run_data():
-                if packed['wb'] is None: packed['wb'] = _mfma_pack(weight, C, CO, pieces, False, True)[1]
-                ws, nws = _mfma_ws(B, C, CO, h, w, dev, zpad)
-                call('smd_conv3x3z_mfma_bwd_data' if zpad else 'smd_conv3x3_mfma_bwd_data', g_y.data_ptr(), packed['wb'].data_ptr(), g_xp.data_ptr(), ws.data_ptr(), nws,
-                     B, C, CO, h, w, pieces, _stream())
-            ok = ctx.served and ((CO % 16 == 0 and C % 32 == 0) or (C == 16 and CO == 16 and not zpad))
-            ref_data = (lambda: thin_bwd(True, False)[0]) if (thin and not bf) else (lambda: cb([True, False, False])[0])
-            if not (ok and _routed('data' + sfx, B, C, CO, h, w, force, run_data, ref_data) and _ran(force, run_data)):
-                g_xp = ref_data()                           # (also: channel counts the data-gradient kernel does not tile)
-        if need_w:
-            g_w = torch.empty_like(weight)
-
-            def run_wgt():
-                ws, nws = _mfma_ws(B, C, CO, h, w, dev, zpad)
-                call('smd_conv3x3z_mfma_bwd_weight' if zpad else 'smd_conv3x3_mfma_bwd_weight', xp.data_ptr(), g_y.data_ptr(), g_w.data_ptr(), ws.data_ptr(), nws,
-                     B, C, CO, h, w, pieces, _stream())
-            ok = ctx.served and (CO % 32 == 0 or thin)
-            ref_wgt = (lambda: thin_bwd(False, True)[1]) if (thin and not bf) else (lambda: cb([False, True, False])[1].float())
-            if not (ok and _routed('wgt' + sfx, B, C, CO, h, w, force, run_wgt, ref_wgt) and _ran(force, run_wgt)): g_w = ref_wgt()
-        return g_xp, g_w, None, None, None
-
-
-def conv3x3_mfma(xp, weight, pieces: int = 3):
-    """`F.conv2d(xp, weight)` for an input that is already reflection-padded, ALWAYS through the split-bf16 MFMA kernels (`smd_conv3x3_mfma_*`): the wide
-    up-convolutions of the decoder (src/networks/decoders/monodepth.py:40-50, 71-84), bias-free (the next glue kernel adds it).  xp (B,C,h+2,w+2) fp32,
-    weight (CO,C,3,3) fp32 -> (B,CO,h,w) fp32; C % 16 == 0 and CO % 32 == 0, or the thin stage CO = 16 with C = 16 | 32 (`_lib.Unsupported` otherwise).  Every fp32 operand is split exactly into three
-    bf16 pieces and six products are kept per fp32 product (`pieces=3`: fp32-class error, see csrc/smd_conv_mfma.hip; `pieces=2` is an experiment setting)."""
-    return _Conv3x3Wide.apply(xp, weight, int(pieces), True)
-
-
-def conv3x3_wide(xp, weight):
-    """The same convolution, each operator through whichever of the MFMA kernels and MIOpen won this box's A/B for its shape (`_conv_route`)."""
-    return _Conv3x3Wide.apply(xp, weight, 3, False)
-
-
-def conv3x3_same(x, weight):
-    """`F.conv2d(x, weight (CO,C,3,3), padding=1)`, bias-free, zero padding: the ResNet encoders' 3x3 stride-1 convolutions (the timm blocks built at
-    src/networks/depth.py:95-98, src/networks/pose.py:39-41).  x (B,C,h,w) fp32 -> (B,CO,h,w) fp32.  Each operator runs on the split-bf16 MFMA kernels
-    (`smd_conv3x3z_mfma_*`, the padding done inside them) or MIOpen, as `_conv_route` says under `fwd_z` / `data_z` / `wgt_z` (`set_conv_route('mfma')`
-    pins the kernels); channel counts or sizes the kernels do not take go to MIOpen."""
-    return _Conv3x3Wide.apply(x, weight, 3, False, True)
-
-
-class _Conv7x7s2Stem(torch.autograd.Function):
-    """`F.conv2d(x, weight (64,C,7,7), stride=2, padding=3)`, the ResNet stem: forward and weight gradient on the split-bf16 MFMA kernels
-    (`smd_conv7x7s2_*`, C = 3 | 6) or MIOpen, as `_conv_route` says under `fwd_s` / `wgt_s`; shapes the kernels do not serve go to MIOpen.  The input is
-    normally the image; a data gradient, where asked for, is ATen's."""
-    @staticmethod
-    def forward(ctx, x, weight):
-        x = _check('x', x)
-        if x.ndim != 4: raise ValueError(f'expected (B,C,H,W), got {tuple(x.shape)}')
-        B, C, H, W = x.shape
-        if weight.ndim != 4 or tuple(weight.shape[1:]) != (C, 7, 7): raise ValueError(f'weight: expected (CO,{C},7,7), got {tuple(weight.shape)}')
-        CO = weight.shape[0]
-        weight = _check('weight', weight, (CO, C, 7, 7))
-        ho, wo = (H - 1)//2 + 1, (W - 1)//2 + 1
-        served = _lib.lib.smd_conv7x7s2_workspace_bytes(B, C, CO, H, W) > 0
-        y = torch.empty((B, CO, ho, wo), device=x.device, dtype=torch.float32)
-
-        def run_mfma():                                     # the pack included: every call pays it
-            wp = torch.empty(_lib.lib.smd_conv7x7s2_packed_bytes(C, CO), device=x.device, dtype=torch.uint8)
-            call('smd_conv7x7s2_pack', weight.data_ptr(), wp.data_ptr(), C, CO, _stream())
-            call('smd_conv7x7s2_fwd', x.data_ptr(), wp.data_ptr(), y.data_ptr(), B, C, CO, H, W, _stream())
-        run_ref = lambda: torch.conv2d(x, weight, None, 2, 3)
-        if not (served and _routed('fwd_s', B, C, CO, H, W, False, run_mfma, run_ref) and _ran(False, run_mfma)): y = run_ref()
-        ctx.save_for_backward(x, weight)
-        ctx.served = served
-        return y
-
-    @staticmethod
-    def backward(ctx, g_y):
-        x, weight = ctx.saved_tensors
-        dev = _on(x)
-        B, C, H, W = x.shape
-        CO = weight.shape[0]
-        need_x, need_w = ctx.needs_input_grad
-        g_y = _check('grad(y)', g_y, (B, CO, (H - 1)//2 + 1, (W - 1)//2 + 1))
-        cb = lambda mask: torch.ops.aten.convolution_backward(g_y, x, weight, None, [2, 2], [3, 3], [1, 1], False, [0, 0], 1, mask)
-        g_x = cb([True, False, False])[0] if need_x else None
-        g_w = None
-        if need_w:
-            g_w = torch.empty_like(weight)
-
-            def run_wgt():
-                nws = _lib.lib.smd_conv7x7s2_workspace_bytes(B, C, CO, H, W)
-                ws = torch.empty(max(nws, 256), device=dev, dtype=torch.uint8)
-                call('smd_conv7x7s2_bwd_weight', x.data_ptr(), g_y.data_ptr(), g_w.data_ptr(), ws.data_ptr(), nws, B, C, CO, H, W, _stream())
-            ref_wgt = lambda: cb([False, True, False])[1]
-            if not (ctx.served and _routed('wgt_s', B, C, CO, H, W, False, run_wgt, ref_wgt) and _ran(False, run_wgt)): g_w = ref_wgt()
-        return g_x, g_w
-
-
-def conv7x7s2_stem(x, weight):
-    """`F.conv2d(x, weight (CO,C,7,7), stride=2, padding=3)`, bias-free: the ResNet encoders' stem (`conv1` of the timm ResNets built at
-    src/networks/depth.py:95-98, src/networks/pose.py:39-41).  x (B,C,H,W) fp32 -> (B,CO,(H-1)//2+1,(W-1)//2+1) fp32.  CO = 64 with C = 3 or 6: forward and
-    weight gradient on the split-bf16 MFMA kernels (`smd_conv7x7s2_*`) or MIOpen, per operator and shape (`_conv_route`, ops `fwd_s` / `wgt_s`;
-    `set_conv_route('mfma')` pins the kernels); any other channel count goes to MIOpen."""
-    return _Conv7x7s2Stem.apply(x, weight)
 
 
 class _EluUpCatPad(torch.autograd.Function):
