@@ -1,11 +1,12 @@
-"""Which device's stream a launch goes to, and the operand checks every operator starts with.  Private: `functional` and `conv_ops` import it."""
+"""Which device's stream a launch goes to, the operand checks every operator starts with, and how operands and workspaces reach the C call.
+Private: the operator modules import it."""
 from __future__ import annotations
 
 import threading
 
 import torch
 
-from ._lib import call as _raw_call
+from ._lib import call as _raw_call, ptr_array
 
 # Device of the operands of the operator this THREAD is executing: launches go to ITS current stream.  Thread-local, and set at
 # the top of every forward (by `_check`) AND every backward (by `_on`): autograd runs the backward of each device on its own
@@ -52,3 +53,20 @@ def _check_fb(name: str, t: torch.Tensor, shape=None) -> torch.Tensor:
     if t.dtype not in (torch.float32, torch.bfloat16): raise TypeError(f'{name} must be float32 or bfloat16, got {t.dtype}')
     if shape is not None and tuple(t.shape) != tuple(shape): raise ValueError(f'{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}')
     return t.contiguous()
+
+
+def _ptr(t):
+    """The device pointer of an optional operand: None (NULL in the C call) for None."""
+    return t.data_ptr() if t is not None else None
+
+
+def _ptrs(ts):
+    """The pointer array of a sequence of tensors (the per-scale operands)."""
+    return ptr_array([t.data_ptr() for t in ts])
+
+
+def _workspace(device, query, *args, floor: int = 0):
+    """-> (uint8 workspace, nbytes): `nbytes = query(*args)`, one of the library's `*_workspace_bytes` (or a size already asked for), is what the C call
+    takes as `workspace_bytes`; at least `floor` bytes are allocated, so that a launch that needs no workspace still gets a pointer."""
+    nbytes = query(*args) if callable(query) else query
+    return torch.empty(max(nbytes, floor), device=device, dtype=torch.uint8), nbytes

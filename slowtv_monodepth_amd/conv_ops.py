@@ -7,7 +7,7 @@ from collections import namedtuple
 import torch
 
 from . import _lib
-from ._device import _check, _check_fb, _on, _stream, call
+from ._device import _check, _check_fb, _on, _ptr, _stream, _workspace, call
 from .conv_routing import serve
 
 _BF = torch.bfloat16
@@ -19,10 +19,8 @@ def _thin_bwd(xp, weight, g_y, want_x, want_w):
     B, C, H, W = xp.shape
     g_xp = torch.empty_like(xp) if want_x else None
     g_w = torch.empty_like(weight) if want_w else None
-    nbytes = _lib.lib.smd_conv3x3_thin_workspace_bytes(B, C, H - 2, W - 2) if want_w else 0
-    ws = torch.empty(max(nbytes, 256), device=xp.device, dtype=torch.uint8) if want_w else None
-    call('smd_conv3x3_thin_bwd', xp.data_ptr(), weight.data_ptr(), g_y.data_ptr(), g_xp.data_ptr() if want_x else None, g_w.data_ptr() if want_w else None,
-         ws.data_ptr() if want_w else None, nbytes, B, C, H - 2, W - 2, _stream())
+    ws, nbytes = _workspace(xp.device, _lib.lib.smd_conv3x3_thin_workspace_bytes, B, C, H - 2, W - 2, floor=256) if want_w else (None, 0)
+    call('smd_conv3x3_thin_bwd', xp.data_ptr(), weight.data_ptr(), g_y.data_ptr(), _ptr(g_xp), _ptr(g_w), _ptr(ws), nbytes, B, C, H - 2, W - 2, _stream())
     return g_xp, g_w
 
 
@@ -69,9 +67,9 @@ def _served(C, CO, zpad, sized) -> _Served:
 
 def _mfma_pack(weight, C, CO, pieces, want_fwd, want_bwd):
     nbytes = _lib.lib.smd_conv3x3_mfma_packed_bytes(C, CO, pieces)
-    wf = torch.empty(max(nbytes, 256), device=weight.device, dtype=torch.uint8) if want_fwd else None
-    wb = torch.empty(max(nbytes, 256), device=weight.device, dtype=torch.uint8) if want_bwd else None
-    call('smd_conv3x3_mfma_pack', weight.data_ptr(), wf.data_ptr() if wf is not None else None, wb.data_ptr() if wb is not None else None, C, CO, pieces, _stream())
+    wf = _workspace(weight.device, nbytes, floor=256)[0] if want_fwd else None
+    wb = _workspace(weight.device, nbytes, floor=256)[0] if want_bwd else None
+    call('smd_conv3x3_mfma_pack', weight.data_ptr(), _ptr(wf), _ptr(wb), C, CO, pieces, _stream())
     return wf, wb
 
 
@@ -81,7 +79,7 @@ def _mfma_ws_bytes(B, C, CO, h, w, zpad):
 
 def _mfma_launch(entry, zpad, a, b, out, nws, dims, pieces):
     """`smd_conv3x3[z]_mfma_<entry>` into `out` (returned) on a workspace of its own; `dims` = (B, C, CO, h, w)."""
-    ws = torch.empty(max(nws, 256), device=out.device, dtype=torch.uint8)
+    ws, nws = _workspace(out.device, nws, floor=256)
     call(('smd_conv3x3z_mfma_' if zpad else 'smd_conv3x3_mfma_') + entry, a.data_ptr(), b.data_ptr(), out.data_ptr(), ws.data_ptr(), nws, *dims, pieces, _stream())
     return out
 
@@ -200,7 +198,7 @@ class _Conv7x7s2Stem(torch.autograd.Function):
         y = torch.empty((B, CO, ho, wo), device=x.device, dtype=torch.float32)
 
         def run_mfma():                                     # the pack included: every call pays it
-            wp = torch.empty(_lib.lib.smd_conv7x7s2_packed_bytes(C, CO), device=x.device, dtype=torch.uint8)
+            wp, _ = _workspace(x.device, _lib.lib.smd_conv7x7s2_packed_bytes, C, CO)
             call('smd_conv7x7s2_pack', weight.data_ptr(), wp.data_ptr(), C, CO, _stream())
             call('smd_conv7x7s2_fwd', x.data_ptr(), wp.data_ptr(), y.data_ptr(), B, C, CO, H, W, _stream())
             return y
@@ -224,8 +222,7 @@ class _Conv7x7s2Stem(torch.autograd.Function):
             g_w = torch.empty_like(weight)
 
             def run_wgt():
-                nws = _lib.lib.smd_conv7x7s2_workspace_bytes(B, C, CO, H, W)
-                ws = torch.empty(max(nws, 256), device=dev, dtype=torch.uint8)
+                ws, nws = _workspace(dev, _lib.lib.smd_conv7x7s2_workspace_bytes, B, C, CO, H, W, floor=256)
                 call('smd_conv7x7s2_bwd_weight', x.data_ptr(), g_y.data_ptr(), g_w.data_ptr(), ws.data_ptr(), nws, B, C, CO, H, W, _stream())
                 return g_w
             g_w = serve(('wgt_s', B, C, CO, H, W), run_wgt, lambda: cb([False, True, False])[1], eligible=ctx.served)
