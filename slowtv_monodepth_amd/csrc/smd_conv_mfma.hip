@@ -9,6 +9,10 @@
 // each exact in the fp32 accumulator's product stage; what is dropped (a1 b2 + a2 b1 + a2 b2) is below 2^-25 |a b|, under the rounding of an fp32
 // multiply-add.  Six `v_mfma_f32_32x32x16_bf16` per K step of 16 = 6/16 of the f32 MFMA's time for the same arithmetic: a ceiling of 2.67 x the fp32
 // matrix peak with fp32-class error (tests: <= 2e-6 of the tensor's max against fp64 `conv2d`, the same bound the f32-MFMA kernels are held to).
+// That bound is the kernels' own fp32 accumulation noise (1e-7 to 1e-6 of the maximum), and a third-order product is at most 2^-18 of a product: one wrong
+// piece at one tap, channel half, K chunk or fragment slot stays under it.  tests/test_gpu_conv_exact.py therefore also runs these kernels (and the stem's) on
+// operands where nothing rounds — piece-built values whose dropped products are exactly zero, one product per output element, and dense small integers
+// (tests/conv_exact.py) — and asks for the fp64 result bit for bit: any kept product missing, doubled or read from the wrong place fails there.
 // PIECES = 2 (three products, 16 significant bits, "better than TF32") exists as an experiment knob only; PIECES = 1 is plain bf16.
 // Round 7: the same kernels serve the ResNet encoders' zero-padded 3x3 stride-1 layers (OFF = 1 below, k_conv_wgrad_dma's ZP form; profiles/r07_encoder_convs.txt).
 //
