@@ -247,6 +247,17 @@ int smd_regression_fwd(const float* pred, const float* target, const uint8_t* ma
 int smd_regression_bwd(const float* pred, const float* target, const uint8_t* mask, size_t N, int flags, float* stats,
                        const float* g_loss, float* g_pred, float* g_target, void* workspace, size_t workspace_bytes, void* stream);
 
+/* smd_depth_metrics: the training-time validation metrics of `MonoDepthModule.compute_metrics` (src/core/trainer.py:531-552, src/utils/metrics.py)
+ * in one call.  pred (b,1,h,w) depth, target (b,1,H,W) (any size relation): p0 = clamp(bilinear(pred -> (H,W), align_corners=False), min, max);
+ * valid = min < target < max (NaN: invalid); both per-sample LOWER medians (rank (n-1)/2, torch.nanmedian) over the valid pixels by an exact radix
+ * select; p = clamp(p0 * med_t/med_p, min, max).
+ * -> values (b,5): MAE, RMSE, LogSI (x100), AbsRel (x100), Acc (x100; count(q < 1.25) over the SUM of q = max(t/p, p/t), as the reference's DeltaAcc),
+ *    NaN for a sample without a valid pixel; medians (b,2): med_p, med_t; counts (b) int32: valid pixels.
+ * Deterministic (integer atomics and fixed-order fp64 sums only); no synchronisation, no copy to the host; the workspace may be reused dirty. */
+size_t smd_depth_metrics_workspace_bytes(int b, int H, int W);
+int smd_depth_metrics(const float* pred, const float* target, int b, int h, int w, int H, int W, float min_depth, float max_depth,
+                      float* values, float* medians, int* counts, void* workspace, size_t workspace_bytes, void* stream);
+
 /* smd_recon_reduce_*: the reduction half of `ReconstructionLoss.forward` on per-support error maps
  * (reconstruction.py:43-57, 59-77, 125).  err_warp (n,B,h,w); err_static (n,B,h,w) (required with SMD_USE_AUTOMASK);
  * mask (B,n,h,w) or NULL: the predictive weighting mask of `apply_mask` (reconstruction.py:46-57), reference layout, applied to the

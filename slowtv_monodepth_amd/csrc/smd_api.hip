@@ -1,6 +1,7 @@
 // smd_api.hip — the extern "C" boundary (include/smd_hotpath.h): argument validation, workspace carving, launches.
 // No torch types, no allocation, no synchronisation; every launch goes to the caller's stream.
 #include <limits.h>
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -49,11 +50,13 @@ int max_strips(int h, int w, int cols) { return smd::ceil_div(w, cols)*smd::ceil
 //   block stays four strips of one scale instead of the four scales of one strip).
 //   conv_two_tiles (1: the decoder's wide convolutions run two tiles of 32 output channels over one staged patch — eight waves per block — where the layer has
 //   them; default 0: measured neutral, profiles/r06_conv_mfma_ablations.txt; same bits either way).
+//   metrics_store_pred (default 1: smd_depth_metrics writes the resampled prediction to its workspace in the first pass and re-reads it; 0: every pass
+//   recomputes the four taps at the valid pixels; same bits either way; 86 vs 104 us at b = 12, 375x1242, 5 % density: profiles/val_metrics_times.txt).
 //   Experiments builds only: fwd_ahead (2: tap gathers two rows ahead, measured slower), bwd_pair (two supports per wave, dropped), smooth_chain.
 struct KnobDef { const char* name; bool experiment; };
 constexpr KnobDef kKnobs[] = {{"fwd_rh", false}, {"bwd_rh", false}, {"fwd_taper_b", false}, {"bwd_taper_b", false}, {"fwd_taper_rh", false},
                               {"bwd_taper_rh", false}, {"fwd_ni", false}, {"fwd_share", false}, {"bwd_skip", false}, {"bwd_wps", false},
-                              {"bwd_guest_finalize", false}, {"bwd_direct_level", false}, {"loss_path_guests", false}, {"bwd_live", false}, {"bwd_scales_block", false}, {"conv_two_tiles", false},
+                              {"bwd_guest_finalize", false}, {"bwd_direct_level", false}, {"loss_path_guests", false}, {"bwd_live", false}, {"bwd_scales_block", false}, {"conv_two_tiles", false}, {"metrics_store_pred", false},
                               {"fwd_ahead", true}, {"bwd_pair", true}, {"smooth_chain", true}};
 constexpr int kNumKnobs = sizeof(kKnobs)/sizeof(kKnobs[0]);
 constexpr int kKnobUnset = INT_MIN;
@@ -736,6 +739,30 @@ int smd_regression_bwd(const float* pred, const float* target, const uint8_t* ma
   if (workspace_bytes < smd_regression_workspace_bytes(N)) return fail(SMD_E_WORKSPACE, "workspace too small");
   return check_launch(smd::launch_regression_bwd(pred, target, mask, N, flags, stats, g_loss, g_pred, g_target, (float*)workspace, (hipStream_t)stream),
                       "regression_bwd");
+}
+
+// workspace of smd_depth_metrics: the radix histograms (zeroed by the call) | the blocks' fp64 partial sums | the resampled prediction
+static size_t metrics_partial_bytes(int b, int H, int W) { return align256((size_t)b*smd::metrics_blocks_per_sample(b, H, W)*smd::kMetSums*sizeof(double)); }
+
+size_t smd_depth_metrics_workspace_bytes(int b, int H, int W) {
+  if (b < 1 || H < 1 || W < 1 || b > 65535 || (size_t)H*W >= ((size_t)1 << 31)) return 0;
+  return align256(smd::metrics_hist_bytes(b)) + metrics_partial_bytes(b, H, W) + align256((size_t)b*H*W*sizeof(float));
+}
+
+int smd_depth_metrics(const float* pred, const float* target, int b, int h, int w, int H, int W, float min_depth, float max_depth, float* values,
+                      float* medians, int* counts, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!pred || !target || !values || !medians || !counts || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (b < 1 || h < 1 || w < 1 || H < 1 || W < 1 || b > 65535) return fail(SMD_E_INVALID, "invalid sizes b=%d h=%d w=%d H=%d W=%d", b, h, w, H, W);
+  if ((size_t)H*W >= ((size_t)1 << 31) || (size_t)h*w >= ((size_t)1 << 31)) return fail(SMD_E_INVALID, "h*w and H*W must stay below 2^31");
+  if (!(min_depth > 0.f)) return fail(SMD_E_INVALID, "Min depth must be greater than 0. (%g)", min_depth);
+  if (!(max_depth > min_depth) || !(max_depth < INFINITY)) return fail(SMD_E_INVALID, "Max depth must be finite and greater than min. (%g vs. %g)", max_depth, min_depth);
+  const size_t need = smd_depth_metrics_workspace_bytes(b, H, W);
+  if (workspace_bytes < need) return fail(SMD_E_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, need);
+  char* ws = (char*)workspace;
+  unsigned* hist = (unsigned*)ws; ws += align256(smd::metrics_hist_bytes(b));
+  double* partial = (double*)ws; ws += metrics_partial_bytes(b, H, W);
+  return check_launch(smd::launch_depth_metrics(pred, target, b, h, w, H, W, min_depth, max_depth, values, medians, counts, hist, partial, (float*)ws,
+                                                knob("metrics_store_pred", 1) != 0, (hipStream_t)stream), "depth_metrics");
 }
 
 size_t smd_recon_reduce_workspace_bytes(int B, int h, int w) {

@@ -341,6 +341,12 @@ hipError_t launch_regression_fwd(const float* pred, const float* target, const u
                                  float* stats, float* ws, hipStream_t st);
 hipError_t launch_regression_bwd(const float* pred, const float* target, const uint8_t* mask, size_t N, int flags, float* stats,
                                  const float* g_loss, float* g_pred, float* g_target, float* ws, hipStream_t st);
+// smd_metrics.hip: the validation depth metrics (radix-select medians + deterministic sums); the workspace is hist | partial | p0
+constexpr int kMetBlock = 256, kMetBins = 2048, kMetSums = 7;
+int metrics_blocks_per_sample(int b, int H, int W);
+size_t metrics_hist_bytes(int b);
+hipError_t launch_depth_metrics(const float* pred, const float* target, int b, int h, int w, int H, int W, float lo, float hi, float* values,
+                                float* medians, int* counts, unsigned* hist, double* partial, float* p0, bool store, hipStream_t st);
 hipError_t launch_pose_fwd(const float* aa, const float* t, const uint8_t* invert, int N, float* T, hipStream_t st);
 hipError_t launch_pose_bwd(const float* aa, const float* t, const uint8_t* invert, int N, const float* g_T, float* g_aa, float* g_t, hipStream_t st);
 hipError_t launch_intrinsics_fwd(const float* fs, const float* cs, const float* Kin, int b, int h, int w, float* K, float* Kinv, hipStream_t st);

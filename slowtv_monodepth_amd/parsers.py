@@ -8,7 +8,7 @@ from torch import nn, optim
 
 from . import registry as reg
 
-__all__ = ['get_net', 'get_loss', 'get_opt', 'get_sched']
+__all__ = ['get_net', 'get_loss', 'get_opt', 'get_sched', 'get_metrics']
 
 
 def get_net(cfg: dict) -> nn.ModuleDict:
@@ -87,3 +87,10 @@ def get_sched(opt: optim.Optimizer, cfg: dict) -> dict:
         if k not in reg.SCHED_REG: raise ValueError(f'Error using "{k}" in {list(reg.SCHED_REG)}')
         out[k] = reg.SCHED_REG[k](opt, **kw)
     return out
+
+
+def get_metrics() -> nn.ModuleDict:
+    """The depth metrics monitored during validation (src/tools/parsers.py:272-280)."""
+    from . import metrics
+    return nn.ModuleDict({'MAE': metrics.MAE(), 'RMSE': metrics.RMSE(), 'LogSI': metrics.ScaleInvariant(mode='log'), 'AbsRel': metrics.AbsRel(),
+                          'Acc': metrics.DeltaAcc(delta=1.25)})

@@ -13,7 +13,7 @@ import torch
 
 from . import ops
 
-__all__ = ['texture', 'kitti_K', 'make_batch']
+__all__ = ['texture', 'kitti_K', 'lidar_depth', 'make_batch']
 
 
 def texture(gen: torch.Generator, b: int, h: int, w: int, shift=(0.0, 0.0), device='cpu', waves: int = 6, coeffs=None):
@@ -38,8 +38,19 @@ def kitti_K(b: int, h: int, w: int, device='cpu') -> torch.Tensor:
     return K[None].repeat(b, 1, 1)
 
 
-def make_batch(b: int, h: int, w: int, supp_idxs=(-1, 1), seed: int = 42, device='cpu'):
-    """-> (x, y, m): x = network inputs (ImageNet-standardised), y = loss inputs (raw [0,1] images, K), m = metadata."""
+def lidar_depth(gen: torch.Generator, b: int, H: int, W: int, device='cpu', density: float = 0.05) -> torch.Tensor:
+    """(b,1,H,W) LiDAR-like ground truth: a smooth positive depth field (2 .. 60 m, nearer towards the bottom rows, modulated by a few sinusoids)
+    kept at about `density` of the pixels and 0 (= no return) elsewhere."""
+    ys, xs = torch.meshgrid(torch.linspace(0, 1, H, device=device), torch.linspace(0, 1, W, device=device), indexing='ij')
+    ph = torch.rand(b, 3, 1, 1, generator=gen, device=device)*2*math.pi
+    field = 2 + 58*(1 - ys)**2*(0.75 + 0.25*torch.sin(6*xs + ph[:, 0])*torch.cos(4*ys + ph[:, 1])) + 0.5*torch.sin(9*xs + ph[:, 2])**2
+    keep = torch.rand(b, H, W, generator=gen, device=device) < density
+    return torch.where(keep, field, torch.zeros_like(field))[:, None]
+
+
+def make_batch(b: int, h: int, w: int, supp_idxs=(-1, 1), seed: int = 42, device='cpu', depth_shape=None):
+    """-> (x, y, m): x = network inputs (ImageNet-standardised), y = loss inputs (raw [0,1] images, K), m = metadata.
+    `depth_shape=(H, W)` adds `y['depth']` (`lidar_depth`), drawn after everything else: the other entries are the same with and without it."""
     gen = torch.Generator(device=device).manual_seed(seed)
     imgs, coeffs = texture(gen, b, h, w, device=device)
     supp = []
@@ -50,4 +61,5 @@ def make_batch(b: int, h: int, w: int, supp_idxs=(-1, 1), seed: int = 42, device
     x = {'imgs': ops.standardize(imgs), 'supp_imgs': ops.standardize(supp), 'supp_idxs': torch.tensor(list(supp_idxs))}
     y = {'imgs': imgs, 'supp_imgs': supp, 'K': kitti_K(b, h, w, device)}
     m = {'supp': [str(i) for i in supp_idxs]}
+    if depth_shape is not None: y['depth'] = lidar_depth(gen, b, int(depth_shape[0]), int(depth_shape[1]), device=device)
     return x, y, m

@@ -25,7 +25,7 @@ from . import io
 from .synthetic import make_batch
 from .trainer import MonoDepthModule
 
-__all__ = ['StepModule', 'FlatAllReduce', 'wrap_ddp', 'train_steps', 'init_distributed', 'main']
+__all__ = ['StepModule', 'FlatAllReduce', 'wrap_ddp', 'train_steps', 'validate', 'init_distributed', 'main']
 
 
 class StepModule(nn.Module):
@@ -223,6 +223,22 @@ def train_steps(model: nn.Module, opt: torch.optim.Optimizer, batch_fn, steps: i
     return losses
 
 
+def validate(module: MonoDepthModule, batch_fn, steps: int) -> dict:
+    """`steps` validation steps with the module in `eval()` (switched back to `train()` afterwards), then ONE all-reduce of the metric states over the
+    ranks.  -> {name: epoch value} as device tensors; the states are reset.  Nothing is read on the host between the steps."""
+    from .metrics import sync_metrics
+    was_training = module.training
+    module.eval()
+    try:
+        for it in range(steps): module.validation_step(batch_fn(it))
+    finally:
+        module.train(was_training)
+    sync_metrics(module.metrics.values())
+    out = {k: m.compute() for k, m in module.metrics.items()}
+    for m in module.metrics.values(): m.reset()
+    return out
+
+
 def dataset_types(cfg: dict) -> list:
     """Dataset types a cfg names.  The reference keys the `dataset` section BY TYPE — `dataset: {kitti_lmdb: {split: ...}}`,
     `parsers.get_ds` iterates `for t, kw in cfg.items()` (src/tools/parsers.py:109-135) — so every key with a (possibly empty)
@@ -285,6 +301,8 @@ def main(argv=None):
     p.add_argument('--shape', default=[192, 640], type=int, nargs=2)
     p.add_argument('--resume', type=Path, default=None, help='checkpoint to continue from (this package\'s last.ckpt or a reference checkpoint): weights, '
                                                                'optimizer and scheduler state, epoch counter')
+    p.add_argument('--val-steps', default=0, type=int, help='validation steps after every epoch (0: none): synthetic batches with LiDAR-like depth, depth metrics printed')
+    p.add_argument('--val-depth-shape', default=[375, 1242], type=int, nargs=2, help='size of the synthetic ground-truth depth maps of the validation batches')
     args = p.parse_args(argv)
 
     cfg = io.load_merge_yaml(*args.cfg_files)
@@ -305,6 +323,7 @@ def main(argv=None):
                          'pass --synthetic-data to run the cfg on synthetic triplets of its shape, or drop the dataset `type`')
     supp_idxs = dataset_supp_idxs(cfg)
     batch = make_batch(b, args.shape[0], args.shape[1], supp_idxs, seed=args.seed + rank, device=device)
+    val_batch = make_batch(b, args.shape[0], args.shape[1], supp_idxs, seed=args.seed + 1000 + rank, device=device, depth_shape=args.val_depth_shape) if args.val_steps > 0 else None
     model = wrap_ddp(StepModule(module), device)
     save_dir = args.ckpt_dir/args.name/f'{args.version:03}'
     if rank == 0: save_dir.mkdir(parents=True, exist_ok=True)
@@ -325,9 +344,11 @@ def main(argv=None):
                              detect_anomaly=bool(tcfg.get('detect_anomaly', False)))
         if sched is not None: sched.step()
         last = losses[-1].item()
+        dt = time.time() - t0
+        val = validate(module, lambda it: tuple(dict(d) for d in val_batch), args.val_steps) if val_batch is not None else {}   # (collective: every rank)
         if rank == 0:
-            dt = time.time() - t0
             print(f'epoch {epoch}: loss {last:.6f}  {args.steps*b*world/dt:.1f} img/s', flush=True)
+            if val: print(f'epoch {epoch}: val ' + '  '.join(f'{k} {v.item():.4f}' for k, v in val.items()), flush=True)
             from .networks.checkpoint import reference_checkpoint
             torch.save(reference_checkpoint(module, epoch=epoch, global_step=(epoch + 1)*args.steps, optimizer=opt, scheduler=sched), save_dir/'last.ckpt')
     if world > 1: dist.destroy_process_group()

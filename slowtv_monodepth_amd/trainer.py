@@ -167,6 +167,7 @@ class MonoDepthModule(nn.Module):
         self.nets = parsers.get_net(cfg['net'])
         self.losses, self.weights = parsers.get_loss(copy.deepcopy(cfg['loss']))
         self.backend = loss_backend or HipLossBackend()
+        self.metrics = parsers.get_metrics()   # validation depth metrics (src/core/trainer.py:48); their buffers are non-persistent: the state dict is unchanged
         self._w_cache = {}     # the frozen loss weights as host numbers, re-read whenever a state dict (checkpoint, --resume) rewrote them: `_loss_weight`
         # Losses whose inputs only networks outside this package produce (the autoencoder network and the
         # virtual-stereo decoder head are out of scope; their handlers and criteria exist and are parity-tested on their own):
@@ -407,6 +408,51 @@ class MonoDepthModule(nn.Module):
             # prep for the previous batch nor keep that batch (and its 150 MB packed buffer) alive
             self._y = self._prepared = self._K_inv = None
         return loss, loss_dict, fwd
+
+    def _default_metrics(self) -> bool:
+        """The metric set is the reference's five (`parsers.get_metrics`), in the column order of the fused operator."""
+        from . import metrics as M
+        from .metric_ops import METRIC_ORDER
+        m = self.metrics
+        if tuple(m.keys()) != METRIC_ORDER: return False
+        kinds = (M.MAE, M.RMSE, M.ScaleInvariant, M.AbsRel, M.DeltaAcc)
+        modes = ('raw', 'raw', 'log', 'raw', 'raw')
+        return all(type(m[k]) is c and m[k].mode == md for k, c, md in zip(METRIC_ORDER, kinds, modes)) and m['Acc'].delta == 1.25
+
+    @torch.no_grad()
+    def compute_metrics(self, pred: torch.Tensor, target: torch.Tensor, fused=None) -> dict:
+        """Depth metrics of one batch (src/core/trainer.py:531-552): pred (b,1,h,w) scaled depth, target (b,1,H,W) LiDAR depth -> {name: batch value}
+        (device tensors; nothing is read on the host), and the metrics' running states are updated.
+        With the default five metrics and fp32 GPU tensors this is ONE `functional.depth_metrics` call whose columns feed the states; otherwise
+        (`fused=False` forces it) the reference's sequence on ATen: resize, clamp, NaN mask, `nanmedian` ratio, clamp, `metric(pred, target)`."""
+        lo, hi = self.min_depth or 0.1, self.max_depth or 100
+        if fused is None: fused = pred.is_cuda and target.is_cuda and pred.dtype == target.dtype == torch.float32 and self._default_metrics()
+        if fused:
+            from . import functional as F
+            from .metric_ops import METRIC_ORDER
+            values, _, _ = F.depth_metrics(pred, target, lo, hi)
+            b, sums = values.shape[0], values.sum(dim=0)
+            for k, name in enumerate(METRIC_ORDER): self.metrics[name].accumulate(sums[k], b)
+            batch = sums/b
+            return {name: batch[k] for k, name in enumerate(METRIC_ORDER)}
+        from .ops import interpolate_like
+        pred = interpolate_like(pred.float(), target, mode='bilinear', align_corners=False).clamp(lo, hi)
+        target = target.float()
+        mask = (target > lo) & (target < hi)
+        nan = target.new_tensor(float('nan'))
+        target, pred = target.where(mask, nan).flatten(1), pred.where(mask, nan).flatten(1)
+        r = target.nanmedian(dim=1, keepdim=True).values/pred.nanmedian(dim=1, keepdim=True).values
+        pred, target = (pred*r).clamp(lo, hi), target.clamp(lo, hi)
+        return {k: metric(pred, target) for k, metric in self.metrics.items()}
+
+    def validation_step(self, batch):
+        """`step(batch, mode='val')` without gradients, then the depth metrics when the batch carries LiDAR depth (src/core/trainer.py:110-113, 186-188).
+        -> (loss, loss_dict, fwd, metrics); metrics is {} without `y['depth']`.  (Switching the module to `eval()` is the caller's business, as in Lightning.)"""
+        with torch.no_grad():
+            loss, loss_dict, fwd = self.step(batch, mode='val')
+            y = batch[1]
+            metrics = self.compute_metrics(fwd['depth_up'][0].detach(), y['depth']) if 'depth' in y else {}
+        return loss, loss_dict, fwd, metrics
 
     def _prepare_frames(self, y: dict, stream=None):
         """Launch the frame-only half of `img_recon` before the networks (it needs `y['imgs']`, `y['supp_imgs']` only).  With the
