@@ -10,6 +10,11 @@
  *     reference's own layouts (NCHW images, row-major 4x4 matrices).  Inputs are const; the library
  *     never allocates, frees or retains a pointer; the caller (PyTorch) owns every buffer.
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream).  Nothing synchronises.
+ *   - Alignment: every pointer handed in (operands, outputs, workspaces) is 16-BYTE ALIGNED.  The kernels go through naturally aligned vector
+ *     types (16-byte float4 rows, float2 pairs, dwords over bf16 rows); what they do at an element-aligned base is undefined.  Exceptions, read and
+ *     written one element at a time: the per-channel vectors of smd_bn_* (running statistics, saved mean / inverse deviation: rows of a (2,C) array)
+ *     and the per-pixel statistics rows of smd_layernorm_cf_* need only their element's alignment.  An allocator's blocks satisfy this; a contiguous
+ *     view at a storage offset may not, and the Python layer copies such an operand before the call (`_device._aligned`).
  *   - Return value: 0 on success, negative on error (SMD_E_*); smd_last_error() returns the message
  *     for the calling thread.
  *   - Symbols: b batch, n support frames, S scales, (h, w) image size.  Every (S,b,...) tensor is

@@ -37,13 +37,24 @@ def _stream() -> int:
     return torch.cuda.current_stream(dev if dev is not None else torch.cuda.current_device()).cuda_stream
 
 
+ALIGN = 16     # bytes: what the C ABI requires of every pointer it is handed (include/smd_hotpath.h)
+
+
+def _aligned(t: torch.Tensor) -> torch.Tensor:
+    """`t` contiguous at a base the C ABI accepts.  The kernels read and write through naturally aligned vector types (16-byte `f4` rows, `float2`
+    pairs, dwords over bf16 rows).  The caching allocator's blocks are aligned far beyond that, but a contiguous VIEW with a storage offset (a slice of a flat
+    parameter or gradient bucket) is only element-aligned: it is copied to a block of its own.  One modulo per operand."""
+    t = t.contiguous()
+    return t if t.data_ptr() % ALIGN == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 def _check(name: str, t: torch.Tensor, shape=None) -> torch.Tensor:
     if not isinstance(t, torch.Tensor): raise TypeError(f'{name} must be a Tensor, got {type(t)}')
     if not t.is_cuda: raise RuntimeError(f'{name} must live on the GPU: the view-synthesis hot path has no CPU implementation')
     _tls.device = t.device
     if t.dtype != torch.float32: raise TypeError(f'{name} must be float32 (the loss path is fp32 only), got {t.dtype}')
     if shape is not None and tuple(t.shape) != tuple(shape): raise ValueError(f'{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}')
-    return t.contiguous()
+    return _aligned(t)
 
 
 def _check_fb(name: str, t: torch.Tensor, shape=None) -> torch.Tensor:
@@ -52,7 +63,7 @@ def _check_fb(name: str, t: torch.Tensor, shape=None) -> torch.Tensor:
     if not t.is_cuda: raise RuntimeError(f'{name} must live on the GPU')
     if t.dtype not in (torch.float32, torch.bfloat16): raise TypeError(f'{name} must be float32 or bfloat16, got {t.dtype}')
     if shape is not None and tuple(t.shape) != tuple(shape): raise ValueError(f'{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}')
-    return t.contiguous()
+    return _aligned(t)
 
 
 def _ptr(t):

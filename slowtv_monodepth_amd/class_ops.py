@@ -5,7 +5,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from ._device import _check, _on, _ptr, _ptrs, _stream, _workspace, call
+from ._device import _aligned, _check, _on, _ptr, _ptrs, _stream, _workspace, call
 from ._lib import FLAGS, REGR_FLAGS, int_array
 
 
@@ -94,7 +94,7 @@ class _Regression(torch.autograd.Function):
             # The reference multiplies by the mask (`mask*err`, `err.sum()/mask.sum()`, src/losses/regression.py:72-74), so a float mask
             # there is a per-pixel WEIGHT; the kernel implements the 0/1 case every caller on this path uses (automask, validity).
             if mask.dtype.is_floating_point: raise TypeError('RegressionLoss: pass a bool (or uint8 0/1) mask; weighting masks are not part of the accelerated path')
-            mask = (mask if mask.dtype == torch.bool else mask != 0).contiguous().view(torch.uint8)
+            mask = _aligned(mask if mask.dtype == torch.bool else mask != 0).view(torch.uint8)
         N, dev = pred.numel(), pred.device
         loss = torch.empty((), device=dev, dtype=torch.float32); err = torch.empty_like(pred)
         stats = torch.zeros(8, device=dev, dtype=torch.float32)
@@ -114,7 +114,7 @@ class _Regression(torch.autograd.Function):
         g_target = torch.empty_like(target) if ctx.needs_input_grad[1] else None
         if g_pred is None and g_target is None: return None, None, None, None
         ws, nbytes = _workspace(pred.device, _lib.lib.smd_regression_workspace_bytes, N)
-        call('smd_regression_bwd', pred.data_ptr(), target.data_ptr(), _ptr(mask), N, ctx.flags, stats.data_ptr(), g_loss.to(torch.float32).contiguous().data_ptr(),
+        call('smd_regression_bwd', pred.data_ptr(), target.data_ptr(), _ptr(mask), N, ctx.flags, stats.data_ptr(), _aligned(g_loss.to(torch.float32)).data_ptr(),
              _ptr(g_pred), _ptr(g_target), ws.data_ptr(), nbytes, _stream())
         return g_pred, g_target, None, None
 
@@ -153,7 +153,7 @@ class _ReconReduce(torch.autograd.Function):
         n, B, h, w, flags = ctx.meta
         g = torch.empty((n, B, h, w), device=sel.device, dtype=torch.float32)
         g_mask = torch.empty_like(mask) if mask is not None else None
-        call('smd_recon_reduce_bwd', sel.data_ptr(), g_loss.to(torch.float32).contiguous().data_ptr(), g.data_ptr(), _ptr(err_warp), _ptr(err_static), _ptr(mask),
+        call('smd_recon_reduce_bwd', sel.data_ptr(), _aligned(g_loss.to(torch.float32)).data_ptr(), g.data_ptr(), _ptr(err_warp), _ptr(err_static), _ptr(mask),
              _ptr(g_mask), n, B, h, w, flags, _stream())
         return g, None, g_mask, None, None, None
 
@@ -235,7 +235,7 @@ class _ScaleMean(torch.autograd.Function):
     def backward(ctx, g_loss):
         xs = ctx.saved_tensors
         _on(xs[0])
-        g_loss = g_loss.float().contiguous()
+        g_loss = _aligned(g_loss.float())
         gs = [torch.empty_like(x) for x in xs]
         call('smd_scale_mean_bwd', _ptrs(xs), _lib.i64_array([x.numel() for x in xs]), len(xs), ctx.mode, g_loss.data_ptr(), _ptrs(gs), _stream())
         return (None, *gs)

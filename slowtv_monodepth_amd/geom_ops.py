@@ -1,7 +1,7 @@
 """The pose / intrinsics prologue of the training step as `torch.autograd.Function`s (`smd_pose_*`, `smd_intrinsics_*`).  `functional` re-exports the wrappers."""
 import torch
 
-from ._device import _check, _on, _ptr, _stream, call
+from ._device import _aligned, _check, _on, _ptr, _stream, call
 
 
 class _PoseMatrices(torch.autograd.Function):
@@ -14,7 +14,7 @@ class _PoseMatrices(torch.autograd.Function):
         N = aa.shape[0]
         if invert is not None:
             if invert.dtype != torch.uint8 or tuple(invert.shape) != (N,) or not invert.is_cuda: raise ValueError('invert must be a CUDA uint8 (N,) tensor')
-            invert = invert.contiguous()
+            invert = _aligned(invert)
         T = torch.empty((N, 4, 4), device=aa.device, dtype=torch.float32)
         call('smd_pose_fwd', aa.data_ptr(), t.data_ptr(), _ptr(invert), N, T.data_ptr(), _stream())
         ctx.save_for_backward(aa, t, invert)
@@ -24,7 +24,7 @@ class _PoseMatrices(torch.autograd.Function):
     def backward(ctx, g_T):
         aa, t, invert = ctx.saved_tensors
         _on(aa)
-        g_T = g_T.contiguous()
+        g_T = _aligned(g_T)
         g_aa, g_t = torch.empty_like(aa), torch.empty_like(t)
         call('smd_pose_bwd', aa.data_ptr(), t.data_ptr(), _ptr(invert), aa.shape[0], g_T.data_ptr(), g_aa.data_ptr(), g_t.data_ptr(), _stream())
         return g_aa, g_t, None
@@ -54,7 +54,7 @@ class _Intrinsics(torch.autograd.Function):
         _on(fs)
         h, w = ctx.size
         g_fs, g_cs = torch.empty_like(fs), torch.empty_like(cs)
-        call('smd_intrinsics_bwd', fs.data_ptr(), cs.data_ptr(), fs.shape[0], h, w, g_K.contiguous().data_ptr(), g_Kinv.contiguous().data_ptr(), g_fs.data_ptr(),
+        call('smd_intrinsics_bwd', fs.data_ptr(), cs.data_ptr(), fs.shape[0], h, w, _aligned(g_K).data_ptr(), _aligned(g_Kinv).data_ptr(), g_fs.data_ptr(),
              g_cs.data_ptr(), _stream())
         return g_fs, g_cs, None, None
 

@@ -5,7 +5,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from ._device import _check, _check_fb, _on, _ptr, _stream, _workspace, call
+from ._device import _aligned, _check, _check_fb, _on, _ptr, _stream, _workspace, call
 
 _BF = torch.bfloat16
 
@@ -31,7 +31,7 @@ class _EluPad(torch.autograd.Function):
         g_x = torch.empty_like(x)
         g_b = torch.empty_like(bias) if (bias is not None and ctx.needs_input_grad[1]) else None
         ws, nbytes = _workspace(x.device, _lib.lib.smd_decoder_glue_workspace_bytes, B, C, h, w) if g_b is not None else (None, 0)
-        call('smd_elu_pad_bwd', x.data_ptr(), _ptr(bias), g_out.to(ctx.out_dtype).contiguous().data_ptr(), g_x.data_ptr(), _ptr(g_b), _ptr(ws), nbytes, B, C, h, w,
+        call('smd_elu_pad_bwd', x.data_ptr(), _ptr(bias), _aligned(g_out.to(ctx.out_dtype)).data_ptr(), g_x.data_ptr(), _ptr(g_b), _ptr(ws), nbytes, B, C, h, w,
              ctx.apply_elu, ctx.dt, _stream())
         return g_x, g_b, None, None
 
@@ -162,7 +162,7 @@ class _EluUpCatPad(torch.autograd.Function):
         g_skip = torch.empty((B, Cs, 2*h, 2*w), device=a.device, dtype=ctx.skip_dtype) if (Cs and ctx.needs_input_grad[2]) else None
         if g_a is None and g_skip is None: return None, None, None, None
         ws, nbytes = _workspace(a.device, _lib.lib.smd_decoder_glue_workspace_bytes, B, Ca, h, w) if g_b is not None else (None, 0)
-        call('smd_elu_up_cat_pad_bwd', a.data_ptr(), _ptr(bias), g_out.to(ctx.out_dtype).contiguous().data_ptr(), _ptr(g_a), _ptr(g_skip), _ptr(g_b), _ptr(ws), nbytes, B,
+        call('smd_elu_up_cat_pad_bwd', a.data_ptr(), _ptr(bias), _aligned(g_out.to(ctx.out_dtype)).data_ptr(), _ptr(g_a), _ptr(g_skip), _ptr(g_b), _ptr(ws), nbytes, B,
              Ca, Cs, h, w, ctx.dt, _stream())
         return g_a, g_b, g_skip, None
 
@@ -184,6 +184,9 @@ class _BatchNormAct(torch.autograd.Function):
         if N*H*W < 2: raise ValueError('Expected more than 1 value per channel when training')   # F.batch_norm's own check
         if residual is not None: residual = _check('residual', residual, x.shape)
         weight = _check('weight', weight, (C,)); bias = _check('bias', bias, (C,))
+        for nm, r in (('running_mean', running_mean), ('running_var', running_var)):     # updated IN PLACE, one element at a time: never copied, so they must be usable as they are
+            if r is not None and not (isinstance(r, torch.Tensor) and r.dtype == torch.float32 and r.device == x.device and tuple(r.shape) == (C,) and r.is_contiguous()):
+                raise ValueError(f'{nm} must be a contiguous float32 ({C},) tensor on {x.device} (it is updated in place)')
         y = torch.empty_like(x)
         save = torch.empty((2, C), device=x.device, dtype=torch.float32)
         ws, nbytes = _workspace(x.device, _lib.lib.smd_bn_workspace_bytes, N, C, H*W)
@@ -198,7 +201,7 @@ class _BatchNormAct(torch.autograd.Function):
         x, y, weight, save = ctx.saved_tensors
         _on(x)
         N, C, H, W = x.shape
-        g_y = g_y.contiguous()
+        g_y = _aligned(g_y)
         g_x = torch.empty_like(x)
         g_res = None
         if ctx.has_res and ctx.needs_input_grad[1]: g_res = torch.empty_like(x) if ctx.relu else g_y   # without ReLU the branch gradient IS g_y
@@ -233,7 +236,7 @@ class _MaxPool3x3s2(torch.autograd.Function):
         _on(idx)
         N, C, H, W = ctx.shape
         g_x = torch.empty((N, C, H, W), device=idx.device, dtype=torch.float32)
-        call('smd_maxpool3x3s2_bwd', g_y.contiguous().data_ptr(), idx.data_ptr(), g_x.data_ptr(), N, C, H, W, _stream())
+        call('smd_maxpool3x3s2_bwd', _aligned(g_y).data_ptr(), idx.data_ptr(), g_x.data_ptr(), N, C, H, W, _stream())
         return g_x
 
 
@@ -262,7 +265,7 @@ class _DwConv7x7(torch.autograd.Function):
         x, weight = ctx.saved_tensors
         _on(x)
         N, C, H, W = x.shape
-        g_y = g_y.contiguous()
+        g_y = _aligned(g_y)
         g_x = g_w = g_b = None
         if ctx.needs_input_grad[0]:
             g_x = torch.empty_like(x)
@@ -302,7 +305,7 @@ class _LayerNormCF(torch.autograd.Function):
         _on(x)
         N, C, H, W = x.shape
         if g_y.dtype not in (torch.float32, torch.bfloat16): g_y = g_y.float()
-        g_y = g_y.contiguous()
+        g_y = _aligned(g_y)
         g_x = torch.empty_like(x); g_w = torch.empty_like(weight); g_b = torch.empty_like(weight)
         ws, nbytes = _workspace(x.device, _lib.lib.smd_layernorm_cf_workspace_bytes, N, C, H*W)
         call('smd_layernorm_cf_bwd', x.data_ptr(), g_y.data_ptr(), int(g_y.dtype == torch.bfloat16), weight.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(),

@@ -7,7 +7,7 @@ from collections import namedtuple
 import torch
 
 from . import _lib
-from ._device import _check, _on, _ptr, _ptrs, _stream, _workspace, call
+from ._device import _aligned, _check, _on, _ptr, _ptrs, _stream, _workspace, call
 from ._lib import FLAGS, int_array
 from .class_ops import crop_resize
 from .geom_ops import inv_intrinsics
@@ -231,7 +231,7 @@ class _ImageRecon(torch.autograd.Function):
         depth, tgt, supp_pk, T, K, K_inv, sel = ctx.saved_tensors
         b, n, S, h, w, flags = ctx.meta
         dev = _on(depth)
-        g_loss = g_loss.to(torch.float32).contiguous()
+        g_loss = _aligned(g_loss.to(torch.float32))
         g_depth = torch.empty((S, b, h, w), device=dev, dtype=torch.float32)
         g_T, g_K, g_Ki, kflag = _pose_k_grads(ctx, n, b, dev)
         ws, nbytes = _workspace(dev, _lib.lib.smd_image_recon_workspace_bytes, b, n, S, h, w)
@@ -287,7 +287,7 @@ class _ImageReconDisp(torch.autograd.Function):
         depth_up, packed, T, K, K_inv, sel = ctx.saved_tensors
         b, n, S, h, w, flags, hs, ws, mn, mx = ctx.meta
         dev = _on(depth_up)
-        g_loss = (g_loss if g_loss is not None else torch.zeros((), device=dev)).to(torch.float32).contiguous()
+        g_loss = _aligned((g_loss if g_loss is not None else torch.zeros((), device=dev)).to(torch.float32))
         if g_depth_up is not None: g_depth_up = _check('grad(depth_up)', g_depth_up.reshape(S, b, h, w), (S, b, h, w))
         g_disps = [torch.empty((b, 1, hs[s], ws[s]), device=dev, dtype=torch.float32) for s in range(S)]
         g_T, g_K, g_Ki, kflag = _pose_k_grads(ctx, n, b, dev)
@@ -344,7 +344,7 @@ class _DispSmooth(torch.autograd.Function):
         img, stats, ew, *disps = ctx.saved_tensors
         _on(img)
         hs, ws, keys, S, b, h, w, flags = ctx.meta
-        g_loss = g_loss.to(torch.float32).contiguous()
+        g_loss = _aligned(g_loss.to(torch.float32))
         g_disps = [torch.empty_like(d) for d in disps]
         call('smd_disp_smooth_bwd', _ptrs(disps), int_array(hs), int_array(ws), int_array(keys), S, b, img.data_ptr(), h, w, flags, stats.data_ptr(), _ptr(ew),
              g_loss.data_ptr(), _ptrs(g_disps), _stream())
@@ -376,7 +376,9 @@ class _LossPath(torch.autograd.Function):
         disps, hs, ws = _check_disps(disps, b)
         if aa is not None:
             aa = _check('aa', aa, (n*b, 3)); t = _check('t', t, (n*b, 3))
-            if invert is not None and (invert.dtype != torch.uint8 or tuple(invert.shape) != (n*b,)): raise ValueError('invert must be uint8 (n*b,)')
+            if invert is not None:
+                if invert.dtype != torch.uint8 or tuple(invert.shape) != (n*b,): raise ValueError('invert must be uint8 (n*b,)')
+                invert = _aligned(invert)
         if fs is not None: fs = _check('fs', fs, (b, 2)); cs = _check('cs', cs, (b, 2))
         hs_a, ws_a, keys_a = int_array(hs), int_array(ws), int_array(keys)
         dev = tgt.device
@@ -402,7 +404,7 @@ class _LossPath(torch.autograd.Function):
         b, n, S, h, w, flags, hs, ws, keys, mn, mx, w_rec, w_sm = ctx.meta
         dev = _on(depth_up)
         if g_depth_up is not None: raise NotImplementedError('loss_path_fused: `depth_up` has another differentiable consumer; use image_recon_fused_disp + disp_smooth_fused')
-        g_loss = (g_loss if g_loss is not None else torch.zeros((), device=dev)).to(torch.float32).contiguous()
+        g_loss = _aligned((g_loss if g_loss is not None else torch.zeros((), device=dev)).to(torch.float32))
         g_disps = [torch.empty((b, 1, hs[s], ws[s]), device=dev, dtype=torch.float32) for s in range(S)]
         g_T, g_K, g_Ki, kflag = _pose_k_grads(ctx, n, b, dev)
         g_aa, g_t = (torch.empty_like(aa), torch.empty_like(t)) if aa is not None else (None, None)
