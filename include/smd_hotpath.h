@@ -460,6 +460,31 @@ int smd_layernorm_cf_bwd(const float* x, const void* g_y, int g_y_is_bf16, const
                          float* g_x, float* g_gamma, float* g_beta, void* workspace, size_t workspace_bytes, int N, int C, int HW, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The attention blocks of the CADepth decoder (src/networks/decoders/cadepth.py; csrc/smd_attention.hip).  fp32, deterministic.
+ *
+ * Structure perception (cadepth.py:14-27: `att = q @ k; att = att.max(-1, keepdim=True)[0] - att; out = x + (att.softmax(-1) @ v).view(...)`):
+ * x, out (B,C,h,w) with n = h*w, any C >= 1 and n >= 1.  out = x + softmax(-(V V^T)) V with V = x.view(B,C,n), evaluated as
+ * exp(rowmin - A) / sum on the f32 matrix cores.  stats (2,B,C) receives (rowmin, 1 / sum) per row: all the backward needs besides x.
+ * Backward: g (B,C,h,w) -> g_x.  Both calls take a workspace of the channel-attention workspace query (backward = 0: one, != 0: two
+ * (B,C,C) matrices; 0 for sizes that are not served): B and ceil(n / 64) below 65536, B*C*max(C, n) below 2^40. */
+size_t smd_channel_attention_workspace_bytes(int B, int C, int n, int backward);
+int smd_channel_attention_fwd(const float* x, float* out, float* stats, void* workspace, size_t workspace_bytes, int B, int C, int n, void* stream);
+int smd_channel_attention_bwd(const float* x, const float* stats, const float* g, float* g_x, void* workspace, size_t workspace_bytes,
+                              int B, int C, int n, void* stream);
+
+/* The squeeze-excite gate of detail emphasis (cadepth.py:35-41, 45: `x + x*self.att(x)` with att = AdaptiveAvgPool2d(1), Conv2d(ch, ch, 1), ReLU,
+ * Conv2d(ch, ch, 1), Sigmoid).  x, y (B,C,h,w) with HW = h*w; w1, w2 (C,C) row-major (the 1x1 convolutions' weights), b1, b2 (C).
+ *   y = x (1 + a),  a = sigmoid(w2 relu(w1 mean_hw(x) + b1) + b2)
+ * save (3,B,C) receives (a, mean, relu(w1 mean + b1)) for the backward.  Backward: g_y -> g_x (or NULL) and g_w1, g_b1, g_w2, g_b2 (all four or all
+ * NULL); every sum in a fixed order.  One workspace size serves both directions (0 for sizes that are not served: a plane of 2^31 elements or more,
+ * 2^31 blocks or more). */
+size_t smd_se_gate_workspace_bytes(int B, int C, int HW);
+int smd_se_gate_fwd(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* y, float* save,
+                    void* workspace, size_t workspace_bytes, int B, int C, int HW, void* stream);
+int smd_se_gate_bwd(const float* x, const float* g_y, const float* w1, const float* w2, const float* save, float* g_x, float* g_w1, float* g_b1,
+                    float* g_w2, float* g_b2, void* workspace, size_t workspace_bytes, int B, int C, int HW, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Pose / intrinsics prologue — one launch each instead of ~45 eager ATen launches.
  *
  * smd_pose_*: `T_from_AAt(aa, t)` (src/tools/geometry.py:181-209), followed by `T.inverse()` where invert[i] != 0

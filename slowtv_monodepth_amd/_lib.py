@@ -114,6 +114,12 @@ PROTOTYPES = {
     'smd_layernorm_cf_workspace_bytes': (_sz, [_i]*3),
     'smd_layernorm_cf_fwd': (_i, [_vp]*4 + [_i] + [_vp]*2 + [_i]*3 + [_f, _vp]),
     'smd_layernorm_cf_bwd': (_i, [_vp]*2 + [_i] + [_vp]*7 + [_sz] + [_i]*3 + [_vp]),
+    'smd_channel_attention_workspace_bytes': (_sz, [_i]*4),
+    'smd_channel_attention_fwd': (_i, [_vp]*4 + [_sz] + [_i]*3 + [_vp]),
+    'smd_channel_attention_bwd': (_i, [_vp]*5 + [_sz] + [_i]*3 + [_vp]),
+    'smd_se_gate_workspace_bytes': (_sz, [_i]*3),
+    'smd_se_gate_fwd': (_i, [_vp]*8 + [_sz] + [_i]*3 + [_vp]),
+    'smd_se_gate_bwd': (_i, [_vp]*11 + [_sz] + [_i]*3 + [_vp]),
     'smd_pose_fwd': (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     'smd_pose_bwd': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     'smd_intrinsics_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

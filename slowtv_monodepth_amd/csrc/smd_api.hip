@@ -1098,6 +1098,54 @@ int smd_maxpool3x3s2_bwd(const float* g_y, const uint8_t* idx, float* g_x, int N
 }
 
 // ------------------------------------------------------------------------------------------------
+// CADepth attention blocks (smd_attention.hip)
+static bool ca_sizes_ok(int B, int C, int n) {
+  return B >= 1 && B < 65536 && C >= 1 && n >= 1 && (n + 63)/64 < 65536 && (long long)B*C*std::max(C, n) < (1ll << 40);
+}
+size_t smd_channel_attention_workspace_bytes(int B, int C, int n, int backward) {
+  if (!ca_sizes_ok(B, C, n)) return 0;
+  return align256((size_t)B*C*C*sizeof(float)*(backward ? 2 : 1));
+}
+int smd_channel_attention_fwd(const float* x, float* out, float* stats, void* workspace, size_t workspace_bytes, int B, int C, int n, void* stream) {
+  if (!x || !out || !stats || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (!ca_sizes_ok(B, C, n)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d n=%d", B, C, n);
+  if (workspace_bytes < smd_channel_attention_workspace_bytes(B, C, n, 0)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return check_launch(smd::launch_channel_attention_fwd(x, out, stats, (float*)workspace, B, C, n, (hipStream_t)stream), "channel_attention_fwd");
+}
+int smd_channel_attention_bwd(const float* x, const float* stats, const float* g, float* g_x, void* workspace, size_t workspace_bytes,
+                              int B, int C, int n, void* stream) {
+  if (!x || !stats || !g || !g_x || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (!ca_sizes_ok(B, C, n)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d n=%d", B, C, n);
+  if (workspace_bytes < smd_channel_attention_workspace_bytes(B, C, n, 1)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return check_launch(smd::launch_channel_attention_bwd(x, stats, g, g_x, (float*)workspace, B, C, n, (hipStream_t)stream), "channel_attention_bwd");
+}
+
+static bool se_sizes_ok(int B, int C, int HW) {
+  return B >= 1 && C >= 1 && HW >= 1 && (long long)B*C*smd::se_chunks(HW) < (1ll << 31) && (long long)C*C < (1ll << 39);
+}
+size_t smd_se_gate_workspace_bytes(int B, int C, int HW) {
+  if (!se_sizes_ok(B, C, HW)) return 0;
+  return align256(((((size_t)B*C*smd::se_chunks(HW) + 3) & ~(size_t)3) + (size_t)3*B*C)*sizeof(float));
+}
+int smd_se_gate_fwd(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* y, float* save,
+                    void* workspace, size_t workspace_bytes, int B, int C, int HW, void* stream) {
+  if (!x || !w1 || !b1 || !w2 || !b2 || !y || !save || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (!se_sizes_ok(B, C, HW)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d HW=%d", B, C, HW);
+  if (workspace_bytes < smd_se_gate_workspace_bytes(B, C, HW)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return check_launch(smd::launch_se_gate_fwd(x, w1, b1, w2, b2, y, save, (float*)workspace, B, C, HW, (hipStream_t)stream), "se_gate_fwd");
+}
+int smd_se_gate_bwd(const float* x, const float* g_y, const float* w1, const float* w2, const float* save, float* g_x, float* g_w1, float* g_b1,
+                    float* g_w2, float* g_b2, void* workspace, size_t workspace_bytes, int B, int C, int HW, void* stream) {
+  if (!x || !g_y || !w1 || !w2 || !save || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  const int np = (g_w1 != nullptr) + (g_b1 != nullptr) + (g_w2 != nullptr) + (g_b2 != nullptr);
+  if (np != 0 && np != 4) return fail(SMD_E_INVALID, "the parameter gradients come all four or not at all");
+  if (!g_x && np == 0) return fail(SMD_E_INVALID, "nothing to compute");
+  if (!se_sizes_ok(B, C, HW)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d HW=%d", B, C, HW);
+  if (workspace_bytes < smd_se_gate_workspace_bytes(B, C, HW)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return check_launch(smd::launch_se_gate_bwd(x, g_y, w1, w2, save, g_x, g_w1, g_b1, g_w2, g_b2, (float*)workspace, B, C, HW, (hipStream_t)stream), "se_gate_bwd");
+}
+
+// ------------------------------------------------------------------------------------------------
 // Depthwise 7x7 convolution (ConvNeXt)
 static bool dw_sizes_ok(int N, int C, int H, int W) {
   return N >= 1 && C >= 1 && H >= 1 && W >= 1 && (long long)N*C*smd::dwconv_tiles(H, W) < (1ll << 31) && (long long)H*W < (1ll << 30);

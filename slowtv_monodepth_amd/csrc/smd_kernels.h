@@ -326,6 +326,13 @@ hipError_t launch_bn_fwd(const float* x, const float* residual, const float* gam
                          hipStream_t st);
 hipError_t launch_bn_bwd(const float* x, const float* y, const float* g_y, const float* gamma, const float* save_mean, const float* save_invstd,
                          int relu, float* g_x, float* g_res, float* g_gamma, float* g_beta, float* ws, int N, int C, int HW, hipStream_t st);
+hipError_t launch_channel_attention_fwd(const float* x, float* out, float* stats, float* ws, int B, int C, int n, hipStream_t st);
+hipError_t launch_channel_attention_bwd(const float* x, const float* stats, const float* g, float* g_x, float* ws, int B, int C, int n, hipStream_t st);
+int se_chunks(int HW);
+hipError_t launch_se_gate_fwd(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* y, float* save, float* ws,
+                              int B, int C, int HW, hipStream_t st);
+hipError_t launch_se_gate_bwd(const float* x, const float* g_y, const float* w1, const float* w2, const float* save, float* g_x, float* g_w1, float* g_b1,
+                              float* g_w2, float* g_b2, float* ws, int B, int C, int HW, hipStream_t st);
 hipError_t launch_maxpool_fwd(const float* x, float* y, uint8_t* idx, size_t planes, int H, int W, hipStream_t st);
 hipError_t launch_maxpool_bwd(const float* g_y, const uint8_t* idx, float* g_x, size_t planes, int H, int W, hipStream_t st);
 int dwconv_tiles(int H, int W);

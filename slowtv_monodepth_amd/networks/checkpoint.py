@@ -7,6 +7,10 @@ the `nets.<key>.` prefix (`src/core/trainer.py:58-60`), or the bare module's —
     reference / timm name                               here
     decoders.disp.decoder.{2(4-i)+j}.conv.{w,b}         decoders.disp.up{j}.{i}.0.{w,b}        (monodepth.py:50-66: ModuleList order)
     decoders.disp.decoder.{10+k}.{w,b}                  decoders.disp.out.{out_sc[k]}.{w,b}
+    with a `cadepth` decoder (cadepth.py:83-104: three modules per stage, then the heads):
+    decoders.disp.decoder.{3(4-i)+j}.conv.{w,b}, j<2    decoders.disp.up{j}.{i}.0.{w,b}
+    decoders.disp.decoder.{3(4-i)+2}.{conv,att}.*       decoders.disp.de.{i}.{conv,att}.*
+    decoders.disp.decoder.{15+k}.{w,b}                  decoders.disp.out.{out_sc[k]}.{w,b}
     encoder.layer{L}.{B}.downsample.{0,1}.*             encoder.layers.{L-1}.{B}.down.{0,1}.*  (timm ResNet, features_only)
     encoder.stem_0 / stem_1 (or stem.0 / stem.1)        encoder.stem.0 / stem.1                (timm ConvNeXt, features_only)
     encoder.stages_{S}.downsample.{0,1}.*               encoder.stages.{S}.{0,1}.*
@@ -27,7 +31,15 @@ import torch.nn as nn
 __all__ = ['from_reference_key', 'to_reference_key', 'load_reference_state_dict', 'to_reference_state_dict', 'reference_checkpoint', 'load_reference_checkpoint']
 
 
-def _decoder_from_ref(rest: str, out_sc):
+def _decoder_from_ref(rest: str, out_sc, kind: str = 'monodepth'):
+    if kind == 'cadepth':
+        m = re.fullmatch(r'decoder\.(\d+)\.(.*)', rest)
+        if not m: return None
+        idx, tail = int(m.group(1)), m.group(2)
+        if idx >= 15: return f'out.{out_sc[idx - 15]}.{tail}'
+        i, j = 4 - idx//3, idx % 3
+        if j == 2: return f'de.{i}.{tail}'
+        return f'up{j}.{i}.0.{tail[len("conv."):]}' if tail.startswith('conv.') else None
     m = re.fullmatch(r'decoder\.(\d+)\.(?:conv\.)?(weight|bias)', rest)
     if not m: return None
     idx, leaf = int(m.group(1)), m.group(2)
@@ -35,7 +47,15 @@ def _decoder_from_ref(rest: str, out_sc):
     return f'out.{out_sc[idx - 10]}.{leaf}'
 
 
-def _decoder_to_ref(rest: str, out_sc):
+def _decoder_to_ref(rest: str, out_sc, kind: str = 'monodepth'):
+    if kind == 'cadepth':
+        m = re.fullmatch(r'up([01])\.(\d)\.0\.(weight|bias)', rest)
+        if m: return f'decoder.{3*(4 - int(m.group(2))) + int(m.group(1))}.conv.{m.group(3)}'
+        m = re.fullmatch(r'de\.(\d)\.(.*)', rest)
+        if m: return f'decoder.{3*(4 - int(m.group(1))) + 2}.{m.group(2)}'
+        m = re.fullmatch(r'out\.(\d)\.(weight|bias)', rest)
+        if m: return f'decoder.{15 + list(out_sc).index(int(m.group(1)))}.{m.group(2)}'
+        return None
     m = re.fullmatch(r'up([01])\.(\d)\.0\.(weight|bias)', rest)
     if m: return f'decoder.{2*(4 - int(m.group(2))) + int(m.group(1))}.conv.{m.group(3)}'
     m = re.fullmatch(r'out\.(\d)\.(weight|bias)', rest)
@@ -83,20 +103,20 @@ def _split(key: str):
     return (m.group(1), m.group(2), m.group(3)) if m else (key, None, '')
 
 
-def from_reference_key(key: str, out_sc=(0, 1, 2, 3)) -> str:
+def from_reference_key(key: str, out_sc=(0, 1, 2, 3), dec_kind: str = 'monodepth') -> str:
     prefix, part, rest = _split(key)
     if part is None: return key
     if part.startswith('decoders.'):
-        new = _decoder_from_ref(rest, list(out_sc))
+        new = _decoder_from_ref(rest, list(out_sc), dec_kind)
         return prefix + part + (new if new is not None else rest)
     return prefix + part + _encoder_from_ref(rest)
 
 
-def to_reference_key(key: str, out_sc=(0, 1, 2, 3), convnext: bool = False) -> str:
+def to_reference_key(key: str, out_sc=(0, 1, 2, 3), convnext: bool = False, dec_kind: str = 'monodepth') -> str:
     prefix, part, rest = _split(key)
     if part is None: return key
     if part.startswith('decoders.'):
-        new = _decoder_to_ref(rest, list(out_sc))
+        new = _decoder_to_ref(rest, list(out_sc), dec_kind)
         return prefix + part + (new if new is not None else rest)
     return prefix + part + _encoder_to_ref(rest, convnext)
 
@@ -105,6 +125,11 @@ def _out_sc(module: nn.Module):
     for m in module.modules():
         if hasattr(m, 'out_sc') and hasattr(m, 'up0'): return list(m.out_sc)
     return [0, 1, 2, 3]
+
+
+def _dec_kind(module: nn.Module) -> str:
+    """Which decoder the module holds (a DepthNet builds its disparity and its mask decoder from one registry key)."""
+    return 'cadepth' if any(hasattr(m, 'de') and hasattr(m, 'up0') for m in module.modules()) else 'monodepth'
 
 
 def _is_convnext(module: nn.Module, key: str) -> bool:
@@ -118,13 +143,13 @@ def _is_convnext(module: nn.Module, key: str) -> bool:
 
 def load_reference_state_dict(module: nn.Module, state_dict: dict, strict: bool = True):
     """Load a reference `state_dict` (of the same kind of module: a network, the `nets` ModuleDict or the whole trainer)."""
-    out_sc = _out_sc(module)
-    return module.load_state_dict({from_reference_key(k, out_sc): v for k, v in state_dict.items()}, strict=strict)
+    out_sc, kind = _out_sc(module), _dec_kind(module)
+    return module.load_state_dict({from_reference_key(k, out_sc, kind): v for k, v in state_dict.items()}, strict=strict)
 
 
 def to_reference_state_dict(module: nn.Module) -> dict:
-    out_sc = _out_sc(module)
-    return {to_reference_key(k, out_sc, _is_convnext(module, k)): v for k, v in module.state_dict().items()}
+    out_sc, kind = _out_sc(module), _dec_kind(module)
+    return {to_reference_key(k, out_sc, _is_convnext(module, k), kind): v for k, v in module.state_dict().items()}
 
 
 def reference_checkpoint(trainer: nn.Module, epoch: int = 0, global_step: int = 0, optimizer=None, scheduler=None,

@@ -1,5 +1,8 @@
-"""Monodepth(2) decoder — registry key `monodepth` (reference: `src/networks/decoders/monodepth.py:14-89`)."""
+"""Monodepth(2) decoder — registry key `monodepth` (reference: `src/networks/decoders/monodepth.py:14-89`) — and the CADepth decoder built on it —
+registry key `cadepth` (reference: `src/networks/decoders/cadepth.py`)."""
 from __future__ import annotations
+
+import contextlib
 
 import torch
 import torch.nn as nn
@@ -7,7 +10,7 @@ import torch.nn.functional as F
 
 from ..registry import register
 
-__all__ = ['MonodepthDecoder', 'ACT']
+__all__ = ['MonodepthDecoder', 'CaDepthDecoder', 'DetailEmphasis', 'ACT']
 
 ACT = {'sigmoid': nn.Sigmoid(), 'relu': nn.ReLU(inplace=True), 'none': nn.Identity(), None: nn.Identity()}
 
@@ -64,13 +67,7 @@ class MonodepthDecoder(nn.Module):
         the two gather kernels of `csrc/smd_decoder.hip`, each writing the next convolution's padded input, and the
         padded ELU output of a stage is shared by its output head and the next stage (the reference pads it twice)."""
         from .. import functional as HF
-        def conv(m, xp):   # input already reflection-padded; the bias is added by the next glue kernel
-            co, ci = m.weight.shape[:2]
-            if (co % 32 == 0 and ci % 16 == 0) or (co == 16 and ci in (16, 32)):
-                # smd_conv3x3_mfma_* (bf16 matrix cores; fp32 tensors: three-way split operands, fp32-class results; bf16 tensors under autocast: one piece) or, per
-                # operator and shape by this box's A/B, MIOpen (the wide stages) / the f32-MFMA kernels smd_conv3x3_thin_* (the 16-channel last stage in fp32)
-                return HF.conv3x3_wide(xp, m.weight.float())
-            return F.conv2d(xp, m.weight)
+        conv = self._conv_glued
         out = {}
         xp = HF.elu_pad(feat[-1], apply_elu=False, out_dtype=out_dtype)   # under bf16 autocast the glue writes bf16 for the bf16 convolutions
         for i in range(4, -1, -1):
@@ -78,13 +75,123 @@ class MonodepthDecoder(nn.Module):
             skip = feat[self.enc_sc.index(2**i)] if (self.use_skip and 2**i in self.enc_sc) else None
             c = conv(m1, HF.elu_up_cat_pad(conv(m0, xp), skip, bias=m0.bias.float(), out_dtype=out_dtype))
             if i in self.out_sc or i > 0: xp = HF.elu_pad(c, bias=m1.bias.float(), apply_elu=True, out_dtype=out_dtype)
-            if i in self.out_sc:
-                m = self.out[str(i)]
-                if self.out_ch == 1 and isinstance(self.act, (nn.Sigmoid, nn.Identity)):   # a one-channel head is a stencil: smd_conv3x3_head_* (fp32 or bf16 activation in, fp32 out)
-                    out[i] = HF.conv3x3_head(xp, m.weight.float(), m.bias.float() if m.bias is not None else None, 'sigmoid' if isinstance(self.act, nn.Sigmoid) else None)
-                elif 1 <= self.out_ch <= 4 and isinstance(self.act, (nn.Sigmoid, nn.ReLU, nn.Identity)):   # a few channels (or one with relu) are still a stencil: smd_conv3x3_headn_* (the mask decoder)
-                    act = 'sigmoid' if isinstance(self.act, nn.Sigmoid) else ('relu' if isinstance(self.act, nn.ReLU) else None)
-                    out[i] = HF.conv3x3_headn(xp, m.weight.float(), m.bias.float() if m.bias is not None else None, act)
-                else:
-                    out[i] = self.act(F.conv2d(xp, m.weight, m.bias))
+            if i in self.out_sc: out[i] = self._head_glued(i, xp)
+        return out
+
+    @staticmethod
+    def _conv_glued(m, xp):
+        """The bias-free 3x3 convolution of an already reflection-padded input; the bias is added by whoever consumes the result."""
+        from .. import functional as HF
+        co, ci = m.weight.shape[:2]
+        if (co % 32 == 0 and ci % 16 == 0) or (co == 16 and ci in (16, 32)):
+            # smd_conv3x3_mfma_* (bf16 matrix cores; fp32 tensors: three-way split operands, fp32-class results; bf16 tensors under autocast: one piece) or, per
+            # operator and shape by this box's A/B, MIOpen (the wide stages) / the f32-MFMA kernels smd_conv3x3_thin_* (the 16-channel last stage in fp32)
+            return HF.conv3x3_wide(xp, m.weight.float())
+        return F.conv2d(xp, m.weight)
+
+    def _head_glued(self, i, xp):
+        """The output head of scale i on the padded activation `xp`."""
+        from .. import functional as HF
+        m = self.out[str(i)]
+        if self.out_ch == 1 and isinstance(self.act, (nn.Sigmoid, nn.Identity)):   # a one-channel head is a stencil: smd_conv3x3_head_* (fp32 or bf16 activation in, fp32 out)
+            return HF.conv3x3_head(xp, m.weight.float(), m.bias.float() if m.bias is not None else None, 'sigmoid' if isinstance(self.act, nn.Sigmoid) else None)
+        if 1 <= self.out_ch <= 4 and isinstance(self.act, (nn.Sigmoid, nn.ReLU, nn.Identity)):   # a few channels (or one with relu) are still a stencil: smd_conv3x3_headn_* (the mask decoder)
+            act = 'sigmoid' if isinstance(self.act, nn.Sigmoid) else ('relu' if isinstance(self.act, nn.ReLU) else None)
+            return HF.conv3x3_headn(xp, m.weight.float(), m.bias.float() if m.bias is not None else None, act)
+        return self.act(F.conv2d(xp, m.weight, m.bias))
+
+
+class DetailEmphasis(nn.Module):
+    """Detail emphasis of CADepth (src/networks/decoders/cadepth.py:30-46): conv3x3 + BatchNorm + ReLU, then the squeeze-excite gate `x + x*att(x)`.
+    Same sub-module names as the reference's, so its state-dict entries load as they are."""
+    def __init__(self, ch: int):
+        super().__init__()
+        self.conv = nn.Sequential(conv3x3(ch, ch), nn.BatchNorm2d(ch), nn.ReLU(inplace=True))
+        self.att = nn.Sequential(nn.AdaptiveAvgPool2d(1), nn.Conv2d(ch, ch, 1), nn.ReLU(inplace=True), nn.Conv2d(ch, ch, 1), nn.Sigmoid())
+
+    def forward(self, x):
+        x = self.conv(x)
+        return x + x*self.att(x)
+
+
+@register('cadepth')
+class CaDepthDecoder(MonodepthDecoder):
+    """CADepth (https://arxiv.org/abs/2112.13047; reference: src/networks/decoders/cadepth.py:49-126): the Monodepth decoder with structure perception
+    (channel self-attention) on the deepest encoder feature and detail emphasis (conv + BN + ReLU + squeeze-excite gate) on every stage's concatenation.
+    Same constructor arguments as `MonodepthDecoder`; `de[str(i)]` is the reference's `detail_emphasis_{i}` (`networks/checkpoint.py` translates the names).
+
+    Precision: on CUDA the glued path computes in fp32, also under bf16 autocast.  It then takes fp32 time and returns fp32 disparities while the encoder
+    around it runs in bf16; a bf16 form of this decoder does not exist (`forward` says what was measured).  Autocast to fp16 takes the plain ATen path."""
+
+    def __init__(self, num_ch_enc, enc_sc, upsample_mode: str = 'nearest', use_skip: bool = True,
+                 out_sc=(0, 1, 2, 3), out_ch: int = 1, out_act: str = 'sigmoid'):
+        super().__init__(num_ch_enc, enc_sc, upsample_mode, use_skip, out_sc, out_ch, out_act)
+        self.de = nn.ModuleDict({str(i): DetailEmphasis(self.up1[str(i)][0].in_channels) for i in range(4, -1, -1)})
+        self._glued = True
+
+    @contextlib.contextmanager
+    def plain_path(self):
+        """Within the block THIS decoder evaluates its plain ATen path wherever its tensors live (the yardstick the glued path is compared and timed against)."""
+        prev, self._glued = self._glued, False
+        try: yield self
+        finally: self._glued = prev
+
+    @staticmethod
+    def structure_perception(x):
+        b, c, h, w = x.shape
+        v = x.view(b, c, -1)
+        att = v @ v.permute(0, 2, 1)
+        att = att.max(dim=-1, keepdim=True)[0] - att
+        return x + (att.softmax(dim=-1) @ v).view(b, c, h, w)
+
+    def forward(self, feat):
+        x = feat[-1]
+        amp_bf16 = torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
+        if self._glued and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and (amp_bf16 or not torch.is_autocast_enabled()) and self.upsample_mode == 'nearest':
+            # Under bf16 autocast this decoder stays in fp32: with its convolutions in bf16 the feature gradients are 6e-2 ... 9e-2 of their sum of magnitudes off
+            # the fp32 run (ATen's own autocast of the plain path: 9e-2 ... 15e-2; DESIGN section 5), outside the 5e-2 the Monodepth decoder's bf16 path holds
+            with torch.autocast('cuda', enabled=False): return self._forward_glued([f.float() for f in feat])
+        out = {}
+        x = self.structure_perception(x)
+        for i in range(4, -1, -1):
+            x = F.interpolate(self.up0[str(i)](x), scale_factor=2, mode=self.upsample_mode)
+            if self.use_skip and 2**i in self.enc_sc: x = torch.cat((x, feat[self.enc_sc.index(2**i)]), 1)
+            x = self.up1[str(i)](self.de[str(i)](x))
+            if i in self.out_sc: out[i] = self.act(self.out[str(i)](x))
+        return out
+
+    # Static routing of the two attention operators by channel count, from profiles/cadepth_times.txt (b = 12 at 192 x 640, forward + backward, kernel vs ATen):
+    #   channel_attention (12,128,6,20) 0.08 vs 0.28 ms, (12,256,6,20) 0.16 vs 0.32 ms: the kernel pair wins; (12,512,6,20) 0.49 vs 0.30 ms, (12,1024,6,20) 1.43 vs
+    #     0.51 ms: rocBLAS's batched GEMMs win, and at any batch (the grid scales with B: (4,512,6,20) 0.29 vs 0.28 ms, forward alone 0.086 vs 0.062).  C >= 512 goes to ATen.
+    #   se_gate (12,512,12,40) 0.38 vs 0.28 ms, but (12,256,24,80) 0.14 vs 0.28 and 2.6-3.3x from there down: the per-sample block that does the two
+    #     C x C matrix-vector products is the cost at C = 512.  C >= 512 goes to ATen.
+    @staticmethod
+    def _attention_plain(x): return x.shape[1] >= 512
+
+    @staticmethod
+    def _gate_plain(x): return x.shape[1] >= 512
+
+    def _forward_glued(self, feat):
+        """Same network, same parameters, fp32.  `smd_channel_attention_*` on the deepest feature; per stage the Monodepth glue (`elu_up_cat_pad` writes the
+        padded concatenation the detail-emphasis convolution reads), `batch_norm_act` for BN + ReLU (eval mode: the ATen affine form on the running statistics),
+        `smd_se_gate_*` for the gate, `elu_pad` for the paddings, the stencil heads."""
+        from .. import functional as HF
+        conv = self._conv_glued
+        out = {}
+        x = feat[-1]
+        xp = HF.elu_pad(self.structure_perception(x) if self._attention_plain(x) else HF.channel_attention(x), apply_elu=False)
+        for i in range(4, -1, -1):
+            m0, m1, de = self.up0[str(i)][0], self.up1[str(i)][0], self.de[str(i)]
+            dc, bn = de.conv[0], de.conv[1]
+            skip = feat[self.enc_sc.index(2**i)] if (self.use_skip and 2**i in self.enc_sc) else None
+            d = conv(dc, HF.elu_up_cat_pad(conv(m0, xp), skip, bias=m0.bias)) + dc.bias.view(1, -1, 1, 1)
+            if bn.training and bn.track_running_stats and bn.momentum is not None and bn.affine:
+                d = HF.batch_norm_act(d, bn.weight, bn.bias, bn.running_mean, bn.running_var, momentum=bn.momentum, eps=bn.eps, relu=True)
+                with torch.no_grad(): bn.num_batches_tracked += 1
+            else:
+                d = F.relu(bn(d), inplace=True)
+            g = d + d*de.att(d) if self._gate_plain(d) else HF.se_gate(d, de.att[1].weight, de.att[1].bias, de.att[3].weight, de.att[3].bias)
+            c = conv(m1, HF.elu_pad(g, apply_elu=False))
+            if i in self.out_sc or i > 0: xp = HF.elu_pad(c, bias=m1.bias, apply_elu=True)
+            if i in self.out_sc: out[i] = self._head_glued(i, xp)
         return out
