@@ -485,6 +485,19 @@ int smd_se_gate_bwd(const float* x, const float* g_y, const float* w1, const flo
                     float* g_w2, float* g_b2, void* workspace, size_t workspace_bytes, int B, int C, int HW, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The DDVNet decoder's output head (additive to ABI 8): `conv3x3(C -> 128 G)` on an already reflection-padded xp (B, C, h + 2, w + 2), softmax over
+ * each group's 128 bins and the expectation over the bin values k/128 (src/networks/decoders/ddvnet.py:110, 116-124, 147-150), G = out_ch in 1..4,
+ * C a multiple of 16.  wp_fwd: the forward image smd_conv3x3_mfma_pack writes for (C, 128 G, pieces = 3); bias (128 G).  The logits are never written:
+ * disp (B, G, h, w), stats (B, G, 2, h, w) = per pixel the row maximum and the reciprocal of the sum of the shifted exponentials.
+ * smd_ddv_head_bwd_logits recomputes the logits and writes g_logits (B, 128 G, h, w) = p_k (k/128 - disp) g_disp — what the convolution's data and weight
+ * gradients (smd_conv3x3_mfma_bwd_* or any other) take as dL/dy — and, where g_bias is not NULL, the bias gradient (128 G), summed in a fixed order.
+ * smd_ddv_head_workspace_bytes: the backward's workspace; 0 for sizes the kernels do not take. */
+size_t smd_ddv_head_workspace_bytes(int B, int C, int G, int h, int w);
+int smd_ddv_head_fwd(const float* xp, const void* wp_fwd, const float* bias, float* disp, float* stats, int B, int C, int G, int h, int w, void* stream);
+int smd_ddv_head_bwd_logits(const float* xp, const void* wp_fwd, const float* bias, const float* disp, const float* stats, const float* g_disp,
+                            float* g_logits, float* g_bias, void* workspace, size_t workspace_bytes, int B, int C, int G, int h, int w, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Pose / intrinsics prologue — one launch each instead of ~45 eager ATen launches.
  *
  * smd_pose_*: `T_from_AAt(aa, t)` (src/tools/geometry.py:181-209), followed by `T.inverse()` where invert[i] != 0

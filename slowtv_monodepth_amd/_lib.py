@@ -120,6 +120,9 @@ PROTOTYPES = {
     'smd_se_gate_workspace_bytes': (_sz, [_i]*3),
     'smd_se_gate_fwd': (_i, [_vp]*8 + [_sz] + [_i]*3 + [_vp]),
     'smd_se_gate_bwd': (_i, [_vp]*11 + [_sz] + [_i]*3 + [_vp]),
+    'smd_ddv_head_workspace_bytes': (_sz, [_i]*5),
+    'smd_ddv_head_fwd': (_i, [_vp]*5 + [_i]*5 + [_vp]),
+    'smd_ddv_head_bwd_logits': (_i, [_vp]*9 + [_sz] + [_i]*5 + [_vp]),
     'smd_pose_fwd': (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     'smd_pose_bwd': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     'smd_intrinsics_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

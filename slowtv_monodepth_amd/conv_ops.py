@@ -129,37 +129,48 @@ class _Conv3x3Wide(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_y):
         xp, weight, wp_bwd = ctx.saved_tensors
-        _on(xp)
-        B, C, H, W = xp.shape
-        zpad, sv = ctx.zpad, ctx.served
-        CO, pieces, force = weight.shape[0], ctx.pieces, ctx.force
-        h, w = (H, W) if zpad else (H - 2, W - 2)
-        dims = (B, C, CO, h, w)
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        bf = xp.dtype == _BF
-        g_y = _check_fb('grad(y)', g_y.to(xp.dtype), (B, CO, h, w))
-        g_xp = g_w = None
-        w_ref = weight.to(_BF) if bf else weight
-        pad = [1, 1] if zpad else [0, 0]
-        cb = lambda mask: torch.ops.aten.convolution_backward(g_y, xp, w_ref, None, [1, 1], pad, [1, 1], False, [0, 0], 1, mask)
-        thin_ref = sv.thin and not bf                       # (the last stage in fp32: the reference is the f32-MFMA kernel)
-        sfx = '_z' if zpad else '_bf16' if bf else ''
-        nws = _mfma_ws_bytes(*dims, zpad) if sv.sized and ((need_x and sv.data) or (need_w and sv.wgt)) else 0
-        if need_x:
-            g_xp = torch.empty_like(xp)
-            packed = {'wb': wp_bwd}
+        return (*_wide_backward(xp, weight, wp_bwd, g_y, ctx.pieces, ctx.force, ctx.zpad, ctx.served, *ctx.needs_input_grad[:2]), None, None, None)
 
-            def run_data():
-                if packed['wb'] is None: packed['wb'] = _mfma_pack(weight, C, CO, pieces, False, True)[1]
-                return _mfma_launch('bwd_data', zpad, g_y, packed['wb'], g_xp, nws, dims, pieces)
-            ref_data = (lambda: _thin_bwd(xp, weight, g_y, True, False)[0]) if thin_ref else (lambda: cb([True, False, False])[0])
-            g_xp = serve(('data' + sfx, *dims), run_data, ref_data, eligible=sv.data and sv.sized, force=force)
-        if need_w:
-            g_w = torch.empty_like(weight)
-            run_wgt = lambda: _mfma_launch('bwd_weight', zpad, xp, g_y, g_w, nws, dims, pieces)
-            ref_wgt = (lambda: _thin_bwd(xp, weight, g_y, False, True)[1]) if thin_ref else (lambda: cb([False, True, False])[1].float())
-            g_w = serve(('wgt' + sfx, *dims), run_wgt, ref_wgt, eligible=sv.wgt and sv.sized, force=force)
-        return g_xp, g_w, None, None, None
+
+def _wide_backward(xp, weight, wp_bwd, g_y, pieces, force, zpad, sv, need_x, need_w, deterministic_ref=False):
+    """(g_xp, g_w) of `_Conv3x3Wide` for dL/dy = g_y, None where not needed: each operator on the MFMA kernels or its reference, as `serve` says.  Also the
+    tail of `ddv_ops.ddv_head`'s backward, whose dL/dy is the recomputed logit gradient.  `deterministic_ref`: where MIOpen serves an operator it is asked for
+    its deterministic solvers (left to itself it may pick one that accumulates with atomics: other bits on every run)."""
+    _on(xp)
+    B, C, H, W = xp.shape
+    CO = weight.shape[0]
+    h, w = (H, W) if zpad else (H - 2, W - 2)
+    dims = (B, C, CO, h, w)
+    bf = xp.dtype == _BF
+    g_y = _check_fb('grad(y)', g_y.to(xp.dtype), (B, CO, h, w))
+    g_xp = g_w = None
+    w_ref = weight.to(_BF) if bf else weight
+    pad = [1, 1] if zpad else [0, 0]
+    def cb(mask):
+        # deterministic_ref: ONLY `torch.backends.cudnn.deterministic` is set, and restored (`torch.backends.cudnn.flags(...)` would also switch `enabled` off
+        # and with it MIOpen itself: ATen's im2col fallback would serve the call)
+        det = torch.backends.cudnn.deterministic
+        if deterministic_ref: torch.backends.cudnn.deterministic = True
+        try: return torch.ops.aten.convolution_backward(g_y, xp, w_ref, None, [1, 1], pad, [1, 1], False, [0, 0], 1, mask)
+        finally: torch.backends.cudnn.deterministic = det
+    thin_ref = sv.thin and not bf                       # (the last stage in fp32: the reference is the f32-MFMA kernel)
+    sfx = '_z' if zpad else '_bf16' if bf else ''
+    nws = _mfma_ws_bytes(*dims, zpad) if sv.sized and ((need_x and sv.data) or (need_w and sv.wgt)) else 0
+    if need_x:
+        g_xp = torch.empty_like(xp)
+        packed = {'wb': wp_bwd}
+
+        def run_data():
+            if packed['wb'] is None: packed['wb'] = _mfma_pack(weight, C, CO, pieces, False, True)[1]
+            return _mfma_launch('bwd_data', zpad, g_y, packed['wb'], g_xp, nws, dims, pieces)
+        ref_data = (lambda: _thin_bwd(xp, weight, g_y, True, False)[0]) if thin_ref else (lambda: cb([True, False, False])[0])
+        g_xp = serve(('data' + sfx, *dims), run_data, ref_data, eligible=sv.data and sv.sized, force=force)
+    if need_w:
+        g_w = torch.empty_like(weight)
+        run_wgt = lambda: _mfma_launch('bwd_weight', zpad, xp, g_y, g_w, nws, dims, pieces)
+        ref_wgt = (lambda: _thin_bwd(xp, weight, g_y, False, True)[1]) if thin_ref else (lambda: cb([False, True, False])[1].float())
+        g_w = serve(('wgt' + sfx, *dims), run_wgt, ref_wgt, eligible=sv.wgt and sv.sized, force=force)
+    return g_xp, g_w
 
 
 def conv3x3_mfma(xp, weight, pieces: int = 3):

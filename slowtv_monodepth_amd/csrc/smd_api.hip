@@ -1146,6 +1146,26 @@ int smd_se_gate_bwd(const float* x, const float* g_y, const float* w1, const flo
 }
 
 // ------------------------------------------------------------------------------------------------
+// The DDVNet output head (smd_ddv.hip): conv3x3 to 128 bins per group + softmax + expectation, the logit volume never written
+size_t smd_ddv_head_workspace_bytes(int B, int C, int G, int h, int w) {
+  if (!smd::ddv_head_sizes_ok(B, C, G, h, w)) return 0;
+  return align256(smd::ddv_head_bias_partials(B, G)*sizeof(float));
+}
+int smd_ddv_head_fwd(const float* xp, const void* wp_fwd, const float* bias, float* disp, float* stats, int B, int C, int G, int h, int w, void* stream) {
+  if (!xp || !wp_fwd || !bias || !disp || !stats) return fail(SMD_E_INVALID, "null pointer");
+  if (!smd::ddv_head_sizes_ok(B, C, G, h, w)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d G=%d h=%d w=%d (C a multiple of 16, G in 1..4)", B, C, G, h, w);
+  return check_launch(smd::launch_ddv_head_fwd(xp, wp_fwd, bias, disp, stats, B, C, G, h, w, (hipStream_t)stream), "ddv_head_fwd");
+}
+int smd_ddv_head_bwd_logits(const float* xp, const void* wp_fwd, const float* bias, const float* disp, const float* stats, const float* g_disp,
+                            float* g_logits, float* g_bias, void* workspace, size_t workspace_bytes, int B, int C, int G, int h, int w, void* stream) {
+  if (!xp || !wp_fwd || !bias || !disp || !stats || !g_disp || !g_logits || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (!smd::ddv_head_sizes_ok(B, C, G, h, w)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d G=%d h=%d w=%d (C a multiple of 16, G in 1..4)", B, C, G, h, w);
+  if (workspace_bytes < smd_ddv_head_workspace_bytes(B, C, G, h, w)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return check_launch(smd::launch_ddv_head_bwd_logits(xp, wp_fwd, bias, disp, stats, g_disp, g_logits, g_bias, (float*)workspace, B, C, G, h, w, (hipStream_t)stream),
+                      "ddv_head_bwd_logits");
+}
+
+// ------------------------------------------------------------------------------------------------
 // Depthwise 7x7 convolution (ConvNeXt)
 static bool dw_sizes_ok(int N, int C, int H, int W) {
   return N >= 1 && C >= 1 && H >= 1 && W >= 1 && (long long)N*C*smd::dwconv_tiles(H, W) < (1ll << 31) && (long long)H*W < (1ll << 30);

@@ -333,6 +333,12 @@ hipError_t launch_se_gate_fwd(const float* x, const float* w1, const float* b1, 
                               int B, int C, int HW, hipStream_t st);
 hipError_t launch_se_gate_bwd(const float* x, const float* g_y, const float* w1, const float* w2, const float* save, float* g_x, float* g_w1, float* g_b1,
                               float* g_w2, float* g_b2, float* ws, int B, int C, int HW, hipStream_t st);
+// smd_ddv.hip: the DDVNet output head (conv3x3 to 128 bins per group + softmax + expectation) without the logit volume; wp = the forward image of launch_conv_mfma_pack
+bool ddv_head_sizes_ok(int B, int C, int G, int h, int w);
+size_t ddv_head_bias_partials(int B, int G);
+hipError_t launch_ddv_head_fwd(const float* xp, const void* wp, const float* bias, float* disp, float* stats, int B, int C, int G, int h, int w, hipStream_t st);
+hipError_t launch_ddv_head_bwd_logits(const float* xp, const void* wp, const float* bias, const float* disp, const float* stats, const float* g_disp,
+                                      float* g_logits, float* g_bias, float* partial, int B, int C, int G, int h, int w, hipStream_t st);
 hipError_t launch_maxpool_fwd(const float* x, float* y, uint8_t* idx, size_t planes, int H, int W, hipStream_t st);
 hipError_t launch_maxpool_bwd(const float* g_y, const uint8_t* idx, float* g_x, size_t planes, int H, int W, hipStream_t st);
 int dwconv_tiles(int H, int W);

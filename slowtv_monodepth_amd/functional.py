@@ -7,6 +7,7 @@ CPU tensors are rejected.  The operators live in one module per family, and ever
 intrinsics), `conv_ops` / `conv_routing` (the routed MFMA convolutions), `metric_ops` (the validation depth metrics), `attention_ops` (the CADepth decoder's attention blocks); `_device` holds what they share."""
 from ._device import _stream, call
 from .attention_ops import channel_attention, se_gate
+from .ddv_ops import ddv_head
 from .class_ops import _ScaleMean, crop_resize, lane_shift_selftest, photo_error, recon_reduce, regression_loss, scale_mean, upsample_stack, view_synth
 from .conv_ops import conv3x3_mfma, conv3x3_same, conv3x3_thin, conv3x3_wide, conv7x7s2_stem
 from .conv_routing import _conv_route, conv_routes, set_conv_route

@@ -11,6 +11,10 @@ the `nets.<key>.` prefix (`src/core/trainer.py:58-60`), or the bare module's —
     decoders.disp.decoder.{3(4-i)+j}.conv.{w,b}, j<2    decoders.disp.up{j}.{i}.0.{w,b}
     decoders.disp.decoder.{3(4-i)+2}.{conv,att}.*       decoders.disp.de.{i}.{conv,att}.*
     decoders.disp.decoder.{15+k}.{w,b}                  decoders.disp.out.{out_sc[k]}.{w,b}
+    with a `ddvnet` decoder (ddvnet.py:93-112: the attention block, the ten stage modules, then the heads; `bins` keeps its name):
+    decoders.disp.decoder.0.{query,key,value}_conv.*    decoders.disp.att.{query,key,value}_conv.*
+    decoders.disp.decoder.{1+2(4-i)+j}.conv.{w,b}       decoders.disp.up{j}.{i}.0.{w,b}
+    decoders.disp.decoder.{11+k}.{w,b}                  decoders.disp.out.{out_sc[k]}.{w,b}
     encoder.layer{L}.{B}.downsample.{0,1}.*             encoder.layers.{L-1}.{B}.down.{0,1}.*  (timm ResNet, features_only)
     encoder.stem_0 / stem_1 (or stem.0 / stem.1)        encoder.stem.0 / stem.1                (timm ConvNeXt, features_only)
     encoder.stages_{S}.downsample.{0,1}.*               encoder.stages.{S}.{0,1}.*
@@ -40,9 +44,13 @@ def _decoder_from_ref(rest: str, out_sc, kind: str = 'monodepth'):
         i, j = 4 - idx//3, idx % 3
         if j == 2: return f'de.{i}.{tail}'
         return f'up{j}.{i}.0.{tail[len("conv."):]}' if tail.startswith('conv.') else None
+    if kind == 'ddvnet':
+        m = re.fullmatch(r'decoder\.0\.(.*)', rest)
+        if m: return f'att.{m.group(1)}'
     m = re.fullmatch(r'decoder\.(\d+)\.(?:conv\.)?(weight|bias)', rest)
     if not m: return None
     idx, leaf = int(m.group(1)), m.group(2)
+    if kind == 'ddvnet': idx -= 1                          # (the attention block is the ModuleList's first entry)
     if idx < 10: return f'up{idx % 2}.{4 - idx//2}.0.{leaf}'
     return f'out.{out_sc[idx - 10]}.{leaf}'
 
@@ -56,10 +64,14 @@ def _decoder_to_ref(rest: str, out_sc, kind: str = 'monodepth'):
         m = re.fullmatch(r'out\.(\d)\.(weight|bias)', rest)
         if m: return f'decoder.{15 + list(out_sc).index(int(m.group(1)))}.{m.group(2)}'
         return None
+    first = 1 if kind == 'ddvnet' else 0
+    if first:
+        m = re.fullmatch(r'att\.(.*)', rest)
+        if m: return f'decoder.0.{m.group(1)}'
     m = re.fullmatch(r'up([01])\.(\d)\.0\.(weight|bias)', rest)
-    if m: return f'decoder.{2*(4 - int(m.group(2))) + int(m.group(1))}.conv.{m.group(3)}'
+    if m: return f'decoder.{first + 2*(4 - int(m.group(2))) + int(m.group(1))}.conv.{m.group(3)}'
     m = re.fullmatch(r'out\.(\d)\.(weight|bias)', rest)
-    if m: return f'decoder.{10 + list(out_sc).index(int(m.group(1)))}.{m.group(2)}'
+    if m: return f'decoder.{first + 10 + list(out_sc).index(int(m.group(1)))}.{m.group(2)}'
     return None
 
 
@@ -129,7 +141,8 @@ def _out_sc(module: nn.Module):
 
 def _dec_kind(module: nn.Module) -> str:
     """Which decoder the module holds (a DepthNet builds its disparity and its mask decoder from one registry key)."""
-    return 'cadepth' if any(hasattr(m, 'de') and hasattr(m, 'up0') for m in module.modules()) else 'monodepth'
+    if any(hasattr(m, 'de') and hasattr(m, 'up0') for m in module.modules()): return 'cadepth'
+    return 'ddvnet' if any(hasattr(m, 'bins') and hasattr(m, 'up0') for m in module.modules()) else 'monodepth'
 
 
 def _is_convnext(module: nn.Module, key: str) -> bool:

@@ -1,5 +1,6 @@
 """Monodepth(2) decoder — registry key `monodepth` (reference: `src/networks/decoders/monodepth.py:14-89`) — and the CADepth decoder built on it —
-registry key `cadepth` (reference: `src/networks/decoders/cadepth.py`)."""
+registry key `cadepth` (reference: `src/networks/decoders/cadepth.py`) — and the DDVNet decoder — registry key `ddvnet` (reference:
+`src/networks/decoders/ddvnet.py`)."""
 from __future__ import annotations
 
 import contextlib
@@ -10,7 +11,7 @@ import torch.nn.functional as F
 
 from ..registry import register
 
-__all__ = ['MonodepthDecoder', 'CaDepthDecoder', 'DetailEmphasis', 'ACT']
+__all__ = ['MonodepthDecoder', 'CaDepthDecoder', 'DetailEmphasis', 'DDVNetDecoder', 'SelfAttentionBlock', 'ACT']
 
 ACT = {'sigmoid': nn.Sigmoid(), 'relu': nn.ReLU(inplace=True), 'none': nn.Identity(), None: nn.Identity()}
 
@@ -195,3 +196,97 @@ class CaDepthDecoder(MonodepthDecoder):
             if i in self.out_sc or i > 0: xp = HF.elu_pad(c, bias=m1.bias, apply_elu=True)
             if i in self.out_sc: out[i] = self._head_glued(i, xp)
         return out
+
+
+class SelfAttentionBlock(nn.Module):
+    """The self-attention block of DDVNet (src/networks/decoders/ddvnet.py:37-54): three 1x1 convolutions + ReLU, then `softmax(q k^T) v` over CHANNELS
+    (the C x C matrix), no residual.  Same sub-module names as the reference's."""
+    def __init__(self, ch: int):
+        super().__init__()
+        self.query_conv = nn.Sequential(nn.Conv2d(ch, ch, 1), nn.ReLU(inplace=True))
+        self.key_conv = nn.Sequential(nn.Conv2d(ch, ch, 1), nn.ReLU(inplace=True))
+        self.value_conv = nn.Sequential(nn.Conv2d(ch, ch, 1), nn.ReLU(inplace=True))
+
+    def forward(self, x):
+        b, c, h, w = x.shape
+        q, k, v = self.query_conv(x).flatten(-2, -1), self.key_conv(x).flatten(-2, -1).permute(0, 2, 1), self.value_conv(x).flatten(-2, -1)
+        return ((q @ k).softmax(dim=-1) @ v).view(b, c, h, w)
+
+
+@register('ddvnet')
+class DDVNetDecoder(MonodepthDecoder):
+    """DDVNet (https://arxiv.org/abs/2003.13951; reference: src/networks/decoders/ddvnet.py:57-152): the Monodepth decoder behind a self-attention block on the
+    deepest encoder feature, with heads that emit 128 logits per output channel — a discrete disparity volume — and return its expectation over the bin
+    values `bins[k] = k/128`.  Same constructor arguments as `MonodepthDecoder`; `out_act` is validated but, as in the reference, not applied.  `att` is the
+    reference's `convs['att']` (`networks/checkpoint.py` translates the names).
+
+    On CUDA (fp32, nearest up-sampling) the stages run on the Monodepth glue and every head is `functional.ddv_head`: convolution, softmax and expectation
+    in one kernel that never writes the logit volume.  That path leaves `self.logits` EMPTY (nothing in the reference reads it); the plain ATen path (CPU,
+    other up-sampling modes, `plain_path()`) fills `self.logits[i]` as the reference does.  The attention block stays on ATen: every supported encoder
+    gives it 512 channels or more, where rocBLAS's batched GEMMs win (profiles/cadepth_times.txt).
+
+    Precision: on CUDA the glued path computes in fp32, also under bf16 autocast (the rule `CaDepthDecoder` follows): it then takes fp32 time and returns
+    fp32 disparities while the encoder around it runs in bf16.  Autocast to fp16 takes the plain ATen path."""
+    num_bins = 128
+
+    def __init__(self, num_ch_enc, enc_sc, upsample_mode: str = 'nearest', use_skip: bool = True,
+                 out_sc=(0, 1, 2, 3), out_ch: int = 1, out_act: str = 'sigmoid'):
+        super().__init__(num_ch_enc, enc_sc, upsample_mode, use_skip, out_sc, out_ch, out_act)
+        self.bins = nn.Parameter((torch.arange(self.num_bins)/self.num_bins).view(1, self.num_bins, 1, 1), requires_grad=False)
+        self.att = SelfAttentionBlock(self.num_ch_enc[-1])
+        for i in self.out_sc: self.out[str(i)] = conv3x3(self.num_ch_dec[i], self.num_bins*out_ch)
+        self.logits = {}
+        self._glued = True
+
+    @contextlib.contextmanager
+    def plain_path(self):
+        """Within the block THIS decoder evaluates its plain ATen path wherever its tensors live (the yardstick the glued path is compared and timed against)."""
+        prev, self._glued = self._glued, False
+        try: yield self
+        finally: self._glued = prev
+
+    def expected_disparity(self, logits):
+        """(b, 128, h, w) logits -> (b, 1, h, w): the expectation of the bin values under softmax(logits) (ddvnet.py:116-124)."""
+        return (logits.softmax(dim=1)*self.bins).sum(dim=1, keepdim=True)
+
+    def forward(self, feat):
+        x = feat[-1]
+        amp_bf16 = torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
+        if self._glued and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and (amp_bf16 or not torch.is_autocast_enabled()) and self.upsample_mode == 'nearest' \
+                and 1 <= self.out_ch <= 4:
+            with torch.autocast('cuda', enabled=False): return self._forward_glued([f.float() for f in feat])
+        out = {}
+        x = self.att(x)
+        for i in range(4, -1, -1):
+            x = F.interpolate(self.up0[str(i)](x), scale_factor=2, mode=self.upsample_mode)
+            if self.use_skip and 2**i in self.enc_sc: x = torch.cat((x, feat[self.enc_sc.index(2**i)]), 1)
+            x = self.up1[str(i)](x)
+            if i in self.out_sc: out[i] = self._head_plain(i, x)
+        return out
+
+    def _head_plain(self, i, x):
+        """The head of scale i on the (unpadded) stage output, the reference's sequence; fills `self.logits[i]`."""
+        logits = self.out[str(i)](x)
+        self.logits[i] = logits
+        return torch.cat([self.expected_disparity(l) for l in logits.chunk(self.out_ch, dim=1)], dim=1)
+
+    def _forward_glued(self, feat):
+        """Same network, same parameters, fp32: the attention block on ATen, the Monodepth stage glue (`elu_pad`, `elu_up_cat_pad`, the routed convolutions),
+        `ddv_head` on the padded stage output it shares with the next stage."""
+        from .. import functional as HF
+        conv = self._conv_glued
+        out = {}
+        self.logits = {}
+        xp = HF.elu_pad(self.att(feat[-1]), apply_elu=False)
+        for i in range(4, -1, -1):
+            m0, m1 = self.up0[str(i)][0], self.up1[str(i)][0]
+            skip = feat[self.enc_sc.index(2**i)] if (self.use_skip and 2**i in self.enc_sc) else None
+            c = conv(m1, HF.elu_up_cat_pad(conv(m0, xp), skip, bias=m0.bias))
+            if i in self.out_sc or i > 0: xp = HF.elu_pad(c, bias=m1.bias, apply_elu=True)
+            if i in self.out_sc: out[i] = self._head_glued(i, xp)
+        return out
+
+    def _head_glued(self, i, xp):
+        from .. import functional as HF
+        m = self.out[str(i)]
+        return HF.ddv_head(xp, m.weight, m.bias, self.out_ch)

@@ -24,6 +24,7 @@ class DepthNet(nn.Module):
         super().__init__()
         if dec_name not in DEC_REG: raise KeyError(f'Invalid decoder. ({dec_name} vs. {list(DEC_REG)}')
         if mask_name not in {None, 'explainability', 'uncertainty'}: raise KeyError(f'Invalid mask. ({mask_name})')
+        if dec_name == 'ddvnet' and mask_name: raise KeyError('DDVNet is not compatible with mask prediction.')   # (src/networks/depth.py:81-82)
         if use_virtual_stereo: raise NotImplementedError('use_virtual_stereo (a three-channel disparity head and `disp_stereo`) is not served by this package')
         if use_stereo_blend: raise NotImplementedError('use_stereo_blend (a second, flipped forward pass blended into the first) is not served by this package')
         if mask_name and (num_ch_mask is None or int(num_ch_mask) <= 0):
