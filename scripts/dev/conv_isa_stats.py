@@ -2,23 +2,36 @@
 """Instruction mix of the decoder convolutions' inner loops, from the ISA hipcc generates (no GPU needed): MFMAs against LDS reads / writes, vector-memory
 instructions and other vector instructions per K chunk (forward forms) / per row (weight gradients).  VERDICT r5 item 2 asked for the MFMA : LDS-read ratio.
 usage: python scripts/dev/conv_isa_stats.py >> profiles/rNN_instruction_counts.txt"""
-import re, subprocess, tempfile
+import re, shutil, subprocess, tempfile
 from pathlib import Path
 ROOT = Path(__file__).resolve().parents[2]
 CSRC = ROOT/'slowtv_monodepth_amd'/'csrc'
 
-def isa(src):
-    out = Path(tempfile.mkdtemp())/'k.s'
-    subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fno-slp-vectorize', f'-I{ROOT}/include', '-S', '--cuda-device-only',
-                    str(CSRC/src), '-o', str(out)], check=True, stderr=subprocess.DEVNULL)
-    return out.read_text().split('\n')
+FLAGS = ['-O3', '-std=c++17', '-fPIC', '-fno-slp-vectorize', '--offload-arch=gfx950']      # csrc/Makefile's CXXFLAGS
 
-def kernel(lines, key):
-    start = [i for i, l in enumerate(lines) if l.startswith(key) and l.rstrip().endswith(':') is False and ':' in l][0]
-    end = [i for i, l in enumerate(lines) if i > start and 's_endpgm' in l][0]
-    body = lines[start:end]
-    meta = {k: next((re.search(r'(\d+)', l.split(k)[1]).group(1) for l in lines[end:end + 400] if k in l), '?') for k in ('.vgpr_count', '.agpr_count', 'NumVgprs', 'NumAgprs', 'ScratchSize', 'LDSByteSize')}
-    return body, meta
+def isa(src):
+    """-> {demangled kernel name without its argument list: (body lines, resource lines of the kernel's own 'Kernel info' block)}"""
+    out = Path(tempfile.mkdtemp())/'k.s'
+    subprocess.run(['/opt/rocm/bin/hipcc', *FLAGS, '-S', '--cuda-device-only', src, '-o', str(out)], check=True, stderr=subprocess.DEVNULL, cwd=CSRC)
+    lines = out.read_text().split('\n')
+    syms = [l.split()[1] for l in lines if l.strip().startswith('.amdhsa_kernel ')]
+    filt = shutil.which('llvm-cxxfilt') or shutil.which('llvm-cxxfilt', path='/opt/rocm/lib/llvm/bin') or shutil.which('c++filt')
+    if filt is None: raise SystemExit('conv_isa_stats.py needs a demangler: llvm-cxxfilt (ROCm) or c++filt (binutils) on the PATH')
+    names = subprocess.run([filt], input='\n'.join(syms), capture_output=True, text=True, check=True).stdout.split('\n')
+    kernels = {}
+    for sym, name in zip(syms, names):
+        start = next(i for i, l in enumerate(lines) if l.startswith(sym + ':'))
+        end = next(i for i in range(start, len(lines)) if lines[i].startswith('.Lfunc_end'))
+        info = next(i for i in range(end, len(lines)) if lines[i].startswith('; Kernel info'))
+        res = {m.group(1): m.group(2) for l in lines[info:info + 30] if (m := re.match(r'; (NumVgprs|NumAgprs|TotalNumSgprs|ScratchSize|Occupancy|LDSByteSize): (\d+)', l))}
+        name = name.replace('(anonymous namespace)::', '').replace('smd::', '').replace('__hip_bfloat16', 'bf16')    # 'void k<args>(parameters)'
+        kernels[name[len('void '):name.index('(')]] = (lines[start:end], res)
+    return kernels
+
+def kernel(kernels, key):
+    """key: the kernel's name with its template arguments as the demangler prints them, e.g. 'k_conv_mfma<64, 3, 0, float, float, 1>'."""
+    if key not in kernels: raise SystemExit(f'no kernel {key!r}; this source has: ' + ', '.join(sorted(kernels)))
+    return kernels[key]
 
 def count(body):
     c = {'mfma': 0, 'ds_read': 0, 'ds_write': 0, 'vmem_load': 0, 'vmem_store': 0, 'valu': 0, 'salu': 0, 'barrier': 0, 'waitcnt': 0}
@@ -51,17 +64,21 @@ def report(lines, key, what, unit):
     print(f'{what}')
     print(f'  main loop ({unit}): {loop["mfma"]} MFMA, {loop["ds_read"]} LDS reads, {loop["ds_write"]} LDS writes, {loop["vmem_load"]} vector-memory loads, {loop["valu"]} other vector, '
           f'{loop["salu"]} scalar, {loop["barrier"]} barriers, {loop["waitcnt"]} waits  ->  MFMA : LDS read = {loop["mfma"]/max(loop["ds_read"], 1):.2f}, other vector per MFMA = {loop["valu"]/max(loop["mfma"], 1):.2f}')
-    print(f'  whole kernel: {whole["mfma"]} MFMA, {whole["vmem_load"]} loads, {whole["vmem_store"]} stores; registers: see the resource table of the build (make EXTRA=-Rpass-analysis=kernel-resource-usage)\n')
+    print(f'  whole kernel: {whole["mfma"]} MFMA, {whole["vmem_load"]} loads, {whole["vmem_store"]} stores; {meta.get("NumVgprs")} VGPRs, {meta.get("NumAgprs")} AGPRs, {meta.get("TotalNumSgprs")} SGPRs, '
+          f'{meta.get("ScratchSize")} bytes of scratch, {meta.get("LDSByteSize")} bytes of LDS, occupancy {meta.get("Occupancy")}\n')
 
-print('\nDecoder convolutions (round 6), produced by scripts/dev/conv_isa_stats.py\n')
+print('\nDecoder convolutions, produced by scripts/dev/conv_isa_stats.py\n')
 L = isa('smd_conv_mfma.hip')
-report(L, '_ZN3smd11k_conv_mfmaILi64ELi3ELb0EffLi1EE', 'k_conv_mfma<64, 3, false, float, float>  (wide forward, fp32 tensors, three pieces: 4 rows x 64 columns x 32 output channels per block; a chunk = 16 channels x 9 taps)', 'one K chunk of one wave: 9 taps x 2 pixel tiles x 6 products = 108 MFMA')
-report(L, '_ZN3smd11k_conv_mfmaILi64ELi3ELb1EffLi1EE', 'k_conv_mfma<64, 3, true, float, float>   (wide data gradient)', 'one K chunk')
-report(L, '_ZN3smd11k_conv_mfmaILi64ELi1ELb0E14__hip_bfloat16S1_Li1EE', 'k_conv_mfma<64, 1, false, bf16, bf16>    (wide forward, bf16 tensors, one piece)', 'one K chunk: 18 MFMA')
-report(L, '_ZN3smd13k_conv16_mfmaILi1ELi3ELb0EffEE', 'k_conv16_mfma<1, 3, false, float, float> (thin forward 16 -> 16: 16x16x32 MFMA, two taps per K step, weights in registers; no loop — one chunk)', 'the whole tile: 5 K steps x 4 rows x 6 products = 120 MFMA')
-report(L, '_ZN3smd16k_conv_wgrad_dmaILi3EEE', 'k_conv_wgrad_dma<3>                      (wide weight gradient, fp32 tensors: 32 output x 64 input channels per block, loop over INPUT rows, ring of four RAW rows by LDS-DMA, split at fragment read; the loop body is three rows)', 'three input rows of one wave (its K step of 16 columns, one tile of 32 input channels): 3 x 54 MFMA')
-report(L, '_ZN3smd18k_conv16_wgrad_dmaILi1ELi3EEE', 'k_conv16_wgrad_dma<1, 3>                 (thin weight gradient 16 -> 16, fp32 tensors: the same on 16x16x32, strips of 64 columns)', 'three input rows of one wave')
-report(L, '_ZN3smd18k_conv16_wgrad_dmaILi2ELi3EEE', 'k_conv16_wgrad_dma<2, 3>                 (thin weight gradient 32 -> 16)', 'three input rows of one wave')
-report(L, '_ZN3smd17k_conv_wgrad_mfmaILi1E14__hip_bfloat16EE', 'k_conv_wgrad_mfma<1, bf16>               (wide weight gradient, bf16 tensors: rows staged through registers, split + filed after the row\'s MFMAs)', 'one input row of one wave: 9 MFMA')
+report(L, 'k_conv_mfma<64, 3, 0, float, float, 1>', 'k_conv_mfma<64, 3, 0, float, float, 1>   (wide forward, fp32 tensors, three pieces: 4 rows x 64 columns x 32 output channels per block; a chunk = 16 channels x 9 taps)', 'one K chunk of one wave: 9 taps x 2 pixel tiles x 6 products = 108 MFMA')
+report(L, 'k_conv_mfma<64, 3, 2, float, float, 1>', 'k_conv_mfma<64, 3, 2, float, float, 1>   (wide data gradient)', 'one K chunk')
+report(L, 'k_conv_mfma<64, 3, 1, float, float, 1>', 'k_conv_mfma<64, 3, 1, float, float, 1>   (zero-padded "same" layer, forward and data gradient)', 'one K chunk')
+report(L, 'k_conv_mfma<64, 1, 0, bf16, bf16, 1>', 'k_conv_mfma<64, 1, 0, bf16, bf16, 1>     (wide forward, bf16 tensors, one piece)', 'one K chunk: 18 MFMA')
+report(L, 'k_conv16_mfma<1, 3, false, float, float>', 'k_conv16_mfma<1, 3, false, float, float> (thin forward 16 -> 16: 16x16x32 MFMA, two taps per K step, weights in registers; no loop — one chunk)', 'the whole tile: 5 K steps x 4 rows x 6 products = 120 MFMA')
+G = isa('smd_conv_wgrad.hip')
+report(G, 'k_wgrad_dma<WgradWide, 3, false>', 'k_wgrad_dma<WgradWide, 3, false>         (wide weight gradient, fp32 tensors: 32 output x 64 input channels per block, loop over INPUT rows, ring of four RAW rows by LDS-DMA, split at fragment read; the loop body is three rows)', 'three input rows of one wave (its K step of 16 columns, one tile of 32 input channels): 3 x 54 MFMA')
+report(G, 'k_wgrad_dma<WgradWide, 3, true>', 'k_wgrad_dma<WgradWide, 3, true>          (the same on the unpadded input of a zero-padded layer)', 'three input rows of one wave')
+report(G, 'k_wgrad_dma<WgradThin<1>, 3, false>', 'k_wgrad_dma<WgradThin<1>, 3, false>      (thin weight gradient 16 -> 16, fp32 tensors: the same on 16x16x32, strips of 64 columns)', 'three input rows of one wave')
+report(G, 'k_wgrad_dma<WgradThin<2>, 3, false>', 'k_wgrad_dma<WgradThin<2>, 3, false>      (thin weight gradient 32 -> 16)', 'three input rows of one wave')
+report(G, 'k_wgrad_staged<WgradWide, 1, bf16>', 'k_wgrad_staged<WgradWide, 1, bf16>       (wide weight gradient, bf16 tensors: rows staged through registers, split + filed after the row\'s MFMAs)', 'one input row of one wave: 9 MFMA')
 T = isa('smd_conv_thin.hip')
-report(T, '_ZN3smd11k_thin_mfmaILi16ELi1ELb0EEE', 'k_thin_mfma<16, 1, false>                (round 5, f32 MFMA 16x16x4: the comparison)', 'the whole tile')
+report(T, 'k_thin_mfma<16, 1, false>', 'k_thin_mfma<16, 1, false>                (round 5, f32 MFMA 16x16x4: the comparison)', 'the whole tile')

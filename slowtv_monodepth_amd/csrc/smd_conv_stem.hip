@@ -1,5 +1,5 @@
 // smd_conv_stem.hip — the ResNet stem, conv2d(x (B,C,H,W), w (64,C,7,7), stride 2, padding 3), on the bf16 matrix cores with fp32-class results: every fp32
-// operand split exactly into three bf16 pieces, six `v_mfma_f32_32x32x16_bf16` per K step of 16 (the scheme of smd_conv_mfma.hip; helpers in smd_split_dev.h).
+// operand split exactly into three bf16 pieces, six `v_mfma_f32_32x32x16_bf16` per K step of 16 (the scheme of smd_conv_mfma.hip; helpers in smd_split_dev.h and smd_conv_mfma_dev.h).
 // C = 3 (the depth network's stem) and C = 6 (the pose network's); zero padding inside the kernels, NCHW fp32 in and out, any H, W >= 1.  No data gradient:
 // the input is the image.
 //
@@ -16,10 +16,10 @@
 // the plane kx selects, from an element offset that depends on kx: five dwords and a funnel shift.  A block walks a band of output rows of a strip of 64
 // columns of one sample: per output row one row of dL/dy (64 channels x 64 pixels, split at filing) and TWO new input rows per channel into a ring of eight
 // (output row y meets input rows 2 y - 3 .. 2 y + 3); loads for the next row are requested before the row's MFMAs and filed after.  Wave = one tile of 32
-// output channels x every second tile of 32 weight columns.  Blocks leave partial sets in the weight's own order; two fixed-order fp64 stages add them.
+// output channels x every second tile of 32 weight columns.  Blocks leave partial sets in the weight's own order; launch_partial_sets_finalize (smd_conv_wgrad.hip) adds them in fp64 in a fixed order.
 #include "smd_common.h"
 #include "smd_kernels.h"
-#include "smd_split_dev.h"
+#include "smd_conv_mfma_dev.h"
 #include <algorithm>
 
 namespace smd {
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void k_stem_pack_w(const float* __restrict__ w
 template <int C>
 __global__ __launch_bounds__(256, 2) void k_stem_fwd(const float* __restrict__ x, const uint4* __restrict__ wp, float* __restrict__ y, int H, int W, int ho, int wo) {
   using T = StemFwd<C>;
-  constexpr int NS = T::NS, NI = T::NI, PR = T::PR, PD = T::PD, PITCH = T::PITCH, PLANE = T::PLANE, ITEMS = T::ITEMS, NPROD = n_products(3);
+  constexpr int NS = T::NS, NI = T::NI, PR = T::PR, PD = T::PD, PITCH = T::PITCH, PLANE = T::PLANE, ITEMS = T::ITEMS;
   __shared__ __attribute__((aligned(16))) unsigned xs[3*PLANE];
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), j = lane & 31, g = lane >> 5;
   const int x0 = blockIdx.x*64, y0 = blockIdx.y*4, b = blockIdx.z;
@@ -100,6 +100,7 @@ __global__ __launch_bounds__(256, 2) void k_stem_fwd(const float* __restrict__ x
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
     for (int p = 0; p < 3; ++p) an[mt][p] = wl[((mt*NS + 0)*3 + p)*64];
+#pragma unroll                                                    // (all 11 / 21 K steps: every patch address is then an immediate)
   for (int s = 0; s < NS; ++s) {
     bf16x8 A[2][3];
 #pragma unroll
@@ -122,15 +123,7 @@ __global__ __launch_bounds__(256, 2) void k_stem_fwd(const float* __restrict__ x
         const unsigned* q = row + p*PLANE + nf*32;
         Bf[nf][p] = as_frag(uint4{q[0], q[1], q[2], q[3]});
       }
-#pragma unroll
-    for (int t = 0; t < NPROD; ++t)
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nf = 0; nf < 2; ++nf) {
-          if (t == NPROD - 1) acc[mt][nf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[mt][0], Bf[nf][0], acc[mt][nf], 0, 0, 0);
-          else lo[mt][nf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[mt][prod_a(3, t)], Bf[nf][prod_b(3, t)], lo[mt][nf], 0, 0, 0);
-        }
+    split_mfma<3>(A, Bf, acc, lo);
   }
 
   const int yy = y0 + wv;
@@ -143,7 +136,7 @@ __global__ __launch_bounds__(256, 2) void k_stem_fwd(const float* __restrict__ x
       if (xx < wo) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int co = mt*32 + (r & 3) + 8*(r >> 2) + 4*g;
+          const int co = mt*32 + mfma32_row(r, g);
           y[(((size_t)b*64 + co)*ho + yy)*wo + xx] = acc[mt][nf][r] + lo[mt][nf][r];
         }
       }
@@ -272,7 +265,7 @@ __global__ __launch_bounds__(256, 2) void k_stem_wgrad(const float* __restrict__
                                 __builtin_amdgcn_alignbit(d3, d2, s16), __builtin_amdgcn_alignbit(d4, d3, s16)});
         }
 #pragma unroll
-        for (int t = 0; t < NPROD; ++t) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[prod_a(3, t)], Bf[prod_b(3, t)], acc[i], 0, 0, 0);
+        for (int t = 0; t < NPROD; ++t) acc[i] = mfma_bf16(A[prod_a(3, t)], Bf[prod_b(3, t)], acc[i]);
       }
     }
     __syncthreads();
@@ -287,34 +280,11 @@ __global__ __launch_bounds__(256, 2) void k_stem_wgrad(const float* __restrict__
     if (nt < NT && n < NW) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int co = mt*32 + (r & 3) + 8*(r >> 2) + 4*g;
+        const int co = mt*32 + mfma32_row(r, g);
         partial[(blk*64 + co)*NW + n] = acc[i][r];
       }
     }
   }
-}
-
-// partial[t][i] (a set = the weight tensor's own order) -> g_w[i], fp64, fixed order: (1) a block = 64 weights x one of G slices of the T sets, its four
-// waves every fourth set of the slice, added in wave order; (2) the G slices in order.  G = 1: the first launch writes g_w itself.
-__global__ __launch_bounds__(256) void k_stem_wgrad_fin1(const float* __restrict__ partial, unsigned T, unsigned G, int n, double* __restrict__ slice, float* __restrict__ g_w) {
-  __shared__ double part[4][64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, i = blockIdx.x*64 + lane;
-  const unsigned g = blockIdx.y, t0 = (unsigned)(((unsigned long long)T*g)/G), t1 = (unsigned)(((unsigned long long)T*(g + 1))/G);
-  double s = 0.0;
-  if (i < n) for (unsigned t = t0 + wv; t < t1; t += 4) s += (double)partial[(size_t)t*n + i];
-  part[wv][lane] = s;
-  __syncthreads();
-  if (wv == 0 && i < n) {
-    const double tot = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
-    if (G == 1) g_w[i] = (float)tot; else slice[(size_t)g*n + i] = tot;
-  }
-}
-__global__ __launch_bounds__(256) void k_stem_wgrad_fin2(const double* __restrict__ slice, unsigned G, int n, float* __restrict__ g_w) {
-  const int i = blockIdx.x*256 + threadIdx.x;
-  if (i >= n) return;
-  double tot = 0.0;
-  for (unsigned g = 0; g < G; ++g) tot += slice[(size_t)g*n + i];
-  g_w[i] = (float)tot;
 }
 
 // strips of 64 columns x bands of rows x samples: about one generation of blocks at two per CU, at least eight rows a block
@@ -325,7 +295,6 @@ void stem_wgrad_shape(int B, int ho, int wo, dim3& grid, int& rows) {
   rows = ceil_div(ho, groups);
   grid = dim3(strips, ceil_div(ho, rows), B);
 }
-unsigned stem_slices(unsigned T) { return T < 64 ? 1u : std::min(32u, T/16); }
 
 }  // namespace
 
@@ -334,9 +303,7 @@ size_t conv_stem_packed_bytes(int C) { return (size_t)2*((7*C + 1)/2)*3*1024; }
 size_t conv_stem_wgrad_floats(int B, int C, int H, int W) {
   dim3 grid; int rows;
   stem_wgrad_shape(B, (H - 1)/2 + 1, (W - 1)/2 + 1, grid, rows);
-  const size_t T = (size_t)grid.x*grid.y*grid.z, n = (size_t)64*49*C;
-  const unsigned G = stem_slices((unsigned)T);
-  return T*n + (G > 1 ? 2*(size_t)G*n : 0);                               // (T n is even: the fp64 slices behind the sets are 8-byte aligned)
+  return partial_sets_floats(grid.x*grid.y*grid.z, (size_t)64*49*C);
 }
 hipError_t launch_conv_stem_pack(const float* w, void* wp, int C, hipStream_t st) {
   const int n = 2*((7*C + 1)/2)*64;
@@ -357,11 +324,7 @@ hipError_t launch_conv_stem_bwd_wgt(const float* x, const float* gy, float* g_w,
   stem_wgrad_shape(B, ho, wo, grid, rows);
   if (C == 3) hipLaunchKernelGGL(k_stem_wgrad<3>, grid, dim3(256), 0, st, x, gy, partial, H, W, ho, wo, rows);
   else hipLaunchKernelGGL(k_stem_wgrad<6>, grid, dim3(256), 0, st, x, gy, partial, H, W, ho, wo, rows);
-  const unsigned T = grid.x*grid.y*grid.z, G = stem_slices(T);
-  double* slice = reinterpret_cast<double*>(partial + (size_t)T*n);
-  hipLaunchKernelGGL(k_stem_wgrad_fin1, dim3(ceil_div(n, 64), G), dim3(256), 0, st, partial, T, G, n, slice, g_w);
-  if (G > 1) hipLaunchKernelGGL(k_stem_wgrad_fin2, dim3(ceil_div(n, 256)), dim3(256), 0, st, slice, G, n, g_w);
-  return hipGetLastError();
+  return launch_partial_sets_finalize(partial, grid.x*grid.y*grid.z, n, SetIndexMap{}, g_w, st);   // the sets are in the weight's own order
 }
 
 }  // namespace smd

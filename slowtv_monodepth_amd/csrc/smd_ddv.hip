@@ -2,9 +2,9 @@
 //     logits = conv3x3(x)  (128 bins per output channel);  disp = sum_k softmax(logits)_k k/128.
 // ATen writes the logit volume (b = 12 at 192 x 640: 755 MB for a 24 MB input and a 6 MB output), re-reads and rewrites it in the softmax and reads it
 // again in the multiply and the sum.  Here the volume never leaves the registers: the convolution is the split-bf16 matrix-core scheme of
-// smd_conv_mfma.hip (same packed weights — `k_conv_pack_w`'s forward image —, same LDS patch with the same bank swizzle, six
+// smd_conv_mfma.hip through the stages of smd_conv_mfma_dev.h (same packed weights — `k_conv_pack_w`'s forward image —, same LDS patch with the same bank swizzle, six
 // `v_mfma_f32_32x32x16_bf16` per K step with the leading product and the five small ones in accumulators of their own) and the epilogue reduces over
-// the bins.  D of that MFMA is [row = output channel][column = pixel] with a lane holding 16 rows of one column (row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)):
+// the bins.  D of that MFMA is [row = output channel][column = pixel] with a lane holding 16 rows of one column (row = mfma32_row):
 // a wave multiplies its pixels by ALL 128 bins of one group (four channel tiles), so a lane ends with 64 of a pixel's 128 logits in registers and lane ^ 32
 // with the other 64 — maximum, sum and weighted sum are in-register loops plus one exchange between the wave's halves.  No atomics anywhere.
 // A block of four waves owns 4 rows x 64 columns of one sample and one group: a wave = one row = two pixel fragments x four channel tiles = 8 + 8
@@ -15,7 +15,7 @@
 // in a fixed order (k_ddv_bias_*), bit-reproducible from run to run.
 #include "smd_common.h"
 #include "smd_kernels.h"
-#include "smd_split_dev.h"
+#include "smd_conv_mfma_dev.h"
 
 namespace smd {
 
@@ -31,11 +31,11 @@ __global__ __launch_bounds__(256, 1) void k_ddv_head(const float* __restrict__ x
                                                      float* __restrict__ disp, float* __restrict__ stats, const float* __restrict__ g_disp,
                                                      float* __restrict__ g_logits, int C, int G, int h, int w, unsigned gx, unsigned gy, unsigned nblk) {
   using T = DdvTile;
-  constexpr int P = 3, NPROD = n_products(P), NPIX = T::NPIX, PW = T::PW, NMT = kDdvBins/32;
+  constexpr int P = 3, NPIX = T::NPIX, PW = T::PW, NMT = kDdvBins/32;
   __shared__ uint4 tile[P*NPIX*2];                                // one patch, [piece][pixel][half] (38 KB)
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), j = lane & 31, g = lane >> 5;
-  // XCD-aware block order, as in k_conv_mfma: the blocks in flight on an XCD are neighbours in the image (and the groups of one tile)
-  const unsigned per = (nblk + 7)/8, lid = (blockIdx.x & 7)*per + (blockIdx.x >> 3);
+  // XCD-aware block order: the blocks in flight on an XCD are neighbours in the image (and the groups of one tile)
+  const unsigned lid = xcd_block_id(nblk);
   if (lid >= nblk) return;
   const int gi = (int)(lid % (unsigned)G);
   const unsigned tl = lid/(unsigned)G;
@@ -44,42 +44,13 @@ __global__ __launch_bounds__(256, 1) void k_ddv_head(const float* __restrict__ x
   const size_t plane = (size_t)hi*wi;
   const float* src = xp + (size_t)b*C*plane;
 
-  // staging: an item = 8 channels of one patch pixel (beyond the image: any valid address, those outputs are not stored)
-  constexpr int ITEMS = 2*NPIX, TRIPS = (ITEMS + 255)/256;
-  int pofs[TRIPS];
-#pragma unroll
-  for (int t = 0; t < TRIPS; ++t) {
-    const int item = min(t*256 + (int)threadIdx.x, ITEMS - 1);
-    const int half = item >= NPIX ? 1 : 0, pix = item - half*NPIX;
-    const int r = pix/PW, cc = pix - r*PW;
-    pofs[t] = min(y0 + r, hi - 1)*wi + min(x0 + cc, wi - 1);
-  }
-  float v[TRIPS][8];
-  auto request = [&](int kc) {
-#pragma unroll
-    for (int t = 0; t < TRIPS; ++t) {
-      const int item = min(t*256 + (int)threadIdx.x, ITEMS - 1);
-      const int half = item >= NPIX ? 1 : 0;
-      const float* p = src + (size_t)(kc*16 + half*8)*plane + (size_t)pofs[t];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[t][e] = p[(size_t)e*plane];
-    }
-  };
-  auto file = [&]() {
-#pragma unroll
-    for (int t = 0; t < TRIPS; ++t) {
-      const int item = t*256 + (int)threadIdx.x;
-      if (item < ITEMS) {
-        const int half = item >= NPIX ? 1 : 0, pix = item - half*NPIX;
-        unsigned pk[4][P];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) split_pair<P>(v[t][2*q], v[t][2*q + 1], pk[q]);
-        const int slot = pix*2 + (half ^ ((pix >> 3) & 1));
-#pragma unroll
-        for (int p = 0; p < P; ++p) tile[p*NPIX*2 + slot] = uint4{pk[0][p], pk[1][p], pk[2][p], pk[3][p]};
-      }
-    }
-  };
+  // staging: as in k_conv_mfma (beyond the image: any valid address, those outputs are not stored)
+  using Stage = PatchStager<256, NPIX, P, float, false>;
+  Stage stage;
+  stage.template rect_offsets<PW>(y0, x0, 0, hi, wi);
+  float v[Stage::TRIPS][8];
+  auto request = [&](int kc) { stage.request(src, plane, kc, v); };
+  auto file = [&]() { stage.file(tile, 0, v); };
 
   f32x16 acc[NMT][2], lo[NMT][2];
 #pragma unroll
@@ -102,10 +73,7 @@ __global__ __launch_bounds__(256, 1) void k_ddv_head(const float* __restrict__ x
     const int ky = tap/3, kx = tap % 3;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-      const int pix = (wv + ky)*PW + nt*32 + j + kx;
-      const int slot = pix*2 + (g ^ ((pix >> 3) & 1));
-#pragma unroll
-      for (int p = 0; p < P; ++p) dst[nt][p] = as_frag(tile[p*NPIX*2 + slot]);
+      Stage::read(tile, 0, (wv + ky)*PW + nt*32 + j + kx, g, dst[nt]);
     }
   };
 
@@ -122,16 +90,7 @@ __global__ __launch_bounds__(256, 1) void k_ddv_head(const float* __restrict__ x
       read_b(Bf, tap);
       if (tap < 8) fetch_a(A[(tap + 1) & 1], kc, tap + 1);
       else if (more) fetch_a(A[2], kc + 1, 0);
-      bf16x8 (&At)[NMT][P] = A[tap == 0 ? 2 : (tap & 1)];
-#pragma unroll
-      for (int t = 0; t < NPROD; ++t)
-#pragma unroll
-        for (int mt = 0; mt < NMT; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < 2; ++nt) {
-            if (t == NPROD - 1) acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(At[mt][0], Bf[nt][0], acc[mt][nt], 0, 0, 0);
-            else lo[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(At[mt][prod_a(P, t)], Bf[nt][prod_b(P, t)], lo[mt][nt], 0, 0, 0);
-          }
+      split_mfma<P>(A[tap == 0 ? 2 : (tap & 1)], Bf, acc, lo);
     }
     if (more) {
       __syncthreads();                                            // nobody reads this patch any more
@@ -153,7 +112,7 @@ __global__ __launch_bounds__(256, 1) void k_ddv_head(const float* __restrict__ x
 #pragma unroll
     for (int mt = 0; mt < NMT; ++mt)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mt][nt][r] = (acc[mt][nt][r] + lo[mt][nt][r]) + bz[32*mt + (r & 3) + 8*(r >> 2) + 4*g];
+      for (int r = 0; r < 16; ++r) acc[mt][nt][r] = (acc[mt][nt][r] + lo[mt][nt][r]) + bz[32*mt + mfma32_row(r, g)];
     if constexpr (!BWD) {
       float m = acc[0][nt][0];
 #pragma unroll
@@ -168,7 +127,7 @@ __global__ __launch_bounds__(256, 1) void k_ddv_head(const float* __restrict__ x
         for (int r = 0; r < 16; ++r) {
           const float e = expf(acc[mt][nt][r] - m);
           s += e;
-          ts = fmaf(e, (float)(32*mt + (r & 3) + 8*(r >> 2) + 4*g)*(1.f/kDdvBins), ts);
+          ts = fmaf(e, (float)(32*mt + mfma32_row(r, g))*(1.f/kDdvBins), ts);
         }
       s += __shfl_xor(s, 32);                                     // (a + b and b + a are the same float: both halves hold the same sums)
       ts += __shfl_xor(ts, 32);
@@ -185,7 +144,7 @@ __global__ __launch_bounds__(256, 1) void k_ddv_head(const float* __restrict__ x
         for (int mt = 0; mt < NMT; ++mt)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int k = 32*mt + (r & 3) + 8*(r >> 2) + 4*g;
+            const int k = 32*mt + mfma32_row(r, g);
             const float p = expf(acc[mt][nt][r] - m)*rinv;
             dst[(size_t)k*hw] = p*((float)k*(1.f/kDdvBins) - d)*gd;  // a register is 32 consecutive pixels of one bin per half wave (128-byte runs)
           }

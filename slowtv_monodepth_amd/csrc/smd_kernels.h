@@ -287,7 +287,7 @@ hipError_t launch_conv_thin_fwd(const float* xp, const float* wgt, float* y, int
 size_t conv_thin_partials(int B, int C, int h, int w);
 hipError_t launch_conv_thin_bwd_wgt(const float* xp, const float* gy, float* g_w, float* partial, int B, int C, int h, int w, hipStream_t st);
 hipError_t launch_conv_thin_bwd_data(const float* gy, const float* wgt, float* g_xp, int B, int C, int h, int w, hipStream_t st);
-// smd_conv_mfma.hip: 3x3 convolutions on the bf16 matrix cores, fp32 operands split into `pieces` bf16 pieces (3: fp32-class results).  zpad = false: the
+// smd_conv_mfma.hip (pack, forward, data gradient) and smd_conv_wgrad.hip (weight gradient): 3x3 convolutions on the bf16 matrix cores, fp32 operands split into `pieces` bf16 pieces (3: fp32-class results).  zpad = false: the
 // decoder's layers on a reflection-padded xp (B, C, h + 2, w + 2), fp32 or (pieces 1) bfloat16; zpad = true: the encoders' zero-padded "same" layers on the
 // unpadded x / g_x, fp32 only.  two_tiles: the knob conv_two_tiles, read once per entry point (smd_api.hip) for its size query and its launch alike.
 enum class ConvOp { Fwd, Data, Wgt };
@@ -299,12 +299,17 @@ inline bool conv_mfma_served(ConvOp op, bool zpad, int C, int CO) {
   return CO % 32 == 0 || thin;
 }
 size_t conv_mfma_packed_elems(int C, int CO, int pieces);
-size_t conv_mfma_wgrad_partials(bool zpad, int B, int C, int CO, int h, int w);
+size_t conv_mfma_wgrad_partials(bool zpad, int B, int C, int CO, int h, int w);                           // smd_conv_wgrad.hip
 size_t conv_mfma_split_elems(ConvOp op, bool zpad, int B, int C, int CO, int h, int w, bool two_tiles);   // floats of K-split partial outputs (0: none, or not served)
 hipError_t launch_conv_mfma_pack(const float* w, void* wp_fwd, void* wp_bwd, int C, int CO, int pieces, hipStream_t st);
 hipError_t launch_conv_mfma_fwd(const void* x, const void* wp_fwd, void* y, float* split_ws, bool zpad, int B, int C, int CO, int h, int w, int pieces, bool two_tiles, hipStream_t st);
 hipError_t launch_conv_mfma_bwd_data(const void* gy, const void* wp_bwd, void* g_x, float* split_ws, bool zpad, int B, int C, int CO, int h, int w, int pieces, bool two_tiles, hipStream_t st);
-hipError_t launch_conv_mfma_bwd_wgt(const void* x, const void* gy, float* g_w, float* partial, bool zpad, int B, int C, int CO, int h, int w, int pieces, hipStream_t st);
+hipError_t launch_conv_mfma_bwd_wgt(const void* x, const void* gy, float* g_w, float* partial, bool zpad, int B, int C, int CO, int h, int w, int pieces, hipStream_t st);   // smd_conv_wgrad.hip
+// smd_conv_wgrad.hip: g_w = the sum of `partial`'s T sets of n sums each (what the blocks of a weight gradient leave), fp64 in a fixed order.  The workspace is
+// partial_sets_floats(T, n) floats (T n even).  SetIndexMap{}: g_w is in the sets' order; {CO, C}: the sets are [tap][co][c] and g_w is [co][c][tap].
+struct SetIndexMap { int CO = 0, C = 0; };
+size_t partial_sets_floats(unsigned T, size_t n);
+hipError_t launch_partial_sets_finalize(float* partial, unsigned T, int n, SetIndexMap index_map, float* g_w, hipStream_t st);
 // smd_conv_stem.hip: the ResNet stem (7x7, stride 2, padding 3, 64 output channels; C = 3 | 6) on the split-bf16 matrix-core form, fp32 NCHW tensors
 bool conv_stem_served(int C, int CO);
 size_t conv_stem_packed_bytes(int C);

@@ -1,5 +1,6 @@
 // smd_split_dev.h — the exact three-way bf16 split of fp32 operands and the products kept of it, shared by the split-bf16 matrix-core kernels
-// (smd_conv_mfma.hip, where the scheme is described, and smd_conv_stem.hip).
+// (smd_conv_mfma.hip, where the scheme is described, smd_conv_wgrad.hip, smd_conv_stem.hip and smd_ddv.hip).  The stages those kernels share — block order,
+// the LDS patch and its stager, the product sequence, the weight gradients' pieces — are smd_conv_mfma_dev.h; this header stays the arithmetic.
 #pragma once
 #include "smd_common.h"
 

@@ -1,8 +1,8 @@
 """Operands on which the split-bf16 convolutions have no rounding at all, so that their results must equal fp64 `conv2d` bit for bit (test_conv_exact.py
 checks the generator on the CPU, test_gpu_conv_exact.py the kernels).
 
-The kernels (csrc/smd_conv_mfma.hip, smd_conv_stem.hip) split every fp32 operand into three bf16 pieces, a = a0 + a1 + a2, and keep the six products
-a_i b_j with i + j <= 2.  A PIECE-BUILT value is  s (n0 + n1 2^-10 + n2 2^-20) 2^e  with s = +-1 and n0, n1, n2 in {1, 2, 3}: its round-to-nearest-even split
+The kernels (csrc/smd_conv_mfma.hip, smd_conv_wgrad.hip, smd_conv_stem.hip; their shared stages: csrc/smd_conv_mfma_dev.h) split every fp32 operand into
+three bf16 pieces, a = a0 + a1 + a2, and keep the six products a_i b_j with i + j <= 2.  A PIECE-BUILT value is  s (n0 + n1 2^-10 + n2 2^-20) 2^e  with s = +-1 and n0, n1, n2 in {1, 2, 3}: its round-to-nearest-even split
 returns exactly s n0 2^e, s n1 2^(e-10), s n2 2^(e-20) (all pieces share the sign: 1 - 3 2^-10 re-splits differently, the bf16 ulp halves below 1, and
 `from_pieces` refuses it).  Three operand FAMILIES make the products the scheme drops (a1 b2, a2 b1, a2 b2) exactly zero while every kept product is
 exercised by one of them; `lead` = n0 only, `two` = n0 + n1 2^-10, `full` = all three:
@@ -25,7 +25,7 @@ PADDED = [(2, 16, 32, 5, 7), (1, 32, 32, 33, 65), (2, 48, 64, 9, 70), (3, 160, 6
 SAME = [(2, 64, 64, 1, 1), (3, 64, 64, 5, 7), (5, 32, 64, 1, 49), (2, 64, 64, 3, 1), (2, 64, 32, 9, 3), (2, 128, 64, 10, 47), (1, 64, 64, 11, 49),
         (1, 64, 64, 13, 100), (1, 512, 64, 4, 20), (5, 512, 512, 3, 5)]
 STEM = [(2, 3, 1, 1), (2, 3, 5, 7), (2, 6, 13, 101), (3, 6, 37, 64), (1, 3, 37, 64)]
-BF16 = [(2, 16, 16, 7, 70), (2, 64, 64, 9, 70), (2, 96, 32, 13, 100)]
+BF16 = [(2, 16, 16, 7, 70), (2, 64, 64, 9, 70), (2, 96, 32, 13, 100), (2, 32, 16, 9, 33)]
 # `conv_two_tiles`: 256 tiles of 64 x 4 pixels in the forward (126 x 62) AND in the data gradient (the padded 128 x 64), neither on row bands (conv_shape)
 TWO_TILES = (8, 64, 64, 126, 62)
 
