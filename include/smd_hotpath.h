@@ -498,6 +498,34 @@ int smd_ddv_head_bwd_logits(const float* xp, const void* wp_fwd, const float* bi
                             float* g_logits, float* g_bias, void* workspace, size_t workspace_bytes, int B, int C, int G, int h, int w, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The DiffNet decoder's attention stage in front of its convolution (additive to ABI 8; reference: src/networks/decoders/diffnet.py:44-47 —
+ * ChannelAttention.forward: `x * sigmoid(fc(avg_pool(x)))` with two bias-free Linear layers — and :70-74 — AttentionBlock.forward: `cat(interpolate(x, 2),
+ * x_skip)` in front of it; the reflection padding is that of the block's conv3x3, decoders/utils.py:44-46; the ReLU on `a` is the previous block's,
+ * diffnet.py:67).  All tensors fp32.
+ *   src  = cat(nearest_x2(act(a + bias_a)), skip)      a (B,Ca,h,w) a raw (bias-free) convolution output or an encoder feature, bias_a (Ca) or NULL,
+ *                                                      act SMD_UCG_NONE / SMD_UCG_RELU, skip (B,Cs,2h,2w) with Cs >= 1; src is never written
+ *   mean = mean_hw(src)                                (for the a half: the mean over h x w of act(a + bias_a))
+ *   hid  = relu(w1 mean),  gate = sigmoid(w2 hid)      w1 (R,C), w2 (C,R) row-major, C = Ca + Cs, any R >= 1
+ *   out (B,C,2h+2,2w+2) = reflect_pad1(gate o src)
+ * gate (B,C), mean (B,C) and hid (B,R) are written for the backward, which recomputes act(a + bias_a): g_out -> g_a, g_skip, g_bias_a (Ca), g_w1 with g_w2
+ * (both or neither); any of them may be NULL.  Every sum runs in a fixed order (no atomics): two runs on the same inputs are bit-equal.  One workspace
+ * size serves both directions; it is 0 for sizes that are not served (a non-positive size, 2^31 blocks or more, a padded plane of 2^30 elements or more). */
+#define SMD_UCG_NONE 0
+#define SMD_UCG_RELU 1
+size_t smd_up_cat_gate_pad_workspace_bytes(int B, int Ca, int Cs, int h, int w, int R);
+int smd_up_cat_gate_pad_fwd(const float* a, const float* bias_a, const float* skip, const float* w1, const float* w2, float* out, float* gate, float* mean,
+                            float* hid, void* workspace, size_t workspace_bytes, int B, int Ca, int Cs, int h, int w, int R, int act, void* stream);
+int smd_up_cat_gate_pad_bwd(const float* a, const float* bias_a, const float* skip, const float* w1, const float* w2, const float* gate, const float* mean,
+                            const float* hid, const float* g_out, float* g_a, float* g_skip, float* g_bias_a, float* g_w1, float* g_w2,
+                            void* workspace, size_t workspace_bytes, int B, int Ca, int Cs, int h, int w, int R, int act, void* stream);
+/* The ReLU form of smd_elu_pad_* (the same kernels with another activation): out (B,C,h+2,w+2) = reflect_pad1(relu(x + bias)), the padded activation of a
+ * DiffNet attention stage (diffnet.py:64-68: conv3x3 + ReLU) that its output head and a following up-sample block read.  fp32; bias (C) or NULL.
+ * Backward: g_out -> g_x and g_bias (C) or NULL (needs smd_decoder_glue_workspace_bytes(B, C, h, w)). */
+int smd_relu_pad_fwd(const float* x, const float* bias, float* out, int B, int C, int h, int w, void* stream);
+int smd_relu_pad_bwd(const float* x, const float* bias, const float* g_out, float* g_x, float* g_bias, void* workspace, size_t workspace_bytes,
+                     int B, int C, int h, int w, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Pose / intrinsics prologue — one launch each instead of ~45 eager ATen launches.
  *
  * smd_pose_*: `T_from_AAt(aa, t)` (src/tools/geometry.py:181-209), followed by `T.inverse()` where invert[i] != 0

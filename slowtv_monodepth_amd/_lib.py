@@ -123,6 +123,11 @@ PROTOTYPES = {
     'smd_ddv_head_workspace_bytes': (_sz, [_i]*5),
     'smd_ddv_head_fwd': (_i, [_vp]*5 + [_i]*5 + [_vp]),
     'smd_ddv_head_bwd_logits': (_i, [_vp]*9 + [_sz] + [_i]*5 + [_vp]),
+    'smd_up_cat_gate_pad_workspace_bytes': (_sz, [_i]*6),
+    'smd_up_cat_gate_pad_fwd': (_i, [_vp]*10 + [_sz] + [_i]*7 + [_vp]),
+    'smd_up_cat_gate_pad_bwd': (_i, [_vp]*15 + [_sz] + [_i]*7 + [_vp]),
+    'smd_relu_pad_fwd': (_i, [_vp]*3 + [_i]*4 + [_vp]),
+    'smd_relu_pad_bwd': (_i, [_vp]*6 + [_sz] + [_i]*4 + [_vp]),
     'smd_pose_fwd': (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     'smd_pose_bwd': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     'smd_intrinsics_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

@@ -1166,6 +1166,46 @@ int smd_ddv_head_bwd_logits(const float* xp, const void* wp_fwd, const float* bi
 }
 
 // ------------------------------------------------------------------------------------------------
+// The DiffNet attention stage in front of its convolution (smd_decoder.hip): up-sample + cat + channel gate + pad, and the ReLU form of the pad glue
+size_t smd_up_cat_gate_pad_workspace_bytes(int B, int Ca, int Cs, int h, int w, int R) {
+  const smd::UpCatGate s{B, Ca, Cs, h, w, R, 0};
+  if (!smd::up_cat_gate_sizes_ok(s)) return 0;
+  return align256(smd::up_cat_gate_workspace_floats(s)*sizeof(float));
+}
+int smd_up_cat_gate_pad_fwd(const float* a, const float* bias_a, const float* skip, const float* w1, const float* w2, float* out, float* gate, float* mean,
+                            float* hid, void* workspace, size_t workspace_bytes, int B, int Ca, int Cs, int h, int w, int R, int act, void* stream) {
+  if (!a || !skip || !w1 || !w2 || !out || !gate || !mean || !hid || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  const smd::UpCatGate s{B, Ca, Cs, h, w, R, act};
+  if (!smd::up_cat_gate_sizes_ok(s)) return fail(SMD_E_INVALID, "invalid sizes B=%d Ca=%d Cs=%d h=%d w=%d R=%d act=%d", B, Ca, Cs, h, w, R, act);
+  if (workspace_bytes < smd_up_cat_gate_pad_workspace_bytes(B, Ca, Cs, h, w, R)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return check_launch(smd::launch_up_cat_gate_pad_fwd(s, a, bias_a, skip, w1, w2, out, gate, mean, hid, (float*)workspace, (hipStream_t)stream), "up_cat_gate_pad_fwd");
+}
+int smd_up_cat_gate_pad_bwd(const float* a, const float* bias_a, const float* skip, const float* w1, const float* w2, const float* gate, const float* mean,
+                            const float* hid, const float* g_out, float* g_a, float* g_skip, float* g_bias_a, float* g_w1, float* g_w2,
+                            void* workspace, size_t workspace_bytes, int B, int Ca, int Cs, int h, int w, int R, int act, void* stream) {
+  if (!a || !skip || !w1 || !w2 || !gate || !mean || !hid || !g_out || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if ((g_w1 != nullptr) != (g_w2 != nullptr)) return fail(SMD_E_INVALID, "the gradients of w1 and w2 come both or not at all");
+  if (!g_a && !g_skip && !g_bias_a && !g_w1) return fail(SMD_E_INVALID, "nothing to compute");
+  const smd::UpCatGate s{B, Ca, Cs, h, w, R, act};
+  if (!smd::up_cat_gate_sizes_ok(s)) return fail(SMD_E_INVALID, "invalid sizes B=%d Ca=%d Cs=%d h=%d w=%d R=%d act=%d", B, Ca, Cs, h, w, R, act);
+  if (workspace_bytes < smd_up_cat_gate_pad_workspace_bytes(B, Ca, Cs, h, w, R)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return check_launch(smd::launch_up_cat_gate_pad_bwd(s, a, bias_a, skip, w1, w2, gate, mean, hid, g_out, g_a, g_skip, g_bias_a, g_w1, g_w2, (float*)workspace,
+                                                      (hipStream_t)stream), "up_cat_gate_pad_bwd");
+}
+int smd_relu_pad_fwd(const float* x, const float* bias, float* out, int B, int C, int h, int w, void* stream) {
+  if (!x || !out) return fail(SMD_E_INVALID, "null pointer");
+  if (B < 1 || C < 1 || !dec_sizes_ok((long long)B*C, h, w)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d h=%d w=%d", B, C, h, w);
+  return check_launch(smd::launch_relu_pad_fwd(x, bias, out, B, C, h, w, (hipStream_t)stream), "relu_pad_fwd");
+}
+int smd_relu_pad_bwd(const float* x, const float* bias, const float* g_out, float* g_x, float* g_bias, void* workspace, size_t workspace_bytes,
+                     int B, int C, int h, int w, void* stream) {
+  if (!x || !g_out || !g_x || (g_bias && !workspace)) return fail(SMD_E_INVALID, "null pointer");
+  if (B < 1 || C < 1 || !dec_sizes_ok((long long)B*C, h, w)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d h=%d w=%d", B, C, h, w);
+  if (g_bias && workspace_bytes < smd_decoder_glue_workspace_bytes(B, C, h, w)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return check_launch(smd::launch_relu_pad_bwd(x, bias, g_out, g_x, g_bias, (float*)workspace, B, C, h, w, (hipStream_t)stream), "relu_pad_bwd");
+}
+
+// ------------------------------------------------------------------------------------------------
 // Depthwise 7x7 convolution (ConvNeXt)
 static bool dw_sizes_ok(int N, int C, int H, int W) {
   return N >= 1 && C >= 1 && H >= 1 && W >= 1 && (long long)N*C*smd::dwconv_tiles(H, W) < (1ll << 31) && (long long)H*W < (1ll << 30);

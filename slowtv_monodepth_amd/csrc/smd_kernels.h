@@ -325,6 +325,18 @@ hipError_t launch_elu_up_cat_pad_fwd(const void* a, const float* bias, const voi
                                      hipStream_t st);
 hipError_t launch_elu_up_cat_pad_bwd(const void* a, const float* bias, const void* g_out, void* g_a, void* g_skip, float* g_bias, float* ws,
                                      int B, int Ca, int Cs, int h, int w, int dt, hipStream_t st);
+hipError_t launch_relu_pad_fwd(const float* x, const float* bias, float* out, int B, int C, int h, int w, hipStream_t st);
+hipError_t launch_relu_pad_bwd(const float* x, const float* bias, const float* g_out, float* g_x, float* g_bias, float* ws, int B, int C, int h, int w,
+                               hipStream_t st);
+// DiffNet's attention stage in front of its convolution: reflect_pad1(gate o cat(nearest_x2(act(a + bias)), skip)); act 0: none, 1: ReLU
+struct UpCatGate { int B, Ca, Cs, h, w, R, act; };
+bool up_cat_gate_sizes_ok(const UpCatGate& s);
+size_t up_cat_gate_workspace_floats(const UpCatGate& s);
+hipError_t launch_up_cat_gate_pad_fwd(const UpCatGate& s, const float* a, const float* bias, const float* skip, const float* w1, const float* w2, float* out,
+                                      float* gate, float* mean, float* hid, float* ws, hipStream_t st);
+hipError_t launch_up_cat_gate_pad_bwd(const UpCatGate& s, const float* a, const float* bias, const float* skip, const float* w1, const float* w2,
+                                      const float* gate, const float* mean, const float* hid, const float* g_out, float* g_a, float* g_skip, float* g_bias,
+                                      float* g_w1, float* g_w2, float* ws, hipStream_t st);
 int bn_chunks(int N, int HW);
 hipError_t launch_bn_fwd(const float* x, const float* residual, const float* gamma, const float* beta, float* running_mean, float* running_var,
                          float momentum, float eps, int relu, float* y, float* save_mean, float* save_invstd, float* ws, int N, int C, int HW,

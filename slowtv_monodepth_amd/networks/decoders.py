@@ -1,9 +1,10 @@
 """Monodepth(2) decoder — registry key `monodepth` (reference: `src/networks/decoders/monodepth.py:14-89`) — and the CADepth decoder built on it —
 registry key `cadepth` (reference: `src/networks/decoders/cadepth.py`) — and the DDVNet decoder — registry key `ddvnet` (reference:
-`src/networks/decoders/ddvnet.py`)."""
+`src/networks/decoders/ddvnet.py`) — and the DiffNet decoder — registry key `diffnet` (reference: `src/networks/decoders/diffnet.py`)."""
 from __future__ import annotations
 
 import contextlib
+from collections import OrderedDict
 
 import torch
 import torch.nn as nn
@@ -11,7 +12,7 @@ import torch.nn.functional as F
 
 from ..registry import register
 
-__all__ = ['MonodepthDecoder', 'CaDepthDecoder', 'DetailEmphasis', 'DDVNetDecoder', 'SelfAttentionBlock', 'ACT']
+__all__ = ['MonodepthDecoder', 'CaDepthDecoder', 'DetailEmphasis', 'DDVNetDecoder', 'SelfAttentionBlock', 'DiffNetDecoder', 'AttentionBlock', 'ChannelAttention', 'ACT']
 
 ACT = {'sigmoid': nn.Sigmoid(), 'relu': nn.ReLU(inplace=True), 'none': nn.Identity(), None: nn.Identity()}
 
@@ -92,8 +93,11 @@ class MonodepthDecoder(nn.Module):
 
     def _head_glued(self, i, xp):
         """The output head of scale i on the padded activation `xp`."""
+        return self._head_stencil(self.out[str(i)], xp)
+
+    def _head_stencil(self, m, xp):
+        """The head convolution `m` with this decoder's activation on the padded activation `xp`."""
         from .. import functional as HF
-        m = self.out[str(i)]
         if self.out_ch == 1 and isinstance(self.act, (nn.Sigmoid, nn.Identity)):   # a one-channel head is a stencil: smd_conv3x3_head_* (fp32 or bf16 activation in, fp32 out)
             return HF.conv3x3_head(xp, m.weight.float(), m.bias.float() if m.bias is not None else None, 'sigmoid' if isinstance(self.act, nn.Sigmoid) else None)
         if 1 <= self.out_ch <= 4 and isinstance(self.act, (nn.Sigmoid, nn.ReLU, nn.Identity)):   # a few channels (or one with relu) are still a stencil: smd_conv3x3_headn_* (the mask decoder)
@@ -290,3 +294,120 @@ class DDVNetDecoder(MonodepthDecoder):
         from .. import functional as HF
         m = self.out[str(i)]
         return HF.ddv_head(xp, m.weight, m.bias, self.out_ch)
+
+
+def conv_block(cin: int, cout: int) -> nn.Sequential:
+    """conv3x3 + ELU under the reference's sub-module names (src/networks/decoders/utils.py:49-54)."""
+    return nn.Sequential(OrderedDict(conv=conv3x3(cin, cout), act=nn.ELU(inplace=True)))
+
+
+def upsample_block(cin: int, cout: int, upsample_mode: str = 'nearest') -> nn.Sequential:
+    """A stage without a skip connection (diffnet.py:12-18): conv + ELU, x2, conv + ELU."""
+    return nn.Sequential(conv_block(cin, cout), nn.Upsample(scale_factor=2, mode=upsample_mode), conv_block(cout, cout))
+
+
+class ChannelAttention(nn.Module):
+    """The squeeze-excite gate of DiffNet (diffnet.py:21-47): `x * sigmoid(fc(mean_hw(x)))` with two bias-free Linear layers around a `ch // ratio`
+    bottleneck.  `flatten(1)` where the reference squeezes: the same for every batch size, 1 included."""
+    def __init__(self, ch: int, ratio: int = 16):
+        super().__init__()
+        self.avg_pool = nn.AdaptiveAvgPool2d(1)
+        self.fc = nn.Sequential(nn.Linear(ch, ch//ratio, bias=False), nn.ReLU(inplace=True), nn.Linear(ch//ratio, ch, bias=False))
+
+    def forward(self, x):
+        return x*self.fc(self.avg_pool(x).flatten(1)).sigmoid()[..., None, None]
+
+
+class AttentionBlock(nn.Module):
+    """A stage with a skip connection (diffnet.py:50-74): `cat(x2(x), skip)` -> channel attention -> conv3x3 -> ReLU.  Same sub-module names as the reference's."""
+    def __init__(self, in_ch: int, skip_ch: int, out_ch: int | None = None, upsample_mode: str = 'nearest'):
+        super().__init__()
+        self.in_ch, self.out_ch, self.upsample_mode = in_ch + skip_ch, out_ch or in_ch, upsample_mode
+        self.layers = nn.Sequential(ChannelAttention(self.in_ch), conv3x3(self.in_ch, self.out_ch), nn.ReLU(inplace=True))
+
+    def forward(self, x, x_skip):
+        return self.layers(torch.cat((F.interpolate(x, scale_factor=2, mode=self.upsample_mode), x_skip), dim=1))
+
+
+@register('diffnet')
+class DiffNetDecoder(nn.Module):
+    """DiffNet (https://arxiv.org/abs/2110.09482; reference: src/networks/decoders/diffnet.py:77-146): five stages (256..16 channels); a stage whose
+    stride is among `enc_sc` is an `AttentionBlock` on the concatenation with that encoder feature, the others are `upsample_block`s.  Same constructor
+    arguments, sub-module names and double registration (`convs`, a ModuleDict, and `decoder`, a ModuleList of the same modules) as the reference, so its
+    state dict IS the reference's: `networks/checkpoint.py` passes the names through.  `outconv_0..3` always exist; they are applied for the scales in `out_sc`.
+
+    On CUDA (fp32, nearest up-sampling) everything in front of an attention stage's convolution — up-sampling, concatenation, pooling, gate, multiply,
+    reflection padding — is `functional.up_cat_gate_pad`, one pass that writes the convolution's padded input; the stage's ReLU and bias are folded into the
+    next stage's call and into `functional.relu_pad`, whose output the head reads.  The plain ATen path (CPU, other up-sampling modes, `plain_path()`) is the
+    reference's sequence.
+
+    Precision: on CUDA the glued path computes in fp32, also under bf16 autocast (the rule `CaDepthDecoder` follows): it then takes fp32 time and returns
+    fp32 disparities while the encoder around it runs in bf16.  Autocast to fp16 takes the plain ATen path."""
+
+    def __init__(self, num_ch_enc, enc_sc, upsample_mode: str = 'nearest', use_skip: bool = True,
+                 out_sc=(0, 1, 2, 3), out_ch: int = 1, out_act: str = 'sigmoid'):
+        super().__init__()
+        if out_act not in ACT: raise KeyError(f'Invalid activation key. ({out_act} vs. {tuple(ACT.keys())}')
+        self.num_ch_enc, self.enc_sc = list(num_ch_enc), list(enc_sc)
+        self.upsample_mode, self.use_skip, self.out_sc, self.out_ch, self.out_act = upsample_mode, use_skip, list(out_sc), out_ch, out_act
+        self.act = ACT[out_act]
+        self.num_ch_dec = [16, 32, 64, 128, 256]
+        self.convs = nn.ModuleDict()
+        for i in range(4, -1, -1):
+            cin, cout = (self.num_ch_enc[-1] if i == 4 else self.num_ch_dec[i + 1]), self.num_ch_dec[i]
+            if self._has_skip(i): self.convs[f'upconv_{i}'] = AttentionBlock(cin, self.num_ch_enc[self.enc_sc.index(2**i)], cout, upsample_mode)
+            else: self.convs[f'upconv_{i}'] = upsample_block(cin, cout, upsample_mode)
+        for i in range(4): self.convs[f'outconv_{i}'] = conv3x3(self.num_ch_dec[i], out_ch)
+        self.decoder = nn.ModuleList(list(self.convs.values()))
+        self._glued = True
+
+    def _has_skip(self, i: int) -> bool: return self.use_skip and 2**i in self.enc_sc
+
+    @contextlib.contextmanager
+    def plain_path(self):
+        """Within the block THIS decoder evaluates its plain ATen path wherever its tensors live (the yardstick the glued path is compared and timed against)."""
+        prev, self._glued = self._glued, False
+        try: yield self
+        finally: self._glued = prev
+
+    def forward(self, feat):
+        x = feat[-1]
+        amp_bf16 = torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
+        if self._glued and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and (amp_bf16 or not torch.is_autocast_enabled()) and self.upsample_mode == 'nearest' \
+                and self._stages_glue():
+            with torch.autocast('cuda', enabled=False): return self._forward_glued([f.float() for f in feat])
+        out = {}
+        for i in range(4, -1, -1):
+            m = self.convs[f'upconv_{i}']
+            x = m(x, feat[self.enc_sc.index(2**i)]) if self._has_skip(i) else m(x)
+            if i in self.out_sc: out[i] = self.act(self.convs[f'outconv_{i}'](x))
+        return out
+
+    def _stages_glue(self) -> bool:
+        """The glue hands an attention stage a raw tensor with the ReLU code or none: no attention stage may follow an `upsample_block` (whose activation is
+        ELU) and the gate needs a bottleneck of at least one channel.  Every ResNet and ConvNeXt trunk qualifies."""
+        skips = [self._has_skip(i) for i in range(4, -1, -1)]
+        return all(a or not b for a, b in zip(skips, skips[1:])) and all(m.layers[0].fc[0].out_features >= 1 for m in self.convs.values() if isinstance(m, AttentionBlock))
+
+    def _forward_glued(self, feat):
+        """Same network, same parameters, fp32.  Per attention stage `up_cat_gate_pad` writes the padded, gated concatenation and the routed bias-free
+        convolution reads it; the raw result goes, with its bias and the ReLU code, into the next stage's `up_cat_gate_pad`, and through `relu_pad` to the
+        stage's head and to a following `upsample_block`.  Those run on the Monodepth glue (`elu_up_cat_pad` without a skip, `elu_pad`)."""
+        from .. import functional as HF
+        conv = MonodepthDecoder._conv_glued
+        out = {}
+        raw, bias, act, xp = feat[-1], None, None, None          # (raw, bias, act): what the next attention stage takes as `a`
+        for i in range(4, -1, -1):
+            m = self.convs[f'upconv_{i}']
+            if self._has_skip(i):
+                gate, cv = m.layers[0], m.layers[1]
+                xin = HF.up_cat_gate_pad(raw, feat[self.enc_sc.index(2**i)], gate.fc[0].weight, gate.fc[2].weight, bias=bias, act=act)
+                raw, bias, act = conv(cv, xin), cv.bias, 'relu'
+                if i in self.out_sc or (i > 0 and not self._has_skip(i - 1)): xp = HF.relu_pad(raw, bias)
+            else:
+                m0, m1 = m[0].conv, m[2].conv
+                if xp is None: xp = HF.elu_pad(feat[-1], apply_elu=False)
+                c = conv(m1, HF.elu_up_cat_pad(conv(m0, xp), None, bias=m0.bias))
+                if i in self.out_sc or i > 0: xp = HF.elu_pad(c, bias=m1.bias, apply_elu=True)
+            if i in self.out_sc: out[i] = MonodepthDecoder._head_stencil(self, self.convs[f'outconv_{i}'], xp)
+        return out
