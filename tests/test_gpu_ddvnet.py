@@ -116,9 +116,14 @@ def test_ddv_head_refuses_wrong_operands_on_the_gpu(F):
     with pytest.raises(TypeError): F.ddv_head(xp, w, None)
     with pytest.raises(RuntimeError, match='GPU'): F.ddv_head(xp, w.cpu(), b)
     with pytest.raises(ValueError): F.ddv_head(xp, w[:, :8], b)
-    only_x = [xp.clone().requires_grad_(True), w, b]                   # a gradient for the input alone
-    F.ddv_head(*only_x).sum().backward()
-    assert only_x[0].grad is not None and torch.isfinite(only_x[0].grad).all()
+    only_x = [xp.clone().requires_grad_(True), w, b]                   # a gradient for the input alone, from the expanded gradient of a sum: its value is that of
+    F.set_conv_route('mfma')                                           # the full backward (route pinned as in test_ddv_head_matches_fp64; every subset: test_gpu_grad_subsets.py)
+    try:
+        F.ddv_head(*only_x).sum().backward()
+        every = [t.clone().requires_grad_(True) for t in (xp, w, b)]
+        F.ddv_head(*every).backward(torch.ones(2, 1, 4, 5, device='cuda'))
+    finally: F.set_conv_route('auto')
+    assert only_x[0].grad is not None and torch.isfinite(only_x[0].grad).all() and torch.equal(only_x[0].grad, every[0].grad)
 
 
 # ------------------------------------------------------------------------------------------------- decoder

@@ -60,7 +60,7 @@ def test_conv3x3_headn_kernel(F, B, C, h, w, act, n):
         yr.backward(gy.double())
         assert y.shape == (B, n, h, w) and rel_to_max(y.double(), yr) <= 2e-6, rel_to_max(y.double(), yr)
         for nm, a, r in zip(('g_xp', 'g_weight', 'g_bias'), L, R): assert rel_to_max(a.grad.double(), r.grad) <= 2e-6, (nm, rel_to_max(a.grad.double(), r.grad))
-    # only the weights ask for a gradient (a frozen encoder side), and only the input
+    # only the weights ask for a gradient (a frozen encoder side), and only the input (every subset, bit for bit against the full backward: test_gpu_grad_subsets.py)
     L = [xp.clone(), wt.clone().requires_grad_(True)]
     F.conv3x3_headn(L[0], L[1], None, act).backward(gy); assert rel_to_max(L[1].grad.double(), R[1].grad) <= 2e-6
     L = [xp.clone().requires_grad_(True), wt.clone()]

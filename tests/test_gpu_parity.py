@@ -1100,6 +1100,7 @@ def test_conv3x3_head_kernel(F, B, C, h, w, act):
     wt = torch.randn(1, C, 3, 3, device='cuda', generator=gen)/(3*C**0.5)
     bs = torch.randn(1, device='cuda', generator=gen)
     gy = torch.randn(B, 1, h, w, device='cuda', generator=gen)
+    refs = {}
     for bias in (bs, None):
         L = [t.clone().requires_grad_(True) for t in (xp, wt)] + ([bias.clone().requires_grad_(True)] if bias is not None else [])
         y = F.conv3x3_head(L[0], L[1], L[2] if bias is not None else None, act)
@@ -1110,11 +1111,13 @@ def test_conv3x3_head_kernel(F, B, C, h, w, act):
         yr.backward(gy.double())
         assert rel_to_max(y.double(), yr) <= 2e-6, rel_to_max(y.double(), yr)
         for nm, a, r in zip(('g_xp', 'g_weight', 'g_bias'), L, R): assert rel_to_max(a.grad.double(), r.grad) <= 2e-6, (nm, rel_to_max(a.grad.double(), r.grad))
-    # only the weights ask for a gradient (a frozen encoder side), and only the input
+        refs[bias is not None] = R
+    # only the weights ask for a gradient (a frozen encoder side), and only the input: the values of the full backward (every subset, bit for bit:
+    # test_gpu_grad_subsets.py)
     L = [xp.clone(), wt.clone().requires_grad_(True)]
-    F.conv3x3_head(L[0], L[1], None, act).backward(gy); assert L[1].grad is not None
+    F.conv3x3_head(L[0], L[1], None, act).backward(gy); assert rel_to_max(L[1].grad.double(), refs[False][1].grad) <= 2e-6
     L = [xp.clone().requires_grad_(True), wt.clone()]
-    F.conv3x3_head(L[0], L[1], bs, act).backward(gy); assert L[0].grad is not None
+    F.conv3x3_head(L[0], L[1], bs, act).backward(gy); assert L[1].grad is None and rel_to_max(L[0].grad.double(), refs[True][0].grad) <= 2e-6
     with pytest.raises(ValueError): F.conv3x3_head(xp, wt.repeat(2, 1, 1, 1), None, act)
     with pytest.raises(RuntimeError): F.conv3x3_head(xp.cpu(), wt.cpu(), None, act)
 
