@@ -19,11 +19,10 @@
 // Forward: per-plane partial sums (many blocks per plane) -> one block per sample finishes the means and does the two matrix-vector products
 // -> one apply sweep.  Backward: partial sums of g x -> one block per sample walks back through sigma, W2, ReLU, W1 -> the parameter gradients
 // (a fixed-order sum over the samples per element) and the apply sweep dx = g (1 + a) + dmean / (h w).  Every reduction has a fixed order: no
-// float atomics, bit-reproducible.
+// float atomics, bit-reproducible.  The gate's stages (chunking, matrix-vector products) and its backward are shared with DiffNet's gate: smd_glue_dev.h.
 #include <math.h>
 
-#include "smd_common.h"
-#include "smd_kernels.h"
+#include "smd_glue_dev.h"
 
 namespace smd {
 
@@ -240,22 +239,8 @@ hipError_t launch_channel_attention_bwd(const float* x, const float* stats, cons
 
 // ---------------------------------------------------------------------------------------------------------------- squeeze-excite gate
 constexpr int kSeBlock = 256;
-constexpr int kSeItems = 4096;             // floats of a plane one block of the pooling / apply sweeps handles
-constexpr int kSeMaxChunks = 256;
-constexpr int kSeGateBlock = 1024;         // the per-sample block of the matrix-vector products
-constexpr int kSeGateWaves = kSeGateBlock/64;
 
-int se_chunks(int HW) {
-  const int c = ceil_div(HW, kSeItems);
-  return c < 1 ? 1 : (c > kSeMaxChunks ? kSeMaxChunks : c);
-}
-
-__device__ __forceinline__ void se_range(int HW, int chunks, int k, int& lo, int& hi) {
-  int len = ceil_div(HW, chunks);
-  len = (len + 3) & ~3;
-  const long long l = (long long)k*len;
-  lo = l < HW ? (int)l : HW; hi = l + len < HW ? (int)(l + len) : HW;
-}
+int se_chunks(int HW) { return pool_chunks(HW); }   // (the name the workspace sizes of the C ABI know it by)
 
 // partial[plane][k] = sum over chunk k of x (BWD: of g x).  grid.x = planes x chunks.
 template <bool BWD, bool VEC>
@@ -265,7 +250,7 @@ __global__ __launch_bounds__(kSeBlock) void k_se_pool(const float* __restrict__ 
   const float* xp = x + (size_t)plane*HW;
   const float* gp = BWD ? g + (size_t)plane*HW : nullptr;
   int lo, hi;
-  se_range(HW, chunks, k, lo, hi);
+  pool_range(HW, chunks, k, lo, hi);
   float s = 0.f;
   if (VEC) {
     for (int i = lo + (int)threadIdx.x*4; i < hi; i += kSeBlock*4) {
@@ -282,105 +267,21 @@ __global__ __launch_bounds__(kSeBlock) void k_se_pool(const float* __restrict__ 
   if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 __device__ __forceinline__ float sigmoidf(double z) { return (float)(1.0/(1.0 + exp(-z))); }
 
-// out[r] = f(sum_c M[r][c] v[c]) for the rows of a row-major C x C matrix: one wave per row.  F(r, sum) stores.
-template <class F> __device__ __forceinline__ void matvec_rows(const float* __restrict__ M, const float* v, int C, F store) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int r = wave; r < C; r += kSeGateWaves) {
-    double s = 0.0;
-    for (int c = lane; c < C; c += 64) s += (double)M[(size_t)r*C + c]*(double)v[c];
-    s = wave_sum_d(s);
-    if (lane == 0) store(r, s);
-  }
-}
-// out[c] = f(sum_r M[r][c] v[r]): the product with the transpose.  Lanes own columns (coalesced rows), the waves split the rows, `red` (waves x 64) sums them.
-template <class F> __device__ __forceinline__ void matvec_cols(const float* __restrict__ M, const float* v, int C, double* red, F store) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int c0 = 0; c0 < C; c0 += 64) {
-    const int c = c0 + lane;
-    double s = 0.0;
-    if (c < C) for (int r = wave; r < C; r += kSeGateWaves) s += (double)M[(size_t)r*C + c]*(double)v[r];
-    __syncthreads();
-    red[wave*64 + lane] = s;
-    __syncthreads();
-    if (wave == 0 && c < C) {
-      double t = 0.0;
-#pragma unroll
-      for (int w = 0; w < kSeGateWaves; ++w) t += red[w*64 + lane];
-      store(c, t);
-    }
-  }
-}
-
 // One block per sample: means from the partial sums, hidden = relu(W1 mean + b1), a = sigmoid(W2 hidden + b2).  save = (a, mean, hidden), each (B, C).
-__global__ __launch_bounds__(kSeGateBlock) void k_se_gate_fwd(const float* __restrict__ partial, const float* __restrict__ w1, const float* __restrict__ b1,
+__global__ __launch_bounds__(kGateBlock) void k_se_gate_fwd(const float* __restrict__ partial, const float* __restrict__ w1, const float* __restrict__ b1,
                                                              const float* __restrict__ w2, const float* __restrict__ b2, float* save, int B, int C, int HW,
                                                              int chunks) {
   const int b = blockIdx.x;
   float* a = save + (size_t)b*C;
   float* mean = save + ((size_t)B + b)*C;
   float* hidden = save + ((size_t)2*B + b)*C;
-  for (int c = threadIdx.x; c < C; c += kSeGateBlock) {
-    double s = 0.0;
-    for (int k = 0; k < chunks; ++k) s += (double)partial[((size_t)b*C + c)*chunks + k];
-    mean[c] = (float)(s/(double)HW);
-  }
+  for (int c = threadIdx.x; c < C; c += kGateBlock) mean[c] = (float)(gate_plane_sum(partial, GatePartial{0, chunks, 0}, b, c, C, 0)/(double)HW);
   __threadfence_block(); __syncthreads();
-  matvec_rows(w1, mean, C, [&](int r, double s) { hidden[r] = fmaxf((float)(s + (double)b1[r]), 0.f); });
+  matvec_rows(w1, mean, C, C, [&](int r, double s) { hidden[r] = fmaxf((float)(s + (double)b1[r]), 0.f); });
   __threadfence_block(); __syncthreads();
-  matvec_rows(w2, hidden, C, [&](int r, double s) { a[r] = sigmoidf(s + (double)b2[r]); });
-}
-
-// One block per sample: da = sum g x (from the partial sums) -> dz2 = da a (1 - a) -> dh = W2^T dz2 -> dz1 = dh [hidden > 0] -> dmean = W1^T dz1 / HW.
-// vec = (dz2, dz1, dmean), each (B, C).
-__global__ __launch_bounds__(kSeGateBlock) void k_se_gate_bwd(const float* __restrict__ partial, const float* __restrict__ w1, const float* __restrict__ w2,
-                                                             const float* __restrict__ save, float* vec, int B, int C, int HW, int chunks) {
-  __shared__ double red[kSeGateWaves*64];
-  const int b = blockIdx.x;
-  const float* a = save + (size_t)b*C;
-  const float* hidden = save + ((size_t)2*B + b)*C;
-  float* dz2 = vec + (size_t)b*C;
-  float* dz1 = vec + ((size_t)B + b)*C;
-  float* dmean = vec + ((size_t)2*B + b)*C;
-  for (int c = threadIdx.x; c < C; c += kSeGateBlock) {
-    double s = 0.0;
-    for (int k = 0; k < chunks; ++k) s += (double)partial[((size_t)b*C + c)*chunks + k];
-    const double av = (double)a[c];
-    dz2[c] = (float)(s*av*(1.0 - av));
-  }
-  __threadfence_block(); __syncthreads();
-  matvec_cols(w2, dz2, C, red, [&](int c, double s) { dz1[c] = hidden[c] > 0.f ? (float)s : 0.f; });
-  __threadfence_block(); __syncthreads();
-  matvec_cols(w1, dz1, C, red, [&](int c, double s) { dmean[c] = (float)(s/(double)HW); });
-}
-
-// g_w2[r][s] = sum_b dz2[b][r] hidden[b][s],  g_w1[r][s] = sum_b dz1[b][r] mean[b][s],  g_b2 = sum_b dz2,  g_b1 = sum_b dz1: the samples in order.
-__global__ __launch_bounds__(256) void k_se_param_grad(const float* __restrict__ save, const float* __restrict__ vec, float* __restrict__ g_w1,
-                                                       float* __restrict__ g_b1, float* __restrict__ g_w2, float* __restrict__ g_b2, int B, int C) {
-  const size_t idx = (size_t)blockIdx.x*256 + threadIdx.x;
-  if (idx >= (size_t)C*C) return;
-  const int r = (int)(idx/C), s = (int)(idx - (size_t)r*C);
-  const float* mean = save + (size_t)B*C;
-  const float* hidden = save + (size_t)2*B*C;
-  const float* dz2 = vec;
-  const float* dz1 = vec + (size_t)B*C;
-  float t1 = 0.f, t2 = 0.f;
-  for (int b = 0; b < B; ++b) {
-    t2 = fmaf(dz2[(size_t)b*C + r], hidden[(size_t)b*C + s], t2);
-    t1 = fmaf(dz1[(size_t)b*C + r], mean[(size_t)b*C + s], t1);
-  }
-  g_w2[idx] = t2; g_w1[idx] = t1;
-  if (idx < (size_t)C) {
-    float u1 = 0.f, u2 = 0.f;
-    for (int b = 0; b < B; ++b) { u2 += dz2[(size_t)b*C + idx]; u1 += dz1[(size_t)b*C + idx]; }
-    g_b2[idx] = u2; g_b1[idx] = u1;
-  }
+  matvec_rows(w2, hidden, C, C, [&](int r, double s) { a[r] = sigmoidf(s + (double)b2[r]); });
 }
 
 // y = x (1 + a[plane])  (BWD: g_x = g (1 + a[plane]) + dmean[plane]).  grid.x = planes x chunks, the chunks of k_se_pool.
@@ -392,7 +293,7 @@ __global__ __launch_bounds__(kSeBlock) void k_se_apply(const float* __restrict__
   float* yp = y + (size_t)plane*HW;
   const float sc = 1.f + a[plane], sh = BWD ? dmean[plane] : 0.f;
   int lo, hi;
-  se_range(HW, chunks, k, lo, hi);
+  pool_range(HW, chunks, k, lo, hi);
   if (VEC) {
     for (int i = lo + (int)threadIdx.x*4; i < hi; i += kSeBlock*4) {
       const f4 v = *(const f4*)(xp + i);
@@ -413,7 +314,7 @@ hipError_t launch_se_gate_fwd(const float* x, const float* w1, const float* b1, 
   const bool vec = (HW % 4) == 0;
   if (vec) hipLaunchKernelGGL((k_se_pool<false, true>), dim3(blocks), dim3(kSeBlock), 0, st, x, (const float*)nullptr, HW, chunks, ws);
   else hipLaunchKernelGGL((k_se_pool<false, false>), dim3(blocks), dim3(kSeBlock), 0, st, x, (const float*)nullptr, HW, chunks, ws);
-  hipLaunchKernelGGL(k_se_gate_fwd, dim3(B), dim3(kSeGateBlock), 0, st, ws, w1, b1, w2, b2, save, B, C, HW, chunks);
+  hipLaunchKernelGGL(k_se_gate_fwd, dim3(B), dim3(kGateBlock), 0, st, ws, w1, b1, w2, b2, save, B, C, HW, chunks);
   if (vec) hipLaunchKernelGGL((k_se_apply<false, true>), dim3(blocks), dim3(kSeBlock), 0, st, x, save, (const float*)nullptr, HW, chunks, y);
   else hipLaunchKernelGGL((k_se_apply<false, false>), dim3(blocks), dim3(kSeBlock), 0, st, x, save, (const float*)nullptr, HW, chunks, y);
   return hipGetLastError();
@@ -425,13 +326,14 @@ hipError_t launch_se_gate_bwd(const float* x, const float* g_y, const float* w1,
   const unsigned blocks = (unsigned)((size_t)B*C*chunks);
   const bool vec = (HW % 4) == 0;
   float* partial = ws;
-  float* vecs = ws + (((size_t)B*C*chunks + 3) & ~(size_t)3);     // (dz2, dz1, dmean)
+  float* vecs = ws + (((size_t)B*C*chunks + 3) & ~(size_t)3);     // (dz2, dz1, dmean), each (B, C)
+  float* dmean = vecs + (size_t)2*B*C;
+  const float* mean = save + (size_t)B*C;                         // save = (a, mean, hidden)
+  const float* hidden = save + (size_t)2*B*C;
   if (vec) hipLaunchKernelGGL((k_se_pool<true, true>), dim3(blocks), dim3(kSeBlock), 0, st, x, g_y, HW, chunks, partial);
   else hipLaunchKernelGGL((k_se_pool<true, false>), dim3(blocks), dim3(kSeBlock), 0, st, x, g_y, HW, chunks, partial);
-  hipLaunchKernelGGL(k_se_gate_bwd, dim3(B), dim3(kSeGateBlock), 0, st, partial, w1, w2, save, vecs, B, C, HW, chunks);
-  if (g_w1) hipLaunchKernelGGL(k_se_param_grad, dim3((unsigned)(((size_t)C*C + 255)/256)), dim3(256), 0, st, save, vecs, g_w1, g_b1, g_w2, g_b2, B, C);
+  launch_gate_bwd(GateBwd{partial, w1, w2, save, mean, hidden, vecs, vecs + (size_t)B*C, dmean, GatePartial{0, chunks, 0}, B, C, 0, C, HW}, g_w1, g_b1, g_w2, g_b2, st);
   if (g_x) {
-    const float* dmean = vecs + (size_t)2*B*C;
     if (vec) hipLaunchKernelGGL((k_se_apply<true, true>), dim3(blocks), dim3(kSeBlock), 0, st, g_y, save, dmean, HW, chunks, g_x);
     else hipLaunchKernelGGL((k_se_apply<true, false>), dim3(blocks), dim3(kSeBlock), 0, st, g_y, save, dmean, HW, chunks, g_x);
   }

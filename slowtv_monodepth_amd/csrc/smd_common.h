@@ -95,6 +95,11 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Per-(support, sample) camera constants, folded so that a pixel costs 6 FMAs + 1 rcp + 2 mul:

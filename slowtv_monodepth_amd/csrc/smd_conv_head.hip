@@ -203,7 +203,7 @@ __global__ __launch_bounds__(64) void k_head_wgt_finalize(const float* __restric
   for (int k = 0; k < nk; ++k) {
     double acc = 0.0;
     for (unsigned t = threadIdx.x; t < T; t += 64) acc += (double)partial[((size_t)c*T + t)*9 + k];
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    acc = wave_sum_f64(acc);
     if (threadIdx.x == 0) {
       if (c == C) { if (g_bias) g_bias[0] = (float)acc; }
       else g_w[c*9 + k] = (float)acc;

@@ -220,7 +220,7 @@ __global__ __launch_bounds__(64) void k_headn_wgt_finalize(const float* __restri
   for (int k = 0; k < nk; ++k) {
     double acc = 0.0;
     for (unsigned t = threadIdx.x; t < T; t += 64) acc += (double)partial[(((size_t)c*T + t)*N + o)*9 + k];
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    acc = wave_sum_f64(acc);
     if (threadIdx.x == 0) {
       if (c == C) { if (g_bias) g_bias[o] = (float)acc; }
       else g_w[((size_t)o*C + c)*9 + k] = (float)acc;

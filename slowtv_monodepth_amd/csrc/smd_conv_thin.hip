@@ -239,7 +239,7 @@ __global__ __launch_bounds__(256) void k_thin_wgt_finalize(const float* __restri
   if (i >= n) return;
   double acc = 0.0;
   for (unsigned t = lane; t < T; t += 64) acc += (double)partial[(size_t)i*T + t];
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  acc = wave_sum_f64(acc);
   if (lane == 0) g_w[i] = (float)acc;
 }
 

@@ -1,38 +1,22 @@
-// smd_decoder.hip — glue between the 3x3 convolutions of the Monodepth decoder.
+// smd_decoder.hip — glue between the 3x3 convolutions of the decoders.
 //
 // The reference decoder (src/networks/decoders/monodepth.py:71-89, decoders/utils.py:44-54) runs, per stage,
 //   reflect-pad -> conv3x3 -> ELU -> nearest x2 -> cat(skip) -> reflect-pad -> conv3x3 -> ELU -> [reflect-pad -> conv3x3 -> sigmoid]
-// as separate ATen kernels, each a full read + write of the activation.  The convolutions stay with MIOpen; everything
-// between them collapses into two gather kernels that write the NEXT convolution's already-padded input:
-//   k_elu_pad         out = reflect_pad1(elu(x + bias))                              (B,C,h,w)           -> (B,C,h+2,w+2)
+// as separate ATen kernels, each a full read + write of the activation.  The convolutions run on this library's split-bf16 MFMA kernels
+// (smd_conv_mfma.hip, smd_conv_thin.hip, the heads; MIOpen only where the routing table serves no kernel); everything between them collapses into
+// gather kernels that write the NEXT convolution's already-padded input:
+//   k_elu_pad         out = reflect_pad1(act(x + bias))                              (B,C,h,w)           -> (B,C,h+2,w+2)
 //   k_elu_up_cat_pad  out = reflect_pad1(cat(nearest_x2(elu(a + bias)), skip))       (B,Ca,h,w),(B,Cs,2h,2w) -> (B,Ca+Cs,2h+2,2w+2)
-// and two adjoint gathers (deterministic, no atomics).  The convolution's bias is added here (the convolution itself runs
-// bias-free), so MIOpen's separate bias pass and ATen's bias-gradient reduction over the full tensor both disappear: the
-// adjoint gathers already hold the pre-activation gradient and emit its per-block channel sums.  ELU is recomputed from the saved pre-activation in the backward
-// (elu'(x) = x > 0 ? 1 : exp(x)), so no activated tensor is kept.
-#include "smd_common.h"
-#include "smd_kernels.h"
+//   k_ucg_*           the same times DiffNet's channel gate (second half of this file)
+// and their adjoint gathers (deterministic, no atomics).  The convolution's bias is added here (the convolution itself runs bias-free), so a separate
+// bias pass and a bias-gradient reduction over the full tensor both disappear: the adjoint gathers already hold the pre-activation gradient and emit
+// its per-block channel sums.  The activation is recomputed from the saved pre-activation in the backward (elu'(x) = x > 0 ? 1 : exp(x)), so no
+// activated tensor is kept.  The stages themselves (source map, pad adjoint, reductions, the gate's matrix-vector products) are in smd_glue_dev.h;
+// this file holds the kernels assembled from them, the backward of the two-layer gate (shared with the squeeze-excite gate of smd_attention.hip) and
+// the launchers.
+#include "smd_glue_dev.h"
 
 namespace smd {
-
-constexpr int kDecBlock = 256;
-constexpr int kDecPerThread = 4;   // block-strided elements per thread: 4 independent load->store chains, 4x fewer blocks
-constexpr int kDecChunk = kDecBlock*kDecPerThread;
-
-__device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : __expf(x) - 1.f; }
-__device__ __forceinline__ float elu1_grad(float x) { return x > 0.f ? 1.f : __expf(x); }
-// the activation the pad kernels apply to x + bias: the Monodepth stages' ELU, the DiffNet attention stages' ReLU
-enum { kActNone = 0, kActElu = 1, kActRelu = 2 };
-__device__ __forceinline__ float glue_act(float x, int act) { return act == kActElu ? elu1(x) : (act == kActRelu ? fmaxf(x, 0.f) : x); }
-__device__ __forceinline__ float glue_act_grad(float x, int act) { return act == kActElu ? elu1_grad(x) : (act == kActRelu ? (x > 0.f ? 1.f : 0.f) : 1.f); }
-__device__ __forceinline__ int unpad_reflect(int p, int n) { const int r = p - 1; return r < 0 ? -r : (r >= n ? 2*(n - 1) - r : r); }
-
-__device__ __forceinline__ void block_store_sum(float v, float* red, float* dst) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) { float t = 0.f; for (int k = 0; k < kDecBlock/64; ++k) t += red[k]; *dst = t; }
-}
 
 // g_bias[c] = sum over samples and chunks of the per-block partial sums of the pre-activation gradient (fp64, fixed order).
 __global__ __launch_bounds__(64) void k_bias_finalize(const float* __restrict__ partial, int B, int C, unsigned chunks, float* __restrict__ g_bias) {
@@ -40,13 +24,9 @@ __global__ __launch_bounds__(64) void k_bias_finalize(const float* __restrict__ 
   double acc = 0.0;
   const unsigned per = chunks, n = (unsigned)B*per;
   for (unsigned i = threadIdx.x; i < n; i += 64) { const unsigned b = i/per, k = i - b*per; acc += (double)partial[((size_t)b*C + c)*per + k]; }
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  acc = wave_sum_f64(acc);
   if (threadIdx.x == 0) g_bias[c] = (float)acc;
 }
-
-// Sum of g over the padded positions that read un-padded index r along one axis of length n: p = r+1, plus the mirrored
-// border cell when r is the second / second-to-last element.
-#define SMD_PAD_ADJ_POS(r, n, p0, p1, p2) const int p0 = (r) + 1, p1 = ((r) == 1) ? 0 : -1, p2 = ((r) == (n) - 2) ? (n) + 1 : -1
 
 template <typename TA, typename TO>
 __global__ __launch_bounds__(kDecBlock) void k_elu_pad_fwd(const TA* __restrict__ x, const float* __restrict__ bias, TO* __restrict__ out, int C, int h, int w, int act,
@@ -79,18 +59,7 @@ __global__ __launch_bounds__(kDecBlock) void k_elu_pad_bwd(const TA* __restrict_
     const int idx = chunk*kDecChunk + k*kDecBlock + threadIdx.x;
     if (idx >= h*w) break;
     const int i = idx/w, j = idx - i*w;
-    float acc = ld_as_float<TO>(g, (i + 1)*W + j + 1);
-    if (i == 1 || i == h - 2 || j == 1 || j == w - 2) {   // rare: mirrored border cells
-      SMD_PAD_ADJ_POS(i, h, y0, y1, y2); SMD_PAD_ADJ_POS(j, w, x0, x1, x2);
-      const int ys[3] = {y0, y1, y2}, xs[3] = {x0, x1, x2};
-      acc = 0.f;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        if (ys[a] < 0) continue;
-#pragma unroll
-        for (int b = 0; b < 3; ++b) if (xs[b] >= 0) acc += ld_as_float<TO>(g, ys[a]*W + xs[b]);
-      }
-    }
+    const float acc = pad_adj_at(g, i, j, h, w, W);
     const float gv = act ? acc*glue_act_grad(ld_as_float<TA>(x, (size_t)plane*h*w + idx) + bc, act) : acc;
     st_from_float<TA>(g_x, (size_t)plane*h*w + idx, gv); bsum += gv;
   }
@@ -131,34 +100,11 @@ __global__ __launch_bounds__(kDecBlock) void k_elu_up_cat_pad_bwd_a(const TA* __
   const TO* g = g_out + ((size_t)b*C + c)*(H2 + 2)*W;
   const float bc = bias ? bias[c] : 0.f;
   for (int k = 0; k < kDecPerThread; ++k) {
-  const int idx = chunk*kDecChunk + k*kDecBlock + threadIdx.x;
-  if (idx >= h*w) break;
-  const int i = idx/w, j = idx - i*w;
-  float acc = 0.f;
-  if (i > 0 && i < h - 1 && j > 0 && j < w - 1) {   // interior: the plain 2x2 block
-    const TO* gp = g + (2*i + 1)*W + 2*j + 1;
-    acc = (ld_as_float<TO>(gp, 0) + ld_as_float<TO>(gp, 1)) + (ld_as_float<TO>(gp, W) + ld_as_float<TO>(gp, W + 1));
-  } else
-#pragma unroll
-  for (int dr = 0; dr < 2; ++dr) {
-    const int r = 2*i + dr;
-    SMD_PAD_ADJ_POS(r, H2, y0, y1, y2);
-    const int ys[3] = {y0, y1, y2};
-#pragma unroll
-    for (int dq = 0; dq < 2; ++dq) {
-      const int q = 2*j + dq;
-      SMD_PAD_ADJ_POS(q, W2, x0, x1, x2);
-      const int xs[3] = {x0, x1, x2};
-#pragma unroll
-      for (int m = 0; m < 3; ++m) {
-        if (ys[m] < 0) continue;
-#pragma unroll
-        for (int n = 0; n < 3; ++n) if (xs[n] >= 0) acc += ld_as_float<TO>(g, ys[m]*W + xs[n]);
-      }
-    }
-  }
-  const float gv = acc*elu1_grad(ld_as_float<TA>(a, (size_t)plane*h*w + idx) + bc);
-  st_from_float<TA>(g_a, (size_t)plane*h*w + idx, gv); bsum += gv;
+    const int idx = chunk*kDecChunk + k*kDecBlock + threadIdx.x;
+    if (idx >= h*w) break;
+    const int i = idx/w, j = idx - i*w;
+    const float gv = up_pad_adj_at<true>(g, i, j, h, w, W)*elu1_grad(ld_as_float<TA>(a, (size_t)plane*h*w + idx) + bc);   // <true>: this kernel's border order
+    st_from_float<TA>(g_a, (size_t)plane*h*w + idx, gv); bsum += gv;
   }
   if (bias_partial) block_store_sum(bsum, red, bias_partial + blockIdx.x);
 }
@@ -176,19 +122,7 @@ __global__ __launch_bounds__(kDecBlock) void k_elu_up_cat_pad_bwd_skip(const TO*
     const int idx = chunk*kDecChunk + k*kDecBlock + threadIdx.x;
     if (idx >= H2*W2) break;
     const int r = idx/W2, q = idx - r*W2;
-    float acc = ld_as_float<TO>(g, (r + 1)*W + q + 1);
-    if (r == 1 || r == H2 - 2 || q == 1 || q == W2 - 2) {
-      SMD_PAD_ADJ_POS(r, H2, y0, y1, y2); SMD_PAD_ADJ_POS(q, W2, x0, x1, x2);
-      const int ys[3] = {y0, y1, y2}, xs[3] = {x0, x1, x2};
-      acc = 0.f;
-#pragma unroll
-      for (int m = 0; m < 3; ++m) {
-        if (ys[m] < 0) continue;
-#pragma unroll
-        for (int n = 0; n < 3; ++n) if (xs[n] >= 0) acc += ld_as_float<TO>(g, ys[m]*W + xs[n]);
-      }
-    }
-    st_from_float<TS>(g_skip, (size_t)plane*H2*W2 + idx, acc);
+    st_from_float<TS>(g_skip, (size_t)plane*H2*W2 + idx, pad_adj_at(g, r, q, H2, W2, W));
   }
 }
 
@@ -196,14 +130,21 @@ __global__ __launch_bounds__(kDecBlock) void k_elu_up_cat_pad_bwd_skip(const TO*
 #define SMD_DT_A 1
 #define SMD_DT_S 2
 #define SMD_DT_O 4
+template <typename T> struct ElemTag { typedef T type; };
+// f(a, s, o): ElemTags of the element types the three dtype bits select.  A kernel launched from f is instantiated for the types f names only.
+template <class F> static void for_dtypes(int dt, F f) {
+  auto pick = [](bool is_bf16, auto g) { if (is_bf16) g(ElemTag<bf16>{}); else g(ElemTag<float>{}); };
+  pick(dt & SMD_DT_A, [&](auto a) { pick(dt & SMD_DT_S, [&](auto s) { pick(dt & SMD_DT_O, [&](auto o) { f(a, s, o); }); }); });
+}
+#define SMD_ELEM(tag) typename decltype(tag)::type
 
 static hipError_t launch_act_pad_fwd(const void* x, const float* bias, void* out, int B, int C, int h, int w, int act, int dt, hipStream_t st) {
   const unsigned chunks = ceil_div((h + 2)*(w + 2), kDecChunk);
   const dim3 grid((unsigned)((size_t)B*C*chunks)), blk(kDecBlock);
-#define SMD_GO(TA_, TO_) hipLaunchKernelGGL((k_elu_pad_fwd<TA_, TO_>), grid, blk, 0, st, (const TA_*)x, bias, (TO_*)out, C, h, w, act, chunks)
-  if (dt & SMD_DT_A) { if (dt & SMD_DT_O) SMD_GO(bf16, bf16); else SMD_GO(bf16, float); }
-  else { if (dt & SMD_DT_O) SMD_GO(float, bf16); else SMD_GO(float, float); }
-#undef SMD_GO
+  for_dtypes(dt, [&](auto ta, auto, auto to) {
+    typedef SMD_ELEM(ta) TA; typedef SMD_ELEM(to) TO;
+    hipLaunchKernelGGL((k_elu_pad_fwd<TA, TO>), grid, blk, 0, st, (const TA*)x, bias, (TO*)out, C, h, w, act, chunks);
+  });
   return hipGetLastError();
 }
 size_t decoder_bias_partials(int B, int C, int h, int w) { return (size_t)B*C*ceil_div(h*w, kDecChunk); }
@@ -211,10 +152,10 @@ static hipError_t launch_act_pad_bwd(const void* x, const float* bias, const voi
                                      int act, int dt, hipStream_t st) {
   const unsigned chunks = ceil_div(h*w, kDecChunk);
   const dim3 grid((unsigned)((size_t)B*C*chunks)), blk(kDecBlock);
-#define SMD_GO(TA_, TO_) hipLaunchKernelGGL((k_elu_pad_bwd<TA_, TO_>), grid, blk, 0, st, (const TA_*)x, bias, (const TO_*)g_out, (TA_*)g_x, g_bias ? ws : nullptr, C, h, w, act, chunks)
-  if (dt & SMD_DT_A) { if (dt & SMD_DT_O) SMD_GO(bf16, bf16); else SMD_GO(bf16, float); }
-  else { if (dt & SMD_DT_O) SMD_GO(float, bf16); else SMD_GO(float, float); }
-#undef SMD_GO
+  for_dtypes(dt, [&](auto ta, auto, auto to) {
+    typedef SMD_ELEM(ta) TA; typedef SMD_ELEM(to) TO;
+    hipLaunchKernelGGL((k_elu_pad_bwd<TA, TO>), grid, blk, 0, st, (const TA*)x, bias, (const TO*)g_out, (TA*)g_x, g_bias ? ws : nullptr, C, h, w, act, chunks);
+  });
   if (g_bias) hipLaunchKernelGGL(k_bias_finalize, dim3(C), dim3(64), 0, st, ws, B, C, chunks, g_bias);
   return hipGetLastError();
 }
@@ -237,14 +178,10 @@ hipError_t launch_elu_up_cat_pad_fwd(const void* a, const float* bias, const voi
                                      hipStream_t st) {
   const unsigned chunks = ceil_div((2*h + 2)*(2*w + 2), kDecChunk);
   const dim3 grid((unsigned)((size_t)B*(Ca + Cs)*chunks)), blk(kDecBlock);
-#define SMD_GO(TA_, TS_, TO_) hipLaunchKernelGGL((k_elu_up_cat_pad_fwd<TA_, TS_, TO_>), grid, blk, 0, st, (const TA_*)a, bias, (const TS_*)skip, (TO_*)out, Ca, Cs, h, w, chunks)
-  switch (dt & 7) {
-    case 0: SMD_GO(float, float, float); break;  case 1: SMD_GO(bf16, float, float); break;
-    case 2: SMD_GO(float, bf16, float); break;   case 3: SMD_GO(bf16, bf16, float); break;
-    case 4: SMD_GO(float, float, bf16); break;   case 5: SMD_GO(bf16, float, bf16); break;
-    case 6: SMD_GO(float, bf16, bf16); break;    default: SMD_GO(bf16, bf16, bf16); break;
-  }
-#undef SMD_GO
+  for_dtypes(dt, [&](auto ta, auto ts, auto to) {
+    typedef SMD_ELEM(ta) TA; typedef SMD_ELEM(ts) TS; typedef SMD_ELEM(to) TO;
+    hipLaunchKernelGGL((k_elu_up_cat_pad_fwd<TA, TS, TO>), grid, blk, 0, st, (const TA*)a, bias, (const TS*)skip, (TO*)out, Ca, Cs, h, w, chunks);
+  });
   return hipGetLastError();
 }
 hipError_t launch_elu_up_cat_pad_bwd(const void* a, const float* bias, const void* g_out, void* g_a, void* g_skip, float* g_bias, float* ws,
@@ -252,19 +189,19 @@ hipError_t launch_elu_up_cat_pad_bwd(const void* a, const float* bias, const voi
   if (g_a) {
     const unsigned chunks = ceil_div(h*w, kDecChunk);
     const dim3 grid((unsigned)((size_t)B*Ca*chunks)), blk(kDecBlock);
-#define SMD_GO(TA_, TO_) hipLaunchKernelGGL((k_elu_up_cat_pad_bwd_a<TA_, TO_>), grid, blk, 0, st, (const TA_*)a, bias, (const TO_*)g_out, (TA_*)g_a, g_bias ? ws : nullptr, Ca, Cs, h, w, chunks)
-    if (dt & SMD_DT_A) { if (dt & SMD_DT_O) SMD_GO(bf16, bf16); else SMD_GO(bf16, float); }
-    else { if (dt & SMD_DT_O) SMD_GO(float, bf16); else SMD_GO(float, float); }
-#undef SMD_GO
+    for_dtypes(dt, [&](auto ta, auto, auto to) {
+      typedef SMD_ELEM(ta) TA; typedef SMD_ELEM(to) TO;
+      hipLaunchKernelGGL((k_elu_up_cat_pad_bwd_a<TA, TO>), grid, blk, 0, st, (const TA*)a, bias, (const TO*)g_out, (TA*)g_a, g_bias ? ws : nullptr, Ca, Cs, h, w, chunks);
+    });
     if (g_bias) hipLaunchKernelGGL(k_bias_finalize, dim3(Ca), dim3(64), 0, st, ws, B, Ca, chunks, g_bias);
   }
   if (g_skip && Cs > 0) {
     const unsigned chunks = ceil_div(4*h*w, kDecChunk);
     const dim3 grid((unsigned)((size_t)B*Cs*chunks)), blk(kDecBlock);
-#define SMD_GO(TS_, TO_) hipLaunchKernelGGL((k_elu_up_cat_pad_bwd_skip<TS_, TO_>), grid, blk, 0, st, (const TO_*)g_out, (TS_*)g_skip, Ca, Cs, h, w, chunks)
-    if (dt & SMD_DT_S) { if (dt & SMD_DT_O) SMD_GO(bf16, bf16); else SMD_GO(bf16, float); }
-    else { if (dt & SMD_DT_O) SMD_GO(float, bf16); else SMD_GO(float, float); }
-#undef SMD_GO
+    for_dtypes(dt, [&](auto, auto ts, auto to) {
+      typedef SMD_ELEM(ts) TS; typedef SMD_ELEM(to) TO;
+      hipLaunchKernelGGL((k_elu_up_cat_pad_bwd_skip<TS, TO>), grid, blk, 0, st, (const TO*)g_out, (TS*)g_skip, Ca, Cs, h, w, chunks);
+    });
   }
   return hipGetLastError();
 }
@@ -277,29 +214,19 @@ hipError_t launch_elu_up_cat_pad_bwd(const void* a, const float* bias, const voi
 //             skip; in fp64 from the first add to the sigmoid: with large Linear weights the gate amplifies a rounding of the mean by the product of the two
 //             layers' gains, and an fp32 mean then decides the error of the output and of every gradient) -> k_ucg_gate_fwd (one block per sample: means, the two small matrix-vector products) -> k_ucg_apply_fwd (the gather of
 //             k_elu_up_cat_pad_fwd times the gate).
-//   backward: k_ucg_reduce_bwd (per-block sums of G o src, G the pad adjoint of g_out, folded on the fly) -> k_ucg_gate_bwd (one block per sample: back
-//             through the sigmoid, W2, the ReLU, W1) -> k_ucg_param_grad (the samples in order) -> k_ucg_apply_bwd_a / _skip (gate G + dmean / n).
+//   backward: k_ucg_reduce_bwd (per-block sums of G o src, G the pad adjoint of g_out, folded on the fly) -> k_gate_bwd (one block per sample: back
+//             through the sigmoid, W2, the ReLU, W1) -> k_gate_param_grad (the samples in order) -> k_ucg_apply_bwd_a / _skip (gate G + dmean / n).
 // Every sum has a fixed order: no float atomics, two runs are bit-equal.
-constexpr int kUcgItems = 4096;            // floats of a plane one block of the pooling sweep handles
-constexpr int kUcgMaxChunks = 256;
-constexpr int kUcgGateBlock = 1024;        // the per-sample block of the matrix-vector products
-constexpr int kUcgGateWaves = kUcgGateBlock/64;
-
-static int ucg_pool_chunks(int n) {
-  const int c = ceil_div(n, kUcgItems);
-  return c < 1 ? 1 : (c > kUcgMaxChunks ? kUcgMaxChunks : c);
-}
-// where the per-block sums of the two halves live and how many each plane has: the a planes first ((b Ca + c) cha + k), then the skip planes
-struct UcgPartial { unsigned na; int cha, chs; };
-static UcgPartial ucg_partial(const UpCatGate& s, bool bwd) {
-  UcgPartial p;
-  p.cha = bwd ? ceil_div(s.h*s.w, kDecChunk) : ucg_pool_chunks(s.h*s.w);
-  p.chs = bwd ? ceil_div(4*s.h*s.w, kDecChunk) : ucg_pool_chunks(4*s.h*s.w);
+// where the per-block sums of the two halves live and how many each plane has: the a planes first, then the skip planes
+static GatePartial ucg_partial(const UpCatGate& s, bool bwd) {
+  GatePartial p;
+  p.cha = bwd ? ceil_div(s.h*s.w, kDecChunk) : pool_chunks(s.h*s.w);
+  p.chs = bwd ? ceil_div(4*s.h*s.w, kDecChunk) : pool_chunks(4*s.h*s.w);
   p.na = (unsigned)((size_t)s.B*s.Ca*p.cha);
   return p;
 }
 static size_t ucg_partial_floats(const UpCatGate& s, bool bwd) {
-  const UcgPartial p = ucg_partial(s, bwd);
+  const GatePartial p = ucg_partial(s, bwd);
   return (((size_t)s.B*s.Ca*p.cha + (size_t)s.B*s.Cs*p.chs) + 3) & ~(size_t)3;
 }
 static size_t ucg_vec_floats(const UpCatGate& s) { return (((size_t)s.B*(2*(s.Ca + s.Cs) + s.R)) + 3) & ~(size_t)3; }   // dz2 (B,C), dmean (B,C), dz1 (B,R)
@@ -315,24 +242,16 @@ size_t up_cat_gate_workspace_floats(const UpCatGate& s) {
   return fwd > bwd ? fwd : bwd;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // partial[block] = the sum of src over chunk k of a plane: blocks [0, na) take act(a + bias) on an h x w plane, the others skip on a 2h x 2w plane
 __global__ __launch_bounds__(kDecBlock) void k_ucg_pool(const float* __restrict__ a, const float* __restrict__ bias, const float* __restrict__ skip, int Ca,
-                                                        int hw, int act, UcgPartial pp, double* __restrict__ partial) {
+                                                        int hw, int act, GatePartial pp, double* __restrict__ partial) {
   __shared__ double red[kDecBlock/64];
   const bool from_a = blockIdx.x < pp.na;
   const unsigned id = from_a ? blockIdx.x : blockIdx.x - pp.na;
   const int ch = from_a ? pp.cha : pp.chs, n = from_a ? hw : 4*hw;
   const unsigned plane = id/ch, k = id - plane*ch;
-  int len = ceil_div(n, ch);
-  len = (len + 3) & ~3;
-  const long long l = (long long)k*len;
-  const int lo = l < n ? (int)l : n, hi = l + len < n ? (int)(l + len) : n;
+  int lo, hi;
+  pool_range(n, ch, k, lo, hi);
   const float* p = (from_a ? a : skip) + (size_t)plane*n;
   const double bc = (from_a && bias) ? (double)bias[plane % Ca] : 0.0;
   const bool relu = from_a && act;
@@ -346,69 +265,29 @@ __global__ __launch_bounds__(kDecBlock) void k_ucg_pool(const float* __restrict_
   } else {
     for (int i = lo + (int)threadIdx.x; i < hi; i += kDecBlock) s += term(p[i]);
   }
-  s = wave_sum_f64(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) { double t = 0.0; for (int k = 0; k < kDecBlock/64; ++k) t += red[k]; partial[blockIdx.x] = t; }
-}
-
-// the sum of src (backward: of G o src) over plane (b, c): its per-block sums in order, fp64
-template <typename T> __device__ __forceinline__ double ucg_plane_sum(const T* __restrict__ partial, UcgPartial pp, int b, int c, int Ca, int Cs) {
-  const bool from_a = c < Ca;
-  const T* p = from_a ? partial + ((size_t)b*Ca + c)*pp.cha : partial + pp.na + ((size_t)b*Cs + (c - Ca))*pp.chs;
-  const int n = from_a ? pp.cha : pp.chs;
-  double s = 0.0;
-  for (int k = 0; k < n; ++k) s += (double)p[k];
-  return s;
-}
-
-// store(r, sum_c M[r][c] v[c]) for the rows of a row-major rows x cols matrix: one wave per row
-template <class F> __device__ __forceinline__ void ucg_matvec_rows(const float* __restrict__ M, const double* v, int rows, int cols, F store) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int r = wave; r < rows; r += kUcgGateWaves) {
-    double s = 0.0;
-    for (int c = lane; c < cols; c += 64) s += (double)M[(size_t)r*cols + c]*v[c];
-    s = wave_sum_f64(s);
-    if (lane == 0) store(r, s);
-  }
-}
-// store(c, sum_r M[r][c] v[r]): the product with the transpose.  Lanes own columns (coalesced rows), the waves split the rows, `red` (waves x 64) sums them.
-template <class F> __device__ __forceinline__ void ucg_matvec_cols(const float* __restrict__ M, const float* v, int rows, int cols, double* red, F store) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int c0 = 0; c0 < cols; c0 += 64) {
-    const int c = c0 + lane;
-    double s = 0.0;
-    if (c < cols) for (int r = wave; r < rows; r += kUcgGateWaves) s += (double)M[(size_t)r*cols + c]*(double)v[r];
-    __syncthreads();
-    red[wave*64 + lane] = s;
-    __syncthreads();
-    if (wave == 0 && c < cols) {
-      double t = 0.0;
-#pragma unroll
-      for (int w = 0; w < kUcgGateWaves; ++w) t += red[w*64 + lane];
-      store(c, t);
-    }
-  }
+  block_store_sum(s, red, partial + blockIdx.x);
 }
 
 // One block per sample: mean (B,C) from the per-block sums, hid (B,R) = relu(W1 mean), gate (B,C) = sigmoid(W2 hid).  The chain runs in fp64 (mean64, hid64:
 // the workspace); what the backward reads is stored in fp32.
-__global__ __launch_bounds__(kUcgGateBlock) void k_ucg_gate_fwd(const double* __restrict__ partial, UcgPartial pp, const float* __restrict__ w1,
-                                                               const float* __restrict__ w2, float* __restrict__ gate, float* __restrict__ mean,
-                                                               float* __restrict__ hid, double* mean64, double* hid64, int Ca, int Cs, int R, int hw) {
+__global__ __launch_bounds__(kGateBlock) void k_ucg_gate_fwd(const double* __restrict__ partial, GatePartial pp, const float* __restrict__ w1,
+                                                            const float* __restrict__ w2, float* __restrict__ gate, float* __restrict__ mean,
+                                                            float* __restrict__ hid, double* mean64, double* hid64, int Ca, int Cs, int R, int hw) {
   const int b = blockIdx.x, C = Ca + Cs;
   double* mb = mean64 + (size_t)b*C;
   double* hb = hid64 + (size_t)b*R;
-  for (int c = threadIdx.x; c < C; c += kUcgGateBlock) {
-    const double m = ucg_plane_sum(partial, pp, b, c, Ca, Cs)/(double)(c < Ca ? hw : 4*hw);
+  for (int c = threadIdx.x; c < C; c += kGateBlock) {
+    const double m = gate_plane_sum(partial, pp, b, c, Ca, Cs)/(double)(c < Ca ? hw : 4*hw);
     mb[c] = m; mean[(size_t)b*C + c] = (float)m;
   }
   __threadfence_block(); __syncthreads();
-  ucg_matvec_rows(w1, mb, R, C, [&](int r, double s) { const double t = fmax(s, 0.0); hb[r] = t; hid[(size_t)b*R + r] = (float)t; });
+  matvec_rows(w1, mb, R, C, [&](int r, double s) { const double t = fmax(s, 0.0); hb[r] = t; hid[(size_t)b*R + r] = (float)t; });
   __threadfence_block(); __syncthreads();
-  ucg_matvec_rows(w2, hb, C, R, [&](int c, double s) { gate[(size_t)b*C + c] = (float)(1.0/(1.0 + exp(-s))); });
+  matvec_rows(w2, hb, C, R, [&](int c, double s) { gate[(size_t)b*C + c] = (float)(1.0/(1.0 + exp(-s))); });
 }
 
+// (k_elu_up_cat_pad_fwd's source map with one source pointer: its blocks are four elements a thread, and the two-pointer prologue of a shared body cost
+// this kernel 18 instructions a block, 0.3 - 0.6 % of the decoder's forward.  tests/test_gpu_diffnet.py pins that the two maps stay one.)
 __global__ __launch_bounds__(kDecBlock) void k_ucg_apply_fwd(const float* __restrict__ a, const float* __restrict__ bias, const float* __restrict__ skip,
                                                              const float* __restrict__ gate, float* __restrict__ out, int Ca, int Cs, int h, int w, int act,
                                                              unsigned chunks) {
@@ -429,33 +308,9 @@ __global__ __launch_bounds__(kDecBlock) void k_ucg_apply_fwd(const float* __rest
   }
 }
 
-// G(r, q): the reflection-pad adjoint at the un-padded position (r, q) of an nr x nq plane whose padded gradient g has rows of W = nq + 2 floats
-__device__ __forceinline__ float pad_adj_at(const float* __restrict__ g, int r, int q, int nr, int nq, int W) {
-  if (!(r == 1 || r == nr - 2 || q == 1 || q == nq - 2)) return g[(r + 1)*W + q + 1];
-  SMD_PAD_ADJ_POS(r, nr, y0, y1, y2); SMD_PAD_ADJ_POS(q, nq, x0, x1, x2);       // rare: mirrored border cells
-  const int ys[3] = {y0, y1, y2}, xs[3] = {x0, x1, x2};
-  float acc = 0.f;
-#pragma unroll
-  for (int m = 0; m < 3; ++m) {
-    if (ys[m] < 0) continue;
-#pragma unroll
-    for (int n = 0; n < 3; ++n) if (xs[n] >= 0) acc += g[ys[m]*W + xs[n]];
-  }
-  return acc;
-}
-// the sum of G over the 2 x 2 children of the low-resolution pixel (i, j) of an h x w plane
-__device__ __forceinline__ float up_pad_adj_at(const float* __restrict__ g, int i, int j, int h, int w, int W) {
-  if (i > 0 && i < h - 1 && j > 0 && j < w - 1) {   // interior: the plain 2x2 block
-    const float* gp = g + (2*i + 1)*W + 2*j + 1;
-    return (gp[0] + gp[1]) + (gp[W] + gp[W + 1]);
-  }
-  return (pad_adj_at(g, 2*i, 2*j, 2*h, 2*w, W) + pad_adj_at(g, 2*i, 2*j + 1, 2*h, 2*w, W)) +
-         (pad_adj_at(g, 2*i + 1, 2*j, 2*h, 2*w, W) + pad_adj_at(g, 2*i + 1, 2*j + 1, 2*h, 2*w, W));
-}
-
 // partial[block] = the sum of G o src over a chunk of a plane (the a planes at low resolution: their 2 x 2 children share one src value)
 __global__ __launch_bounds__(kDecBlock) void k_ucg_reduce_bwd(const float* __restrict__ a, const float* __restrict__ bias, const float* __restrict__ skip,
-                                                              const float* __restrict__ g_out, int Ca, int Cs, int h, int w, int act, UcgPartial pp,
+                                                              const float* __restrict__ g_out, int Ca, int Cs, int h, int w, int act, GatePartial pp,
                                                               float* __restrict__ partial) {
   __shared__ float red[kDecBlock/64];
   const bool from_a = blockIdx.x < pp.na;
@@ -473,41 +328,39 @@ __global__ __launch_bounds__(kDecBlock) void k_ucg_reduce_bwd(const float* __res
   for (int k = 0; k < kDecPerThread; ++k) {
     const int idx = chunk*kDecChunk + k*kDecBlock + threadIdx.x;
     if (idx >= n) break;
-    if (from_a) { const int i = idx/w, j = idx - i*w; s = fmaf(up_pad_adj_at(g, i, j, h, w, W), glue_act(src[idx] + bc, av), s); }
+    if (from_a) { const int i = idx/w, j = idx - i*w; s = fmaf(up_pad_adj_at<false>(g, i, j, h, w, W), glue_act(src[idx] + bc, av), s); }
     else { const int r = idx/W2, q = idx - r*W2; s = fmaf(pad_adj_at(g, r, q, H2, W2, W), src[idx], s); }
   }
   block_store_sum(s, red, partial + blockIdx.x);
 }
 
-// One block per sample: dgate = sum G o src (from the per-block sums) -> dz2 = dgate gate (1 - gate) -> dhid = W2^T dz2 -> dz1 = dhid [hid > 0] ->
-// dmean = W1^T dz1, stored divided by the elements of the plane it was the mean of.  vec = dz2 (B,C), dmean (B,C), dz1 (B,R).
-__global__ __launch_bounds__(kUcgGateBlock) void k_ucg_gate_bwd(const float* __restrict__ partial, UcgPartial pp, const float* __restrict__ w1,
-                                                               const float* __restrict__ w2, const float* __restrict__ gate, const float* __restrict__ hid,
-                                                               float* vec, int B, int Ca, int Cs, int R, int hw) {
-  __shared__ double red[kUcgGateWaves*64];
-  const int b = blockIdx.x, C = Ca + Cs;
-  const float* gb = gate + (size_t)b*C;
-  const float* hb = hid + (size_t)b*R;
-  float* dz2 = vec + (size_t)b*C;
-  float* dmean = vec + ((size_t)B + b)*C;
-  float* dz1 = vec + (size_t)2*B*C + (size_t)b*R;
-  for (int c = threadIdx.x; c < C; c += kUcgGateBlock) {
+// ---------------------------------------------------------------------------------------------------------------- the backward of a two-layer gate
+// One block per sample: dgate (from the per-block sums) -> dz2 = dgate gate (1 - gate) -> dhid = W2^T dz2 -> dz1 = dhid [hid > 0] -> dmean = W1^T dz1,
+// stored divided by the elements of the plane it was the mean of.
+__global__ __launch_bounds__(kGateBlock) void k_gate_bwd(GateBwd g) {
+  __shared__ double red[kGateWaves*64];
+  const int b = blockIdx.x, C = g.Ca + g.Cs, Ca = g.Ca, R = g.R, hw = g.hw;
+  const float* gb = g.gate + (size_t)b*C;
+  const float* hb = g.hid + (size_t)b*R;
+  float* dz2 = g.dz2 + (size_t)b*C;
+  float* dz1 = g.dz1 + (size_t)b*R;
+  float* dmean = g.dmean + (size_t)b*C;
+  for (int c = threadIdx.x; c < C; c += kGateBlock) {
     const double gv = (double)gb[c];
-    dz2[c] = (float)(ucg_plane_sum(partial, pp, b, c, Ca, Cs)*gv*(1.0 - gv));
+    dz2[c] = (float)(gate_plane_sum(g.partial, g.pp, b, c, Ca, g.Cs)*gv*(1.0 - gv));
   }
   __threadfence_block(); __syncthreads();
-  ucg_matvec_cols(w2, dz2, C, R, red, [&](int r, double s) { dz1[r] = hb[r] > 0.f ? (float)s : 0.f; });
+  matvec_cols(g.w2, dz2, C, R, red, [&](int r, double s) { dz1[r] = hb[r] > 0.f ? (float)s : 0.f; });
   __threadfence_block(); __syncthreads();
-  ucg_matvec_cols(w1, dz1, R, C, red, [&](int c, double s) { dmean[c] = (float)(s/(double)(c < Ca ? hw : 4*hw)); });
+  matvec_cols(g.w1, dz1, R, C, red, [&](int c, double s) { dmean[c] = (float)(s/(double)(c < Ca ? hw : 4*hw)); });
 }
 
-// g_w1[r][c] = sum_b dz1[b][r] mean[b][c],  g_w2[c][r] = sum_b dz2[b][c] hid[b][r]: the samples in order.
-__global__ __launch_bounds__(256) void k_ucg_param_grad(const float* __restrict__ mean, const float* __restrict__ hid, const float* __restrict__ vec,
-                                                        float* __restrict__ g_w1, float* __restrict__ g_w2, int B, int C, int R) {
+// g_w1[r][c] = sum_b dz1[b][r] mean[b][c],  g_w2[c][r] = sum_b dz2[b][c] hid[b][r],  with biases g_b1 = sum_b dz1, g_b2 = sum_b dz2: the samples in order.
+__global__ __launch_bounds__(256) void k_gate_param_grad(const float* __restrict__ mean, const float* __restrict__ hid, const float* __restrict__ dz2,
+                                                         const float* __restrict__ dz1, float* __restrict__ g_w1, float* __restrict__ g_b1,
+                                                         float* __restrict__ g_w2, float* __restrict__ g_b2, int B, int C, int R) {
   const size_t idx = (size_t)blockIdx.x*256 + threadIdx.x;
   if (idx >= (size_t)C*R) return;
-  const float* dz2 = vec;
-  const float* dz1 = vec + (size_t)2*B*C;
   const int r1 = (int)(idx/C), c1 = (int)(idx - (size_t)r1*C), c2 = (int)(idx/R), r2 = (int)(idx - (size_t)c2*R);
   float t1 = 0.f, t2 = 0.f;
   for (int b = 0; b < B; ++b) {
@@ -515,6 +368,16 @@ __global__ __launch_bounds__(256) void k_ucg_param_grad(const float* __restrict_
     t2 = fmaf(dz2[(size_t)b*C + c2], hid[(size_t)b*R + r2], t2);
   }
   g_w1[idx] = t1; g_w2[idx] = t2;
+  if (!g_b1) return;
+  if (idx < (size_t)R) { float u = 0.f; for (int b = 0; b < B; ++b) u += dz1[(size_t)b*R + idx]; g_b1[idx] = u; }
+  if (idx < (size_t)C) { float u = 0.f; for (int b = 0; b < B; ++b) u += dz2[(size_t)b*C + idx]; g_b2[idx] = u; }
+}
+
+void launch_gate_bwd(const GateBwd& g, float* g_w1, float* g_b1, float* g_w2, float* g_b2, hipStream_t st) {
+  const int C = g.Ca + g.Cs;
+  hipLaunchKernelGGL(k_gate_bwd, dim3(g.B), dim3(kGateBlock), 0, st, g);
+  if (g_w1) hipLaunchKernelGGL(k_gate_param_grad, dim3((unsigned)(((size_t)C*g.R + 255)/256)), dim3(256), 0, st, g.mean, g.hid, g.dz2, g.dz1, g_w1, g_b1, g_w2, g_b2,
+                               g.B, C, g.R);
 }
 
 // g_a = act'(a + bias) (gate sum-of-children G + dmean) at low resolution; its per-block sums are the bias gradient's.  g_a may be NULL (g_bias alone).
@@ -534,7 +397,7 @@ __global__ __launch_bounds__(kDecBlock) void k_ucg_apply_bwd_a(const float* __re
     const int idx = chunk*kDecChunk + k*kDecBlock + threadIdx.x;
     if (idx >= h*w) break;
     const int i = idx/w, j = idx - i*w;
-    float gv = fmaf(gt, up_pad_adj_at(g, i, j, h, w, W), dm);
+    float gv = fmaf(gt, up_pad_adj_at<false>(g, i, j, h, w, W), dm);
     if (av) gv *= glue_act_grad(a[(size_t)plane*h*w + idx] + bc, av);
     if (g_a) g_a[(size_t)plane*h*w + idx] = gv;
     bsum += gv;
@@ -561,14 +424,14 @@ __global__ __launch_bounds__(kDecBlock) void k_ucg_apply_bwd_skip(const float* _
 
 hipError_t launch_up_cat_gate_pad_fwd(const UpCatGate& s, const float* a, const float* bias, const float* skip, const float* w1, const float* w2, float* out,
                                       float* gate, float* mean, float* hid, float* ws, hipStream_t st) {
-  const UcgPartial pp = ucg_partial(s, false);
+  const GatePartial pp = ucg_partial(s, false);
   const int C = s.Ca + s.Cs, hw = s.h*s.w;
   const unsigned blocks = pp.na + (unsigned)((size_t)s.B*s.Cs*pp.chs);
   double* partial = (double*)ws;
   double* mean64 = partial + ucg_partial_floats(s, false);
   double* hid64 = mean64 + (size_t)s.B*C;
   hipLaunchKernelGGL(k_ucg_pool, dim3(blocks), dim3(kDecBlock), 0, st, a, bias, skip, s.Ca, hw, s.act, pp, partial);
-  hipLaunchKernelGGL(k_ucg_gate_fwd, dim3(s.B), dim3(kUcgGateBlock), 0, st, partial, pp, w1, w2, gate, mean, hid, mean64, hid64, s.Ca, s.Cs, s.R, hw);
+  hipLaunchKernelGGL(k_ucg_gate_fwd, dim3(s.B), dim3(kGateBlock), 0, st, partial, pp, w1, w2, gate, mean, hid, mean64, hid64, s.Ca, s.Cs, s.R, hw);
   const unsigned chunks = ceil_div((2*s.h + 2)*(2*s.w + 2), kDecChunk);
   hipLaunchKernelGGL(k_ucg_apply_fwd, dim3((unsigned)((size_t)s.B*C*chunks)), dim3(kDecBlock), 0, st, a, bias, skip, gate, out, s.Ca, s.Cs, s.h, s.w, s.act, chunks);
   return hipGetLastError();
@@ -577,16 +440,15 @@ hipError_t launch_up_cat_gate_pad_fwd(const UpCatGate& s, const float* a, const 
 hipError_t launch_up_cat_gate_pad_bwd(const UpCatGate& s, const float* a, const float* bias, const float* skip, const float* w1, const float* w2,
                                       const float* gate, const float* mean, const float* hid, const float* g_out, float* g_a, float* g_skip, float* g_bias,
                                       float* g_w1, float* g_w2, float* ws, hipStream_t st) {
-  const UcgPartial pp = ucg_partial(s, true);
-  const int C = s.Ca + s.Cs, hw = s.h*s.w;
+  const GatePartial pp = ucg_partial(s, true);
+  const int C = s.Ca + s.Cs;
   float* partial = ws;
-  float* vec = partial + ucg_partial_floats(s, true);
+  float* vec = partial + ucg_partial_floats(s, true);       // dz2 (B,C), dmean (B,C), dz1 (B,R)
   float* bias_partial = vec + ucg_vec_floats(s);
-  const float* dmean = vec + (size_t)s.B*C;
+  float* dmean = vec + (size_t)s.B*C;
   const unsigned blocks = pp.na + (unsigned)((size_t)s.B*s.Cs*pp.chs);
   hipLaunchKernelGGL(k_ucg_reduce_bwd, dim3(blocks), dim3(kDecBlock), 0, st, a, bias, skip, g_out, s.Ca, s.Cs, s.h, s.w, s.act, pp, partial);
-  hipLaunchKernelGGL(k_ucg_gate_bwd, dim3(s.B), dim3(kUcgGateBlock), 0, st, partial, pp, w1, w2, gate, hid, vec, s.B, s.Ca, s.Cs, s.R, hw);
-  if (g_w1) hipLaunchKernelGGL(k_ucg_param_grad, dim3((unsigned)(((size_t)C*s.R + 255)/256)), dim3(256), 0, st, mean, hid, vec, g_w1, g_w2, s.B, C, s.R);
+  launch_gate_bwd(GateBwd{partial, w1, w2, gate, mean, hid, vec, vec + (size_t)2*s.B*C, dmean, pp, s.B, s.Ca, s.Cs, s.R, s.h*s.w}, g_w1, nullptr, g_w2, nullptr, st);
   if (g_a || g_bias) {
     hipLaunchKernelGGL(k_ucg_apply_bwd_a, dim3(pp.na), dim3(kDecBlock), 0, st, a, bias, g_out, gate, dmean, g_a, g_bias ? bias_partial : nullptr, s.Ca, s.Cs,
                        s.h, s.w, s.act, (unsigned)pp.cha);

@@ -18,8 +18,7 @@ __global__ __launch_bounds__(1024) void k_sum_partials(const float* __restrict__
     acc += ((double)a + (double)b) + ((double)c + (double)d);
   }
   for (; i < count; i += 1024) acc += (double)partial[i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  acc = wave_sum_f64(acc);
   if (lane == 0) red[wv] = acc;
   __syncthreads();
   if (threadIdx.x == 0) {

@@ -853,8 +853,7 @@ __device__ __forceinline__ void recon_main_reduce(const ReconMainArgs& a, MainTa
 #pragma unroll
     for (int q = 0; q < 16; q += 4) acc += ((v[q].x + v[q].y) + (v[q + 1].x + v[q + 1].y)) + ((v[q + 2].x + v[q + 2].y) + (v[q + 3].x + v[q + 3].y));   // fixed order
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  acc = wave_sum_f64(acc);
   if (lane == 0) {
     const float l_rec = (float)(acc*a.loss_scale);
     a.loss[0] = l_rec;

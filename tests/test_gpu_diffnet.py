@@ -98,6 +98,32 @@ def test_each_gradient_subset_alone_equals_the_full_backward(F, shape):
             else: assert p is None, f'operand {k} got a gradient nobody asked for (subset {sorted(need)})'
 
 
+@pytest.mark.parametrize('shape', [(2, 3, 2, 4, 5, 1), (1, 2, 1, 33, 35, 2)], ids=lambda s: 'x'.join(map(str, s)))
+def test_gated_and_monodepth_glue_share_one_index_map(F, shape):
+    """With w2 = 0 the gate is exactly 0.5 and its dmean exactly 0; with a > 0 and no bias ELU is the identity with derivative 1.  Then `up_cat_gate_pad` is
+    bit for bit half of `elu_up_cat_pad`: the output, g_skip everywhere, and g_a on the interior pixels 1..h-2, 1..w-2 (on a border pixel the Monodepth
+    kernel runs one accumulator through the four children and the gated kernel pairs them: two legitimate sum orders).  A scaling by 0.5 is exact, so any
+    difference is a different source index, pad-adjoint cell or sum order."""
+    B, Ca, Cs, h, w, R = shape
+    C = Ca + Cs
+    g = torch.Generator().manual_seed(5150 + sum(shape))
+    a = (0.25 + torch.rand(B, Ca, h, w, generator=g)).cuda()
+    skip = torch.randn(B, Cs, 2*h, 2*w, generator=g).cuda()
+    w1, w2 = torch.randn(R, C, generator=g).cuda(), torch.zeros(C, R).cuda()
+    gout = torch.randn(B, C, 2*h + 2, 2*w + 2, generator=g).cuda()
+    res = {}
+    for name in ('gated', 'monodepth'):
+        la, ls = a.clone().requires_grad_(True), skip.clone().requires_grad_(True)
+        out = F.up_cat_gate_pad(la, ls, w1, w2, None, None) if name == 'gated' else F.elu_up_cat_pad(la, ls)
+        out.backward(gout)
+        res[name] = (out.detach(), ls.grad, la.grad)
+    (o, gs, ga), (om, gsm, gam) = res['gated'], res['monodepth']
+    assert torch.equal(o, 0.5*om), 'output'
+    assert torch.equal(gs, 0.5*gsm), 'g_skip'
+    assert torch.equal(ga[:, :, 1:h - 1, 1:w - 1], 0.5*gam[:, :, 1:h - 1, 1:w - 1]), 'g_a on the interior'
+    assert torch.isfinite(ga).all() and ga.shape == gam.shape
+
+
 @pytest.mark.parametrize('bias', [True, False], ids=['bias', 'nobias'])
 @pytest.mark.parametrize('shape', [(1, 1, 2, 2), (2, 16, 5, 33), (1, 3, 7, 70)], ids=lambda s: 'x'.join(map(str, s)))
 def test_relu_pad_matches_fp64(F, shape, bias):
