@@ -815,19 +815,19 @@ static bool head_sizes_ok(int B, int C, int h, int w) {
 }
 size_t smd_conv3x3_head_workspace_bytes(int B, int C, int h, int w) {
   if (!head_sizes_ok(B, C, h, w)) return 0;
-  return align256(smd::conv_head_partials(B, C, h, w)*sizeof(float));
+  return align256(smd::conv_head_partials(B, C, 1, h, w)*sizeof(float));
 }
 int smd_conv3x3_head_fwd(const void* xp, const float* weight, const float* bias, float* y, int B, int C, int h, int w, int act, void* stream) {
   if (!xp || !weight || !y) return fail(SMD_E_INVALID, "null pointer");
   if (!head_sizes_ok(B, C, h, w) || (act & ~(1 | SMD_HEAD_X_BF16))) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d h=%d w=%d act=%d", B, C, h, w, act);
-  return check_launch(smd::launch_conv_head_fwd(xp, (act & SMD_HEAD_X_BF16) != 0, weight, bias, y, B, C, h, w, act & 1, (hipStream_t)stream), "conv3x3_head_fwd");
+  return check_launch(smd::launch_conv_head_fwd(xp, (act & SMD_HEAD_X_BF16) != 0, weight, bias, y, B, C, 1, h, w, act & 1, (hipStream_t)stream), "conv3x3_head_fwd");
 }
 int smd_conv3x3_head_bwd(const void* xp, const float* weight, const float* y, const float* g_y, void* g_xp, float* g_weight, float* g_bias,
                          void* workspace, size_t workspace_bytes, int B, int C, int h, int w, int act, void* stream) {
   if (!weight || !y || !g_y || (!g_xp && !g_weight) || (g_weight && (!xp || !workspace)) || (g_bias && !g_weight)) return fail(SMD_E_INVALID, "null pointer");
   if (!head_sizes_ok(B, C, h, w) || (act & ~(1 | SMD_HEAD_X_BF16))) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d h=%d w=%d act=%d", B, C, h, w, act);
   if (g_weight && workspace_bytes < smd_conv3x3_head_workspace_bytes(B, C, h, w)) return fail(SMD_E_WORKSPACE, "workspace too small");
-  return check_launch(smd::launch_conv_head_bwd(xp, (act & SMD_HEAD_X_BF16) != 0, weight, y, g_y, g_xp, g_weight, g_bias, (float*)workspace, B, C, h, w, act & 1, (hipStream_t)stream), "conv3x3_head_bwd");
+  return check_launch(smd::launch_conv_head_bwd(xp, (act & SMD_HEAD_X_BF16) != 0, weight, y, g_y, g_xp, g_weight, g_bias, (float*)workspace, B, C, 1, h, w, act & 1, (hipStream_t)stream), "conv3x3_head_bwd");
 }
 static bool headn_args_ok(int B, int C, int n, int h, int w, int act) {
   const int a = act & 3;
@@ -835,26 +835,26 @@ static bool headn_args_ok(int B, int C, int n, int h, int w, int act) {
 }
 size_t smd_conv3x3_headn_workspace_bytes(int B, int C, int n, int h, int w) {
   if (!headn_args_ok(B, C, n, h, w, 0)) return 0;
-  return align256(smd::conv_headn_partials(B, C, n, h, w)*sizeof(float));
+  return align256(smd::conv_head_partials(B, C, n, h, w)*sizeof(float));
 }
 int smd_conv3x3_headn_fwd(const void* xp, const float* weight, const float* bias, float* y, int B, int C, int n, int h, int w, int act, void* stream) {
   if (!xp || !weight || !y) return fail(SMD_E_INVALID, "null pointer");
   if (!headn_args_ok(B, C, n, h, w, act)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d n=%d h=%d w=%d act=%d (1 <= n <= 4)", B, C, n, h, w, act);
-  return check_launch(smd::launch_conv_headn_fwd(xp, (act & SMD_HEADN_X_BF16) != 0, weight, bias, y, B, C, n, h, w, act & 3, (hipStream_t)stream), "conv3x3_headn_fwd");
+  return check_launch(smd::launch_conv_head_fwd(xp, (act & SMD_HEADN_X_BF16) != 0, weight, bias, y, B, C, n, h, w, act & 3, (hipStream_t)stream), "conv3x3_headn_fwd");
 }
 int smd_conv3x3_headn_bwd_data(const float* weight, const float* y, const float* g_y, void* g_xp, int B, int C, int n, int h, int w, int act, void* stream) {
   if (!weight || !y || !g_y || !g_xp) return fail(SMD_E_INVALID, "null pointer");
   if (!headn_args_ok(B, C, n, h, w, act)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d n=%d h=%d w=%d act=%d (1 <= n <= 4)", B, C, n, h, w, act);
-  return check_launch(smd::launch_conv_headn_bwd(nullptr, (act & SMD_HEADN_X_BF16) != 0, weight, y, g_y, g_xp, nullptr, nullptr, nullptr, B, C, n, h, w, act & 3,
-                                                 (hipStream_t)stream), "conv3x3_headn_bwd_data");
+  return check_launch(smd::launch_conv_head_bwd(nullptr, (act & SMD_HEADN_X_BF16) != 0, weight, y, g_y, g_xp, nullptr, nullptr, nullptr, B, C, n, h, w, act & 3,
+                                                (hipStream_t)stream), "conv3x3_headn_bwd_data");
 }
 int smd_conv3x3_headn_bwd_wgt(const void* xp, const float* y, const float* g_y, float* g_weight, float* g_bias, void* workspace, size_t workspace_bytes,
                               int B, int C, int n, int h, int w, int act, void* stream) {
   if (!xp || !y || !g_y || !g_weight || !workspace) return fail(SMD_E_INVALID, "null pointer");
   if (!headn_args_ok(B, C, n, h, w, act)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d n=%d h=%d w=%d act=%d (1 <= n <= 4)", B, C, n, h, w, act);
   if (workspace_bytes < smd_conv3x3_headn_workspace_bytes(B, C, n, h, w)) return fail(SMD_E_WORKSPACE, "workspace too small");
-  return check_launch(smd::launch_conv_headn_bwd(xp, (act & SMD_HEADN_X_BF16) != 0, nullptr, y, g_y, nullptr, g_weight, g_bias, (float*)workspace, B, C, n, h, w, act & 3,
-                                                 (hipStream_t)stream), "conv3x3_headn_bwd_wgt");
+  return check_launch(smd::launch_conv_head_bwd(xp, (act & SMD_HEADN_X_BF16) != 0, nullptr, y, g_y, nullptr, g_weight, g_bias, (float*)workspace, B, C, n, h, w, act & 3,
+                                                (hipStream_t)stream), "conv3x3_headn_bwd_wgt");
 }
 
 // Predictive-mask post-process and regularisers (smd_masks.hip)

@@ -261,15 +261,11 @@ hipError_t launch_recon_reduce_bwd(const uint8_t* sel, const float* g_loss, floa
                                    const float* mask, float* g_mask, int n, int B, int h, int w, int flags, hipStream_t st);
 hipError_t launch_debug_lane_shift(float* out_left, float* out_right, hipStream_t st);
 hipError_t launch_stream_copy(const void* src, void* dst, size_t nbytes, int mode, hipStream_t st);
-size_t conv_head_partials(int B, int C, int h, int w);
-hipError_t launch_conv_head_fwd(const void* xp, int x_bf16, const float* wgt, const float* bias, float* y, int B, int C, int h, int w, int act, hipStream_t st);
+// smd_conv_head.hip: output heads with N = 1..4 channels (hipErrorInvalidValue otherwise); act 0 identity, 1 sigmoid, 2 relu
+size_t conv_head_partials(int B, int C, int N, int h, int w);
+hipError_t launch_conv_head_fwd(const void* xp, int x_bf16, const float* wgt, const float* bias, float* y, int B, int C, int N, int h, int w, int act, hipStream_t st);
 hipError_t launch_conv_head_bwd(const void* xp, int x_bf16, const float* wgt, const float* y, const float* gy, void* g_xp, float* g_w, float* g_bias, float* partial,
-                                int B, int C, int h, int w, int act, hipStream_t st);
-// smd_conv_headn.hip: heads with 1..4 output channels (the predictive-mask decoder); act 0 identity, 1 sigmoid, 2 relu
-size_t conv_headn_partials(int B, int C, int N, int h, int w);
-hipError_t launch_conv_headn_fwd(const void* xp, int x_bf16, const float* wgt, const float* bias, float* y, int B, int C, int N, int h, int w, int act, hipStream_t st);
-hipError_t launch_conv_headn_bwd(const void* xp, int x_bf16, const float* wgt, const float* y, const float* gy, void* g_xp, float* g_w, float* g_bias, float* partial,
-                                 int B, int C, int N, int h, int w, int act, hipStream_t st);
+                                int B, int C, int N, int h, int w, int act, hipStream_t st);
 // smd_masks.hip: multi-scale, multi-channel bilinear up-sampling into a scale-major stack, and the mean over scales of per-scale means
 hipError_t launch_upsample_stack_fwd(const ScaleSet& sc, int planes, int h, int w, float* out, hipStream_t st);
 hipError_t launch_upsample_stack_bwd(const ScaleSet& sc, int planes, int h, int w, const float* g_out, hipStream_t st);

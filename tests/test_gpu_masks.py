@@ -75,6 +75,30 @@ def test_conv3x3_headn_refusals(F):
     with pytest.raises(ValueError): F.conv3x3_head(xp, wt[:2].contiguous(), None, 'sigmoid')   # the one-channel entry keeps refusing wider weights
 
 
+# (B, C, h, w), the smallest that reach each path: C < 8 -> the unsplit forward of 4 rows per thread, two tile columns, ragged last row group and column;
+# the split forward of 2 rows, 22 row tiles -> 8 weight-gradient chunks with a short last one; the split forward of 1 row, even width (bf16: the dword reader);
+# the same with an odd width (bf16: the element reader) and the data gradient's channel groups capped by C
+@pytest.mark.parametrize('B,C,h,w', [(2, 4, 9, 70), (2, 8, 342, 130), (1, 16, 6, 8), (1, 8, 5, 7)])
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize('act', ['sigmoid', None])
+def test_conv3x3_head_and_headn_agree_bit_for_bit_on_one_channel(F, B, C, h, w, dtype, act):
+    """`conv3x3_head` and `conv3x3_headn` with a (1, C, 3, 3) weight run the same kernels: output, `g_xp`, `g_weight` and `g_bias` are equal bit for bit,
+    with and without bias, over an fp32 and a bf16 padded activation."""
+    gen = torch.Generator(device='cuda').manual_seed(B*1000 + C*10 + h + w)
+    xp, wt, bs = _headn_inputs(B, C, 1, h, w, act, gen)
+    xp = xp.to(dtype)
+    gy = torch.randn(B, 1, h, w, device='cuda', generator=gen)
+    for bias in (bs, None):
+        runs = []
+        for op in (F.conv3x3_head, F.conv3x3_headn):
+            L = [t.clone().requires_grad_(True) for t in ((xp, wt) if bias is None else (xp, wt, bias))]
+            y = op(L[0], L[1], None if bias is None else L[2], act)
+            y.backward(gy)
+            runs.append([y.detach()] + [t.grad for t in L])
+        assert runs[0][1].dtype == dtype
+        for nm, a, b in zip(('y', 'g_xp', 'g_weight', 'g_bias'), *runs): assert torch.equal(a, b), (nm, bias is not None, rel_to_max(a.double(), b.double()))
+
+
 @pytest.mark.parametrize('B,C,h,w', [(2, 16, 50, 70), (12, 16, 192, 640), (1, 64, 24, 80)])
 @pytest.mark.parametrize('act', ['sigmoid', 'relu'])
 def test_conv3x3_headn_bf16_activation(F, B, C, h, w, act):
