@@ -1064,7 +1064,7 @@ int smd_elu_up_cat_pad_bwd(const void* a, const float* bias, const void* g_out, 
 // BatchNorm (+ residual, + ReLU)
 size_t smd_bn_workspace_bytes(int N, int C, int HW) {
   if (N < 1 || C < 1 || HW < 1) return 0;
-  return align256(((size_t)C*smd::bn_chunks(N, HW)*2 + (size_t)C*3)*sizeof(float));
+  return align256(((size_t)C*smd::bn_chunks(N, HW)*3 + (size_t)C*3)*sizeof(float));   // forward: 3 floats per chunk (k_bn_stats); backward: 2
 }
 int smd_bn_fwd(const float* x, const float* residual, const float* gamma, const float* beta, float* running_mean, float* running_var,
                float momentum, float eps, int relu, float* y, float* save_mean, float* save_invstd, void* workspace, size_t workspace_bytes,

@@ -6,7 +6,7 @@
 // the MLP runs as 1x1 convolutions on the same Linear weights) leaves a norm whose reduction axis is strided by H*W:
 // one lane per pixel walks the channels, so every load/store is coalesced across the wave and nothing is transposed.
 // A block = 64 pixels x 4 waves that split the channels (deep stages have few pixels but many channels).
-//   forward : pass 1 sum / sum of squares over C (shifted by channel 0), pass 2 normalise + affine (second read from L2)
+//   forward : pass 1 mean over C, pass 2 sum of squared deviations from it, pass 3 normalise + affine (passes 2 and 3 read from L2)
 //   backward: dx kernel (pass 1 sum_c g*gamma and sum_c g*gamma*xhat, pass 2 dx) and, separately, d gamma / d beta as a
 //             BatchNorm-style per-channel reduction over the pixels (grid (chunks, C)) with an fp64 finalize.
 #include "smd_common.h"
@@ -41,17 +41,31 @@ __global__ __launch_bounds__(kLnBlock) void k_ln_cf_fwd(const float* __restrict_
   const bool ok = pix < npix;
   const size_t q = ok ? pix : 0, n = q/HW, p = q - n*HW;
   const float* __restrict__ xp = x + n*(size_t)C*HW + p;
-  const float shift = xp[0];
+  // Two passes for the statistics, so that they depend on no single channel: `m`, the plain mean, only has to be NEAR the mean (it is the shift of the
+  // second pass); then mean = m + r/C exactly, with r = sum(x - m) a rounding-sized correction, and var = sum((x - m)^2)/C - (r/C)^2.
+  float s = 0.f, unused = 0.f;
+  for (int c = wv; c < C; c += kLnWaves) s += xp[(size_t)c*HW];
+  combine_waves(s, unused, red);
+  const float m = s/(float)C;
+  __syncthreads();   // `red` is written again below
   float s1 = 0.f, s2 = 0.f;
-  for (int c = wv; c < C; c += kLnWaves) { const float d = xp[(size_t)c*HW] - shift; s1 += d; s2 = fmaf(d, d, s2); }
+  for (int c = wv; c < C; c += kLnWaves) { const float d = xp[(size_t)c*HW] - m; s1 += d; s2 = fmaf(d, d, s2); }
   combine_waves(s1, s2, red);
   const float m1 = s1/(float)C;
   const float var = fmaxf(s2/(float)C - m1*m1, 0.f);
-  const float mu = shift + m1, rs = rsqrtf(var + eps);
+  const float mu = m + m1, rs = rsqrtf(var + eps);
   if (!ok) return;
   if (wv == 0) { mean[pix] = mu; rstd[pix] = rs; }
   TY* __restrict__ yp = y + n*(size_t)C*HW + p;
   for (int c = wv; c < C; c += kLnWaves) st_from_float<TY>(yp, (size_t)c*HW, fmaf((xp[(size_t)c*HW] - mu)*rs, gamma[c], beta[c]));
+}
+
+// g*gamma as ONE rounded value in both passes of the dx kernel: fused into the subtraction of pass 2 (g*gamma - ...), the unrounded product would differ from
+// the rounded one that pass 1 summed, and at C = 1, where the sum IS that product, leave rstd*2^-24*g where dx is exactly 0.
+__device__ __forceinline__ float rounded_product(float a, float b) {
+  float p = a*b;
+  asm volatile("" : "+v"(p));   // (the value has to exist in a register: nothing is fused across this)
+  return p;
 }
 
 // dx: per pixel a = sum_c g*gamma, b = sum_c g*gamma*xhat;  dx = rstd*(g*gamma - (a + xhat*b)/C).
@@ -69,16 +83,16 @@ __global__ __launch_bounds__(kLnBlock) void k_ln_cf_bwd_dx(const float* __restri
   const float mu = mean[q], rs = rstd[q];
   float a = 0.f, b = 0.f;
   for (int c = wv; c < C; c += kLnWaves) {
-    const float g = ld_as_float<TG>(gp, (size_t)c*HW)*gamma[c];
+    const float g = rounded_product(ld_as_float<TG>(gp, (size_t)c*HW), gamma[c]);
     a += g; b = fmaf(g, (xp[(size_t)c*HW] - mu)*rs, b);
   }
   combine_waves(a, b, red);
   if (!ok) return;
-  const float rc = 1.f/(float)C;
+  const float rc = C == 1 ? 1.f : 1.f/(float)C;   // (C = 1: dx is exactly 0 only if this is exactly 1, which the fast division does not promise)
   float* __restrict__ dp = g_x + n*(size_t)C*HW + p;
   for (int c = wv; c < C; c += kLnWaves) {
     const float xh = (xp[(size_t)c*HW] - mu)*rs;
-    dp[(size_t)c*HW] = rs*(ld_as_float<TG>(gp, (size_t)c*HW)*gamma[c] - rc*(a + xh*b));
+    dp[(size_t)c*HW] = rs*(rounded_product(ld_as_float<TG>(gp, (size_t)c*HW), gamma[c]) - rc*(a + xh*b));
   }
 }
 

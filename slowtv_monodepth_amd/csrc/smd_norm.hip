@@ -4,7 +4,7 @@
 // element-wise ops around it were the largest non-convolution item of the step (MIOpen's spatial BN kernels launch one
 // workgroup per channel: 64 workgroups on a 256-CU device for the stem).
 //
-//   forward : stats sweep (shifted sums, many blocks per channel) -> apply sweep (each block combines the channel's partials in fp64)
+//   forward : stats sweep (per chunk: mean, then squared deviations from it; many blocks per channel) -> apply sweep (each block combines the chunks in fp64, Chan's formula)
 //   backward: reduce sweep (sum dz, sum dz*(x-mean))               -> apply sweep (same; block 0 of a channel writes g_gamma, g_beta)
 //   layers with N*HW <= 16384 (layer3/4 of the encoders): ONE launch per direction, one block per channel
 // where dz = g_y masked by (y > 0) when the ReLU is fused.  NCHW fp32; float4 path when HW % 4 == 0.
@@ -40,31 +40,80 @@ __device__ __forceinline__ void chunk_range(long long total, int chunks, int k, 
   lo = (long long)k*len; hi = lo + len < total ? lo + len : total;
 }
 
+// Statistics of a range in two passes, so that they depend on no single element: pass 1 sums the values (their mean `m` only has to be NEAR the mean: it is the
+// shift of pass 2), pass 2 sums r = sum(x - m) and q = sum((x - m)^2).  Then mean = m + r/n exactly and M2 = q - r*r/n, where r is a rounding-sized correction.
+// A thread keeps its first kBnKeep values in registers between the passes (a chunk of the stats sweep has no more: one read from memory); whatever a
+// longer range holds is read again (the upper half of the single-launch path, from L2, and chunks of more than kBnItemsPerBlock floats).
+constexpr int kBnKeep = kBnItemsPerBlock/kBnBlock;   // 32
+
+template <bool VEC, bool KEEP>
+__device__ __forceinline__ void range_stats(const float* __restrict__ x, int C, int HW, int c, long long lo, long long hi, float* red, float& m, float& r, float& q) {
+  constexpr int W = VEC ? 4 : 1, STEPS = KEEP ? kBnKeep/W : 0;
+  const long long stride = (long long)kBnBlock*W, first = lo + (long long)threadIdx.x*W;
+  float v[KEEP ? kBnKeep : 1];
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < STEPS; ++j) {
+    const long long i = first + j*stride;
+#pragma unroll
+    for (int e = 0; e < W; ++e) v[j*W + e] = 0.f;
+    if (i < hi) {
+      const int n = (int)(i/HW), p = (int)(i - (long long)n*HW);
+      const size_t off = ((size_t)n*C + c)*HW + p;
+      if (VEC) {
+        const f4 t = *(const f4*)(x + off);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { v[j*W + e] = t[e]; s += t[e]; }
+      } else { v[j] = x[off]; s += v[j]; }
+    }
+  }
+  for (long long i = first + STEPS*stride; i < hi; i += stride) {
+    const int n = (int)(i/HW), p = (int)(i - (long long)n*HW);
+    const size_t off = ((size_t)n*C + c)*HW + p;
+    if (VEC) {
+      const f4 t = *(const f4*)(x + off);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s += t[e];
+    } else s += x[off];
+  }
+  float tot, unused;
+  block_sum2(s, 0.f, red, tot, unused);
+  m = tot/(float)(hi - lo);
+  __syncthreads();   // `red` is written again below
+  float a = 0.f, b = 0.f;
+#pragma unroll
+  for (int j = 0; j < STEPS; ++j) {
+    if (first + j*stride < hi) {
+#pragma unroll
+      for (int e = 0; e < W; ++e) { const float d = v[j*W + e] - m; a += d; b = fmaf(d, d, b); }
+    }
+  }
+  for (long long i = first + STEPS*stride; i < hi; i += stride) {
+    const int n = (int)(i/HW), p = (int)(i - (long long)n*HW);
+    const size_t off = ((size_t)n*C + c)*HW + p;
+    if (VEC) {
+      const f4 t = *(const f4*)(x + off);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { const float d = t[e] - m; a += d; b = fmaf(d, d, b); }
+    } else { const float d = x[off] - m; a += d; b = fmaf(d, d, b); }
+  }
+  block_sum2(a, b, red, r, q);
+}
+
+// Stats sweep of the chunked path: per chunk (m, r/n, M2) with the chunk's mean = m + r/n.
 template <bool VEC>
 __global__ __launch_bounds__(kBnBlock) void k_bn_stats(const float* __restrict__ x, int N, int C, int HW, int chunks, float* __restrict__ partial) {
   __shared__ float red[2*kBnBlock/64];
   const int c = blockIdx.y, k = blockIdx.x;
-  const long long total = (long long)N*HW;
   long long lo, hi;
-  chunk_range(total, chunks, k, lo, hi);
-  const float shift = x[(size_t)c*HW];   // first element of the channel: sums of (x - shift) stay well conditioned
-  float s1 = 0.f, s2 = 0.f;
-  if (VEC) {
-    for (long long i = lo + (long long)threadIdx.x*4; i < hi; i += kBnBlock*4) {
-      const int n = (int)(i/HW), p = (int)(i - (long long)n*HW);
-      const f4 v = *(const f4*)(x + ((size_t)n*C + c)*HW + p);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { const float d = v[q] - shift; s1 += d; s2 = fmaf(d, d, s2); }
-    }
-  } else {
-    for (long long i = lo + threadIdx.x; i < hi; i += kBnBlock) {
-      const int n = (int)(i/HW), p = (int)(i - (long long)n*HW);
-      const float d = x[((size_t)n*C + c)*HW + p] - shift; s1 += d; s2 = fmaf(d, d, s2);
-    }
+  chunk_range((long long)N*HW, chunks, k, lo, hi);
+  float m = 0.f, r = 0.f, q = 0.f;
+  if (lo < hi) range_stats<VEC, true>(x, C, HW, c, lo, hi, red, m, r, q);   // (block-uniform)
+  if (threadIdx.x == 0) {
+    const float rn = lo < hi ? r/(float)(hi - lo) : 0.f;
+    float* out = partial + ((size_t)c*chunks + k)*3;
+    out[0] = m; out[1] = rn; out[2] = fmaxf(fmaf(-r, rn, q), 0.f);
   }
-  float r1, r2;
-  block_sum2(s1, s2, red, r1, r2);
-  if (threadIdx.x == 0) { partial[((size_t)c*chunks + k)*2] = r1; partial[((size_t)c*chunks + k)*2 + 1] = r2; }
 }
 
 // fp64 combine of a channel's partial pairs by the whole block (every block of the apply sweeps does this for itself:
@@ -75,6 +124,27 @@ __device__ __forceinline__ void combine_partials(const float* __restrict__ parti
   for (int off = 32; off > 0; off >>= 1) { a += __shfl_xor(a, off, 64); b += __shfl_xor(b, off, 64); }
   const int wv = threadIdx.x >> 6;
   __syncthreads();
+  if ((threadIdx.x & 63) == 0) { red[wv*2] = a; red[wv*2 + 1] = b; }
+  __syncthreads();
+  s1 = 0.0; s2 = 0.0;
+#pragma unroll
+  for (int k = 0; k < kBnBlock/64; ++k) { s1 += red[k*2]; s2 += red[k*2 + 1]; }
+}
+
+// Chan's combination of the stats sweep's chunks in fp64, about the mean of chunk 0 (`shift`): s1 = sum n_k (mean_k - shift), s2 = sum M2_k + n_k (mean_k - shift)^2,
+// i.e. the shifted sums of the whole channel that `finish_stats` takes.
+__device__ __forceinline__ void combine_chunk_stats(const float* __restrict__ partial, int c, int chunks, long long total, double* red, double& shift, double& s1, double& s2) {
+  const float* pc = partial + (size_t)c*chunks*3;
+  shift = (double)pc[0] + (double)pc[1];
+  double a = 0.0, b = 0.0;
+  for (int k = threadIdx.x; k < chunks; k += kBnBlock) {
+    long long lo, hi;
+    chunk_range(total, chunks, k, lo, hi);
+    const double n = hi > lo ? (double)(hi - lo) : 0.0, d = ((double)pc[k*3] + (double)pc[k*3 + 1]) - shift;
+    a += n*d; b += (double)pc[k*3 + 2] + n*d*d;
+  }
+  for (int off = 32; off > 0; off >>= 1) { a += __shfl_xor(a, off, 64); b += __shfl_xor(b, off, 64); }
+  const int wv = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) { red[wv*2] = a; red[wv*2 + 1] = b; }
   __syncthreads();
   s1 = 0.0; s2 = 0.0;
@@ -97,9 +167,11 @@ __device__ __forceinline__ BnStat finish_stats(double s1, double s2, double shif
   return {(float)mean, (float)invstd};
 }
 
+// y = (x - mean)*sc + beta [+ residual] [ReLU].  The mean comes off x BEFORE the scale: folded into the offset (x*sc + (beta - mean*sc)) the two large terms
+// cancel after the offset was rounded, which costs |mean|/sigma ulps of y.
 template <bool VEC>
 __device__ __forceinline__ void apply_range(const float* __restrict__ x, const float* __restrict__ residual, float* __restrict__ y, int C, int HW, int c,
-                                            long long lo, long long hi, float sc, float sh, int relu) {
+                                            long long lo, long long hi, float mean, float sc, float beta, int relu) {
   constexpr int W = VEC ? 4 : 1;
   for (long long i = lo + (long long)threadIdx.x*W; i < hi; i += kBnBlock*W) {
     const int n = (int)(i/HW), p = (int)(i - (long long)n*HW);
@@ -108,7 +180,7 @@ __device__ __forceinline__ void apply_range(const float* __restrict__ x, const f
       const f4 v = *(const f4*)(x + off);
       f4 o;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) o[q] = fmaf(v[q], sc, sh);
+      for (int q = 0; q < 4; ++q) o[q] = fmaf(v[q] - mean, sc, beta);
       if (residual) { const f4 r = *(const f4*)(residual + off); o += r; }
       if (relu) {
 #pragma unroll
@@ -116,7 +188,7 @@ __device__ __forceinline__ void apply_range(const float* __restrict__ x, const f
       }
       *(f4*)(y + off) = o;
     } else {
-      float o = fmaf(x[off], sc, sh);
+      float o = fmaf(x[off] - mean, sc, beta);
       if (residual) o += residual[off];
       y[off] = relu ? fmaxf(o, 0.f) : o;
     }
@@ -131,17 +203,15 @@ __global__ __launch_bounds__(kBnBlock) void k_bn_apply(const float* __restrict__
                                                        float* __restrict__ save_mean, float* __restrict__ save_invstd, float* __restrict__ y) {
   __shared__ double red[2*kBnBlock/64];
   const int c = blockIdx.y, k = blockIdx.x;
-  double s1, s2;
-  combine_partials(partial, c, chunks, red, s1, s2);
-  const BnStat st = finish_stats(s1, s2, (double)x[(size_t)c*HW], N, HW, momentum, eps, c, k == 0 && threadIdx.x == 0, running_mean, running_var,
-                                 save_mean, save_invstd);
-  const float sc = gamma[c]*st.invstd, sh = fmaf(-st.mean, sc, beta[c]);
+  double shift, s1, s2;
+  combine_chunk_stats(partial, c, chunks, (long long)N*HW, red, shift, s1, s2);
+  const BnStat st = finish_stats(s1, s2, shift, N, HW, momentum, eps, c, k == 0 && threadIdx.x == 0, running_mean, running_var, save_mean, save_invstd);
   long long lo, hi;
   chunk_range((long long)N*HW, chunks, k, lo, hi);
-  apply_range<VEC>(x, residual, y, C, HW, c, lo, hi, sc, sh, relu);
+  apply_range<VEC>(x, residual, y, C, HW, c, lo, hi, st.mean, gamma[c]*st.invstd, beta[c], relu);
 }
 
-// Single-launch path for small channels (N*HW <= kBnSmall): one block per channel does stats, finalize and apply (second read from L2).
+// Single-launch path for small channels (N*HW <= kBnSmall): one block per channel does stats, finalize and apply (later reads from L2).
 template <bool VEC>
 __global__ __launch_bounds__(kBnBlock) void k_bn_fwd_small(const float* __restrict__ x, const float* __restrict__ residual, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, int N, int C, int HW, float momentum, float eps, int relu,
@@ -150,24 +220,10 @@ __global__ __launch_bounds__(kBnBlock) void k_bn_fwd_small(const float* __restri
   __shared__ float red[2*kBnBlock/64];
   const int c = blockIdx.x;
   const long long total = (long long)N*HW;
-  const float shift = x[(size_t)c*HW];
-  constexpr int W = VEC ? 4 : 1;
-  float s1 = 0.f, s2 = 0.f;
-  for (long long i = (long long)threadIdx.x*W; i < total; i += kBnBlock*W) {
-    const int n = (int)(i/HW), p = (int)(i - (long long)n*HW);
-    const size_t off = ((size_t)n*C + c)*HW + p;
-    if (VEC) {
-      const f4 v = *(const f4*)(x + off);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { const float d = v[q] - shift; s1 += d; s2 = fmaf(d, d, s2); }
-    } else { const float d = x[off] - shift; s1 += d; s2 = fmaf(d, d, s2); }
-  }
-  float r1, r2;
-  block_sum2(s1, s2, red, r1, r2);
-  const BnStat st = finish_stats((double)r1, (double)r2, (double)shift, N, HW, momentum, eps, c, threadIdx.x == 0, running_mean, running_var,
-                                 save_mean, save_invstd);
-  const float sc = gamma[c]*st.invstd, sh = fmaf(-st.mean, sc, beta[c]);
-  apply_range<VEC>(x, residual, y, C, HW, c, 0, total, sc, sh, relu);
+  float m, r, q;
+  range_stats<VEC, true>(x, C, HW, c, 0, total, red, m, r, q);   // (layer3/4 of the encoders hold <= kBnItemsPerBlock values per channel: nothing is read twice for the statistics)
+  const BnStat st = finish_stats((double)r, (double)q, (double)m, N, HW, momentum, eps, c, threadIdx.x == 0, running_mean, running_var, save_mean, save_invstd);
+  apply_range<VEC>(x, residual, y, C, HW, c, 0, total, st.mean, gamma[c]*st.invstd, beta[c], relu);
 }
 
 template <bool VEC>
@@ -329,7 +385,7 @@ __global__ __launch_bounds__(256) void k_maxpool_fwd(const float* __restrict__ x
     const int o = chunk*1024 + k*256 + threadIdx.x;
     if (o >= Ho*Wo) break;
     const int oh = o/Wo, ow = o - oh*Wo;
-    float best = -INFINITY; int bi = 0;
+    float best = -INFINITY; int bi = -1;   // no tap yet: a window of nothing but -inf selects its first VALID tap (as ATen), never one in the padding
 #pragma unroll
     for (int dh = 0; dh < 3; ++dh) {
       const int h = 2*oh - 1 + dh;
@@ -339,7 +395,7 @@ __global__ __launch_bounds__(256) void k_maxpool_fwd(const float* __restrict__ x
         const int w = 2*ow - 1 + dw;
         if (w < 0 || w >= W) continue;
         const float v = xp[h*W + w];
-        if (v > best || v != v) { best = v; bi = dh*3 + dw; }
+        if (v > best || v != v || bi < 0) { best = v; bi = dh*3 + dw; }
       }
     }
     y[(size_t)plane*Ho*Wo + o] = best; idx[(size_t)plane*Ho*Wo + o] = (uint8_t)bi;
