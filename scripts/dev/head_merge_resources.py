@@ -18,7 +18,9 @@ FLAGS = '-O3 -std=c++17 -fPIC -fno-slp-vectorize --offload-arch=gfx950 --cuda-de
 BYTES = {'ubyte': 1, 'sbyte': 1, 'ushort': 2, 'sshort': 2, 'short': 2, 'byte': 1, 'dword': 4, 'dwordx2': 8, 'dwordx3': 12, 'dwordx4': 16}
 
 
-def kernels(csrc, files):
+def kernels(csrc, files, keep=lambda sym: 'k_head' in sym):
+    """{demangled kernel: (vgpr, sgpr, scratch, lds, occupancy, 'loads/bytes', 'stores/bytes', vmcnt waits, instructions, barriers)} of the kernels of
+    `files` whose mangled name `keep` accepts."""
     out = {}
     for f in files:
         if not os.path.exists(os.path.join(csrc, f)):
@@ -30,19 +32,19 @@ def kernels(csrc, files):
                 for m in re.finditer(r'- \.agpr_count:.*?\.name:\s+(\S+).*?\.wavefront_size', text, re.S)}
         for m in re.finditer(r'^(_ZN3smd\w+):[^\n]*\n(.*?)^\.Lfunc_end', text, re.S | re.M):
             sym, body = m.group(1), m.group(2)
-            if 'k_head' not in sym:
+            if sym not in meta or not keep(sym):
                 continue
             name = subprocess.check_output(['c++filt', sym], text=True).strip()
             name = re.sub(r'^void smd::|\(.*$', '', name).replace('__hip_bfloat16', 'bf16')
             insts = [l.split()[0] for l in body.split('\n') if re.match(r'^\s+[a-z]\w+', l) and not l.lstrip().startswith(('.', ';'))]
             ld = [i for i in insts if re.match(r'(global|flat|buffer)_load', i)]
             st = [i for i in insts if re.match(r'(global|flat|buffer)_store', i)]
-            nb = lambda v: sum(BYTES[i.rsplit('_', 1)[1]] for i in v)
+            nb = lambda v: sum(next(BYTES[t] for t in i.split('_')[2:] if t in BYTES) for i in v)   # (global_load_short_d16_hi: the size is not last)
             occ = re.search(r'; Occupancy: (\d+)', text[m.end():])
             k = meta[sym]
             out[name] = (int(k['vgpr_count']), int(k['sgpr_count']), int(k['private_segment_fixed_size']), int(k['group_segment_fixed_size']), int(occ.group(1)),
                          '%d/%d' % (len(ld), nb(ld)), '%d/%d' % (len(st), nb(st)),
-                         sum(1 for l in body.split('\n') if 's_waitcnt' in l and 'vmcnt' in l), len(insts))
+                         sum(1 for l in body.split('\n') if 's_waitcnt' in l and 'vmcnt' in l), len(insts), insts.count('s_barrier'))
     return out
 
 
@@ -67,7 +69,7 @@ def main():
     print(head % 'parent kernel', ' |', head % 'successor')
     order = lambda n: (not n.startswith('k_head_fwd') and not n.startswith('k_headn_fwd'), 'data' not in n and 'fwd' not in n, 'finalize' in n, 'headn' in n, n)
     for name in sorted(parent, key=order):
-        p, s = parent[name], this[successor(name)]
+        p, s = parent[name][:9], this[successor(name)][:9]
         print(fmt % ((name,) + p), ' |', fmt % ((successor(name),) + s))
         if p[5].split('/')[0] != s[5].split('/')[0] or p[6].split('/')[0] != s[6].split('/')[0]:
             print('    ^ load/store count differs')

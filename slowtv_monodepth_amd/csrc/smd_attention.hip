@@ -261,10 +261,7 @@ __global__ __launch_bounds__(kSeBlock) void k_se_pool(const float* __restrict__ 
   } else {
     for (int i = lo + (int)threadIdx.x; i < hi; i += kSeBlock) s += BWD ? xp[i]*gp[i] : xp[i];
   }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  block_store_sum<Waves::Pairwise, kSeBlock/64>(s, red, partial + blockIdx.x);
 }
 
 __device__ __forceinline__ float sigmoidf(double z) { return (float)(1.0/(1.0 + exp(-z))); }

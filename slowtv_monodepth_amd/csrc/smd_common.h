@@ -21,6 +21,7 @@
 #endif
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include <hip/hip_bf16.h>
 
@@ -100,6 +101,71 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
+__device__ __forceinline__ double wave_sum(double v) { return wave_sum_f64(v); }
+
+// ---------------------------------------------------------------------------------------------
+// Block sums (T: float | double): the lanes of a wave by butterfly, lane 0 of each wave to `red`, ONE barrier, then the NW waves' values in the order the call
+// names.  A sum is bit-reproducible only in its order, and both orders are in use:
+//   Waves::Sequential   ((w0 + w1) + w2) + ...          Waves::Pairwise   (w0 + w1) + (w2 + w3)      (NW = 4)
+// `red` holds NW values per summed quantity (wave w, quantity k at red[w*K + k]).  A kernel that writes `red` a second time places the __syncthreads() between
+// the two uses itself: nothing here adds a barrier a kernel does not need.  (Sequential starts from w0, not from +0: the two differ only where every wave's
+// sum is -0, which a per-thread accumulator that started at +0 never is.)
+// Not members of this family, because their orders are other algorithms and nothing would be shared: the LDS trees of smd_regression.hip (`block_reduce`) and
+// smd_ddv.hip, the 16-lane segmented butterfly and the per-lane `combine_waves` of smd_attention.hip / smd_layernorm.hip, smd_metrics.hip, and the in-launch
+// arrival-counter reductions of the loss kernels and smd_smooth_dev.h.
+// ---------------------------------------------------------------------------------------------
+enum class Waves { Sequential, Pairwise };
+
+// the sum over the waves of quantity k (of K per wave) in `red`
+template <Waves ORDER, int NW, typename T> __device__ __forceinline__ T sum_waves(const T* red, int K = 1, int k = 0) {
+  if constexpr (ORDER == Waves::Pairwise) {
+    static_assert(NW == 4, "Pairwise is (w0 + w1) + (w2 + w3)");
+    return (red[k] + red[K + k]) + (red[2*K + k] + red[3*K + k]);
+  } else {
+    T t = red[k];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) t += red[w*K + k];
+    return t;
+  }
+}
+// the first half: every wave's sums of the K values of a thread to red[wave*stride + k], and the barrier
+// (a pair's two butterflies run side by side and leave with one store: one after the other they were 0.4 us of k_bn_apply's 38.  Longer lists go value by
+// value: k_dwconv7_wrw's 50 sums held at once cost it 27 VGPRs and two waves of occupancy.)
+template <int K, typename T> __device__ __forceinline__ void stage_wave_sums(const T (&v)[K], T* red, int stride = K) {
+  T* mine = red + (threadIdx.x >> 6)*stride;
+  if constexpr (K == 2) {
+    const T a = wave_sum(v[0]), b = wave_sum(v[1]);
+    if ((threadIdx.x & 63) == 0) { mine[0] = a; mine[1] = b; }
+  } else {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const T t = wave_sum(v[k]);
+      if ((threadIdx.x & 63) == 0) mine[k] = t;
+    }
+  }
+  __syncthreads();
+}
+// every thread gets the block's sum of v
+template <Waves ORDER, int NW, typename T> __device__ __forceinline__ T block_sum(T v, T* red) {
+  const T a[1] = {v};
+  stage_wave_sums(a, red);
+  return sum_waves<ORDER, NW>(red);
+}
+// ... of a pair, in place (red: 2 NW values)
+template <Waves ORDER, int NW, typename T> __device__ __forceinline__ void block_sum2(T& a, T& b, T* red) {
+  const T v[2] = {a, b};
+  stage_wave_sums(v, red);
+  a = sum_waves<ORDER, NW>(red, 2, 0); b = sum_waves<ORDER, NW>(red, 2, 1);
+}
+// thread 0 stores the block's sum of v
+template <Waves ORDER, int NW, typename T> __device__ __forceinline__ void block_store_sum(T v, T* red, T* dst) {
+  const T a[1] = {v};
+  stage_wave_sums(a, red);
+  if (threadIdx.x == 0) *dst = sum_waves<ORDER, NW>(red);
+}
+
+// f(std::true_type | std::false_type): one spelling of a launch for both values of a kernel's template flag
+template <class F> static inline void for_bool(bool b, F f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
 
 // ---------------------------------------------------------------------------------------------
 // Per-(support, sample) camera constants, folded so that a pixel costs 6 FMAs + 1 rcp + 2 mul:

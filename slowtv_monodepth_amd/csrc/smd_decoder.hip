@@ -63,7 +63,7 @@ __global__ __launch_bounds__(kDecBlock) void k_elu_pad_bwd(const TA* __restrict_
     const float gv = act ? acc*glue_act_grad(ld_as_float<TA>(x, (size_t)plane*h*w + idx) + bc, act) : acc;
     st_from_float<TA>(g_x, (size_t)plane*h*w + idx, gv); bsum += gv;
   }
-  if (bias_partial) block_store_sum(bsum, red, bias_partial + blockIdx.x);
+  if (bias_partial) block_store_sum<Waves::Sequential, kDecBlock/64>(bsum, red, bias_partial + blockIdx.x);
 }
 
 template <typename TA, typename TS, typename TO>
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(kDecBlock) void k_elu_up_cat_pad_bwd_a(const TA* __
     const float gv = up_pad_adj_at<true>(g, i, j, h, w, W)*elu1_grad(ld_as_float<TA>(a, (size_t)plane*h*w + idx) + bc);   // <true>: this kernel's border order
     st_from_float<TA>(g_a, (size_t)plane*h*w + idx, gv); bsum += gv;
   }
-  if (bias_partial) block_store_sum(bsum, red, bias_partial + blockIdx.x);
+  if (bias_partial) block_store_sum<Waves::Sequential, kDecBlock/64>(bsum, red, bias_partial + blockIdx.x);
 }
 
 // Adjoint w.r.t. the skip tensor (full resolution): plain reflection-pad adjoint of its channel slice.
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(kDecBlock) void k_ucg_pool(const float* __restrict_
   } else {
     for (int i = lo + (int)threadIdx.x; i < hi; i += kDecBlock) s += term(p[i]);
   }
-  block_store_sum(s, red, partial + blockIdx.x);
+  block_store_sum<Waves::Sequential, kDecBlock/64>(s, red, partial + blockIdx.x);
 }
 
 // One block per sample: mean (B,C) from the per-block sums, hid (B,R) = relu(W1 mean), gate (B,C) = sigmoid(W2 hid).  The chain runs in fp64 (mean64, hid64:
@@ -331,7 +331,7 @@ __global__ __launch_bounds__(kDecBlock) void k_ucg_reduce_bwd(const float* __res
     if (from_a) { const int i = idx/w, j = idx - i*w; s = fmaf(up_pad_adj_at<false>(g, i, j, h, w, W), glue_act(src[idx] + bc, av), s); }
     else { const int r = idx/W2, q = idx - r*W2; s = fmaf(pad_adj_at(g, r, q, H2, W2, W), src[idx], s); }
   }
-  block_store_sum(s, red, partial + blockIdx.x);
+  block_store_sum<Waves::Sequential, kDecBlock/64>(s, red, partial + blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the backward of a two-layer gate
@@ -402,7 +402,7 @@ __global__ __launch_bounds__(kDecBlock) void k_ucg_apply_bwd_a(const float* __re
     if (g_a) g_a[(size_t)plane*h*w + idx] = gv;
     bsum += gv;
   }
-  if (bias_partial) block_store_sum(bsum, red, bias_partial + blockIdx.x);
+  if (bias_partial) block_store_sum<Waves::Sequential, kDecBlock/64>(bsum, red, bias_partial + blockIdx.x);
 }
 
 // g_skip = gate G + dmean at full resolution

@@ -104,14 +104,8 @@ __global__ __launch_bounds__(256) void k_dwconv7_wrw(const float* __restrict__ x
       }
     }
   }
-  const int wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 50; ++k) {
-    const float t = wave_sum(acc[k]);
-    if ((threadIdx.x & 63) == 0) red[wv][k] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < 50) partial[((size_t)c*tiles + tile)*50 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  stage_wave_sums(acc, &red[0][0], 52);
+  if (threadIdx.x < 50) partial[((size_t)c*tiles + tile)*50 + threadIdx.x] = sum_waves<Waves::Pairwise, 4>(&red[0][0], 52, threadIdx.x);
 }
 
 __global__ __launch_bounds__(64) void k_dwconv7_wrw_finalize(const float* __restrict__ partial, int tiles, float* __restrict__ gw, float* __restrict__ gb) {

@@ -1,7 +1,7 @@
 // smd_glue_dev.h — the stages the decoder glue kernels (smd_decoder.hip) and the squeeze-excite gate (smd_attention.hip) are assembled from, each written
-// once: the activations, the reflection-pad adjoint (alone and under a nearest x2 up-sampling), the block reductions, the chunking of a pooled plane, the
-// matrix-vector pair of a two-layer gate, and the gate's backward (one kernel for both gates, defined in smd_decoder.hip).
-// Every sum here has a fixed order; a kernel that needs another order says so where it calls.
+// once: the activations, the reflection-pad adjoint (alone and under a nearest x2 up-sampling), the chunking of a pooled plane, the matrix-vector pair of a
+// two-layer gate, and the gate's backward (one kernel for both gates, defined in smd_decoder.hip).  The block reductions are the library's one family
+// (smd_common.h: block_store_sum<Waves::...>); every sum has a fixed order, named where it is called.
 #pragma once
 #include "smd_common.h"
 #include "smd_kernels.h"
@@ -19,15 +19,6 @@ enum { kActNone = 0, kActElu = 1, kActRelu = 2 };
 __device__ __forceinline__ float glue_act(float x, int act) { return act == kActElu ? elu1(x) : (act == kActRelu ? fmaxf(x, 0.f) : x); }
 __device__ __forceinline__ float glue_act_grad(float x, int act) { return act == kActElu ? elu1_grad(x) : (act == kActRelu ? (x > 0.f ? 1.f : 0.f) : 1.f); }
 __device__ __forceinline__ int unpad_reflect(int p, int n) { const int r = p - 1; return r < 0 ? -r : (r >= n ? 2*(n - 1) - r : r); }
-
-// ---------------------------------------------------------------------------------------------------------------- block reductions
-// *dst = the block's sum of v (kDecBlock threads): the lanes of a wave by butterfly, then the waves in order from 0.  T: float | double.
-template <typename T> __device__ __forceinline__ void block_store_sum(T v, T* red, T* dst) {
-  if constexpr (sizeof(T) == sizeof(double)) v = wave_sum_f64(v); else v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) { T t = 0; for (int k = 0; k < kDecBlock/64; ++k) t += red[k]; *dst = t; }
-}
 
 // ---------------------------------------------------------------------------------------------------------------- the reflection-pad adjoint
 // acc += g over the padded cells that read the un-padded position (r, q) of an nr x nq plane (g: the padded plane, rows of W = nq + 2): the cell

@@ -8,9 +8,11 @@
 // A block = 64 pixels x 4 waves that split the channels (deep stages have few pixels but many channels).
 //   forward : pass 1 mean over C, pass 2 sum of squared deviations from it, pass 3 normalise + affine (passes 2 and 3 read from L2)
 //   backward: dx kernel (pass 1 sum_c g*gamma and sum_c g*gamma*xhat, pass 2 dx) and, separately, d gamma / d beta as a
-//             BatchNorm-style per-channel reduction over the pixels (grid (chunks, C)) with an fp64 finalize.
+//             BatchNorm-style per-channel reduction over the pixels (grid (chunks, C)) with an fp64 finalize: the sweep is BatchNorm's
+//             `channel_sweep` (smd_norm_dev.h), the block sum `stage_wave_sums` + `sum_waves<Waves::Pairwise>` (smd_common.h).
 #include "smd_common.h"
 #include "smd_kernels.h"
+#include "smd_norm_dev.h"
 
 namespace smd {
 
@@ -97,25 +99,21 @@ __global__ __launch_bounds__(kLnBlock) void k_ln_cf_bwd_dx(const float* __restri
 }
 
 // d gamma / d beta: per channel sums over all pixels of g*xhat and g — the BatchNorm-style reduction (grid (chunks, C)).
+// The sweep is BatchNorm's (smd_norm_dev.h), one float per step; the chunks are this kernel's own: equal parts that are NOT rounded up to a multiple of 4.
 template <typename TG>
-__global__ __launch_bounds__(256) void k_ln_cf_bwd_wb(const float* __restrict__ x, const TG* __restrict__ g_y, const float* __restrict__ mean,
-                                                      const float* __restrict__ rstd, int N, int C, int HW, int chunks, float* __restrict__ partial) {
-  __shared__ float red[8];
+__global__ __launch_bounds__(kBnBlock) void k_ln_cf_bwd_wb(const float* __restrict__ x, const TG* __restrict__ g_y, const float* __restrict__ mean,
+                                                           const float* __restrict__ rstd, int N, int C, int HW, int chunks, float* __restrict__ partial) {
+  __shared__ float red[2*kBnBlock/64];
   const int c = blockIdx.y, k = blockIdx.x;
   const long long total = (long long)N*HW;
   const long long len = (total + chunks - 1)/chunks, lo = (long long)k*len, hi = lo + len < total ? lo + len : total;
-  float s1 = 0.f, s2 = 0.f;
-  for (long long i = lo + threadIdx.x; i < hi; i += 256) {
-    const long long n = i/HW, p = i - n*HW;
-    const size_t off = ((size_t)n*C + c)*HW + p;
+  float s[2] = {0.f, 0.f};
+  channel_sweep<false>(lo, hi, C, HW, c, [&](size_t off, long long i) {
     const float g = ld_as_float<TG>(g_y, off);
-    s1 = fmaf(g, (x[off] - mean[i])*rstd[i], s1); s2 += g;
-  }
-  s1 = wave_sum(s1); s2 = wave_sum(s2);
-  const int wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[wv*2] = s1; red[wv*2 + 1] = s2; }
-  __syncthreads();
-  if (threadIdx.x < 2) partial[((size_t)c*chunks + k)*2 + threadIdx.x] = (red[threadIdx.x] + red[2 + threadIdx.x]) + (red[4 + threadIdx.x] + red[6 + threadIdx.x]);
+    s[0] = fmaf(g, (x[off] - mean[i])*rstd[i], s[0]); s[1] += g;
+  });
+  stage_wave_sums(s, red);
+  if (threadIdx.x < 2) partial[((size_t)c*chunks + k)*2 + threadIdx.x] = sum_waves<Waves::Pairwise, 4>(red, 2, threadIdx.x);
 }
 
 __global__ __launch_bounds__(64) void k_ln_cf_bwd_finalize(const float* __restrict__ partial, int chunks, int C, float* __restrict__ g_gamma, float* __restrict__ g_beta) {
@@ -135,8 +133,10 @@ hipError_t launch_ln_cf_fwd(const float* x, const float* gamma, const float* bet
                             float eps, hipStream_t st) {
   const size_t npix = (size_t)N*HW;
   const dim3 grid((unsigned)((npix + 63)/64));
-  if (y_bf16) hipLaunchKernelGGL(k_ln_cf_fwd<bf16>, grid, dim3(kLnBlock), 0, st, x, gamma, beta, (bf16*)y, mean, rstd, C, HW, npix, eps);
-  else hipLaunchKernelGGL(k_ln_cf_fwd<float>, grid, dim3(kLnBlock), 0, st, x, gamma, beta, (float*)y, mean, rstd, C, HW, npix, eps);
+  for_bool(y_bf16 != 0, [&](auto is_bf16) {
+    using TY = std::conditional_t<decltype(is_bf16)::value, bf16, float>;
+    hipLaunchKernelGGL(k_ln_cf_fwd<TY>, grid, dim3(kLnBlock), 0, st, x, gamma, beta, (TY*)y, mean, rstd, C, HW, npix, eps);
+  });
   return hipGetLastError();
 }
 hipError_t launch_ln_cf_bwd(const float* x, const void* g_y, int g_bf16, const float* gamma, const float* mean, const float* rstd, float* g_x, float* g_gamma,
@@ -144,13 +144,11 @@ hipError_t launch_ln_cf_bwd(const float* x, const void* g_y, int g_bf16, const f
   const size_t npix = (size_t)N*HW;
   const int chunks = ln_cf_chunks(npix);
   const dim3 grid((unsigned)((npix + 63)/64));
-  if (g_bf16) {
-    hipLaunchKernelGGL(k_ln_cf_bwd_dx<bf16>, grid, dim3(kLnBlock), 0, st, x, (const bf16*)g_y, gamma, mean, rstd, g_x, C, HW, npix);
-    hipLaunchKernelGGL(k_ln_cf_bwd_wb<bf16>, dim3(chunks, C), dim3(256), 0, st, x, (const bf16*)g_y, mean, rstd, N, C, HW, chunks, ws);
-  } else {
-    hipLaunchKernelGGL(k_ln_cf_bwd_dx<float>, grid, dim3(kLnBlock), 0, st, x, (const float*)g_y, gamma, mean, rstd, g_x, C, HW, npix);
-    hipLaunchKernelGGL(k_ln_cf_bwd_wb<float>, dim3(chunks, C), dim3(256), 0, st, x, (const float*)g_y, mean, rstd, N, C, HW, chunks, ws);
-  }
+  for_bool(g_bf16 != 0, [&](auto is_bf16) {
+    using TG = std::conditional_t<decltype(is_bf16)::value, bf16, float>;
+    hipLaunchKernelGGL(k_ln_cf_bwd_dx<TG>, grid, dim3(kLnBlock), 0, st, x, (const TG*)g_y, gamma, mean, rstd, g_x, C, HW, npix);
+    hipLaunchKernelGGL(k_ln_cf_bwd_wb<TG>, dim3(chunks, C), dim3(kBnBlock), 0, st, x, (const TG*)g_y, mean, rstd, N, C, HW, chunks, ws);
+  });
   hipLaunchKernelGGL(k_ln_cf_bwd_finalize, dim3(ceil_div(C, 64)), dim3(64), 0, st, ws, chunks, C, g_gamma, g_beta);
   return hipGetLastError();
 }

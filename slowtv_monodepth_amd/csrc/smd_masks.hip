@@ -131,11 +131,9 @@ __global__ __launch_bounds__(256) void k_scale_mean_fwd(const MeanSet ms, int mo
     const long long e = e0 + (long long)k*256;
     if (e < n) acc += mean_f(x[e], mode);
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
+  acc = block_sum<Waves::Pairwise, 4>(acc, red);
   if (threadIdx.x == 0) {
-    __hip_atomic_store(partial + blockIdx.x, (red[0] + red[1]) + (red[2] + red[3]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(partial + blockIdx.x, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __threadfence();
     last = (__hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u) ? 1u : 0u;
   }

@@ -10,7 +10,6 @@ namespace smd {
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void k_sum_partials(const float* __restrict__ partial, int count, double scale, float* out) {
   __shared__ double red[16];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   double acc = 0.0;
   int i = threadIdx.x;
   for (; i + 3*1024 < count; i += 4*1024) {      // four independent loads in flight; the order of the additions is fixed
@@ -18,15 +17,9 @@ __global__ __launch_bounds__(1024) void k_sum_partials(const float* __restrict__
     acc += ((double)a + (double)b) + ((double)c + (double)d);
   }
   for (; i < count; i += 1024) acc += (double)partial[i];
-  acc = wave_sum_f64(acc);
-  if (lane == 0) red[wv] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double tot = 0.0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) tot += red[k];
-    out[0] = (float)(tot*scale);
-  }
+  const double a[1] = {acc};
+  stage_wave_sums(a, red);
+  if (threadIdx.x == 0) out[0] = (float)(sum_waves<Waves::Sequential, 16>(red)*scale);
 }
 
 hipError_t launch_sum_partials(const float* partial, int count, double scale, float* out, hipStream_t st) {

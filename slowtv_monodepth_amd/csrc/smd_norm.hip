@@ -7,15 +7,18 @@
 //   forward : stats sweep (per chunk: mean, then squared deviations from it; many blocks per channel) -> apply sweep (each block combines the chunks in fp64, Chan's formula)
 //   backward: reduce sweep (sum dz, sum dz*(x-mean))               -> apply sweep (same; block 0 of a channel writes g_gamma, g_beta)
 //   layers with N*HW <= 16384 (layer3/4 of the encoders): ONE launch per direction, one block per channel
-// where dz = g_y masked by (y > 0) when the ReLU is fused.  NCHW fp32; float4 path when HW % 4 == 0.
+// where dz = g_y masked by (y > 0) when the ReLU is fused.  NCHW fp32; 4-float steps when HW % 4 == 0.
+// Every sweep is `channel_sweep` (smd_norm_dev.h: chunk range, offset of a flat index, block-strided steps of 1 or 4 floats) around a body written once for
+// both step widths; every block sum is `block_sum2<Waves::Sequential>` (smd_common.h).
 #include "smd_common.h"
 #include "smd_kernels.h"
+#include "smd_norm_dev.h"
 
 namespace smd {
 
-constexpr int kBnBlock = 256;
 constexpr int kBnItemsPerBlock = 8192;   // floats a block sweeps in the reduction kernels
 constexpr int kBnMaxChunks = 128;
+constexpr int kBnWaves = kBnBlock/64;
 
 int bn_chunks(int N, int HW) {
   const long long total = (long long)N*HW;
@@ -23,62 +26,38 @@ int bn_chunks(int N, int HW) {
   return (int)(c < 1 ? 1 : (c > kBnMaxChunks ? kBnMaxChunks : c));
 }
 
-__device__ __forceinline__ void block_sum2(float a, float b, float* red, float& ra, float& rb) {
-  a = wave_sum(a); b = wave_sum(b);
-  const int wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[wv*2] = a; red[wv*2 + 1] = b; }
-  __syncthreads();
-  ra = 0.f; rb = 0.f;
-#pragma unroll
-  for (int k = 0; k < kBnBlock/64; ++k) { ra += red[k*2]; rb += red[k*2 + 1]; }
-}
-
-// Range of the flattened (n, p) index space of one channel swept by chunk k (multiple of 4 when VEC).
-__device__ __forceinline__ void chunk_range(long long total, int chunks, int k, long long& lo, long long& hi) {
-  long long len = (total + chunks - 1)/chunks;
-  len = (len + 3) & ~3ll;
-  lo = (long long)k*len; hi = lo + len < total ? lo + len : total;
-}
-
 // Statistics of a range in two passes, so that they depend on no single element: pass 1 sums the values (their mean `m` only has to be NEAR the mean: it is the
 // shift of pass 2), pass 2 sums r = sum(x - m) and q = sum((x - m)^2).  Then mean = m + r/n exactly and M2 = q - r*r/n, where r is a rounding-sized correction.
 // A thread keeps its first kBnKeep values in registers between the passes (a chunk of the stats sweep has no more: one read from memory); whatever a
 // longer range holds is read again (the upper half of the single-launch path, from L2, and chunks of more than kBnItemsPerBlock floats).
+// (The kept part stays a fully unrolled loop of its own, so that `v` lives in registers; it decodes its indices through the sweep's channel_offset.)
 constexpr int kBnKeep = kBnItemsPerBlock/kBnBlock;   // 32
 
-template <bool VEC, bool KEEP>
+template <bool VEC>
 __device__ __forceinline__ void range_stats(const float* __restrict__ x, int C, int HW, int c, long long lo, long long hi, float* red, float& m, float& r, float& q) {
-  constexpr int W = VEC ? 4 : 1, STEPS = KEEP ? kBnKeep/W : 0;
-  const long long stride = (long long)kBnBlock*W, first = lo + (long long)threadIdx.x*W;
-  float v[KEEP ? kBnKeep : 1];
-  float s = 0.f;
+  constexpr int W = VEC ? 4 : 1, STEPS = kBnKeep/W;
+  const long long stride = (long long)kBnBlock*W, first = lo + (long long)threadIdx.x*W, rest = lo + STEPS*stride;
+  float v[kBnKeep];
+  float s = 0.f, unused = 0.f;
 #pragma unroll
   for (int j = 0; j < STEPS; ++j) {
     const long long i = first + j*stride;
-#pragma unroll
-    for (int e = 0; e < W; ++e) v[j*W + e] = 0.f;
+    fvec<W> t = 0.f;
     if (i < hi) {
-      const int n = (int)(i/HW), p = (int)(i - (long long)n*HW);
-      const size_t off = ((size_t)n*C + c)*HW + p;
-      if (VEC) {
-        const f4 t = *(const f4*)(x + off);
+      t = ldv<W>(x + channel_offset(i, C, HW, c));
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { v[j*W + e] = t[e]; s += t[e]; }
-      } else { v[j] = x[off]; s += v[j]; }
+      for (int e = 0; e < W; ++e) s += t[e];
     }
-  }
-  for (long long i = first + STEPS*stride; i < hi; i += stride) {
-    const int n = (int)(i/HW), p = (int)(i - (long long)n*HW);
-    const size_t off = ((size_t)n*C + c)*HW + p;
-    if (VEC) {
-      const f4 t = *(const f4*)(x + off);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) s += t[e];
-    } else s += x[off];
+    for (int e = 0; e < W; ++e) v[j*W + e] = t[e];
   }
-  float tot, unused;
-  block_sum2(s, 0.f, red, tot, unused);
-  m = tot/(float)(hi - lo);
+  channel_sweep<VEC>(rest, hi, C, HW, c, [&](size_t off, long long) {
+    const fvec<W> t = ldv<W>(x + off);
+#pragma unroll
+    for (int e = 0; e < W; ++e) s += t[e];
+  });
+  block_sum2<Waves::Sequential, kBnWaves>(s, unused, red);
+  m = s/(float)(hi - lo);
   __syncthreads();   // `red` is written again below
   float a = 0.f, b = 0.f;
 #pragma unroll
@@ -88,27 +67,24 @@ __device__ __forceinline__ void range_stats(const float* __restrict__ x, int C, 
       for (int e = 0; e < W; ++e) { const float d = v[j*W + e] - m; a += d; b = fmaf(d, d, b); }
     }
   }
-  for (long long i = first + STEPS*stride; i < hi; i += stride) {
-    const int n = (int)(i/HW), p = (int)(i - (long long)n*HW);
-    const size_t off = ((size_t)n*C + c)*HW + p;
-    if (VEC) {
-      const f4 t = *(const f4*)(x + off);
+  channel_sweep<VEC>(rest, hi, C, HW, c, [&](size_t off, long long) {
+    const fvec<W> t = ldv<W>(x + off);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) { const float d = t[e] - m; a += d; b = fmaf(d, d, b); }
-    } else { const float d = x[off] - m; a += d; b = fmaf(d, d, b); }
-  }
-  block_sum2(a, b, red, r, q);
+    for (int e = 0; e < W; ++e) { const float d = t[e] - m; a += d; b = fmaf(d, d, b); }
+  });
+  block_sum2<Waves::Sequential, kBnWaves>(a, b, red);
+  r = a; q = b;
 }
 
 // Stats sweep of the chunked path: per chunk (m, r/n, M2) with the chunk's mean = m + r/n.
 template <bool VEC>
 __global__ __launch_bounds__(kBnBlock) void k_bn_stats(const float* __restrict__ x, int N, int C, int HW, int chunks, float* __restrict__ partial) {
-  __shared__ float red[2*kBnBlock/64];
+  __shared__ float red[2*kBnWaves];
   const int c = blockIdx.y, k = blockIdx.x;
   long long lo, hi;
   chunk_range((long long)N*HW, chunks, k, lo, hi);
   float m = 0.f, r = 0.f, q = 0.f;
-  if (lo < hi) range_stats<VEC, true>(x, C, HW, c, lo, hi, red, m, r, q);   // (block-uniform)
+  if (lo < hi) range_stats<VEC>(x, C, HW, c, lo, hi, red, m, r, q);   // (block-uniform)
   if (threadIdx.x == 0) {
     const float rn = lo < hi ? r/(float)(hi - lo) : 0.f;
     float* out = partial + ((size_t)c*chunks + k)*3;
@@ -116,40 +92,27 @@ __global__ __launch_bounds__(kBnBlock) void k_bn_stats(const float* __restrict__
   }
 }
 
-// fp64 combine of a channel's partial pairs by the whole block (every block of the apply sweeps does this for itself:
-// <= 128 pairs, so the separate one-thread-per-channel finalize launch is gone and nothing needs an atomic).
+// The two fp64 combines of a channel's chunks by the whole block (every block of the apply sweeps does this for itself: <= 128 chunks, so the separate
+// one-thread-per-channel finalize launch is gone and nothing needs an atomic): what a thread adds up, then one block sum.
+// Backward: the plain sums of the reduce sweep's pairs.
 __device__ __forceinline__ void combine_partials(const float* __restrict__ partial, int c, int chunks, double* red, double& s1, double& s2) {
-  double a = 0.0, b = 0.0;
-  for (int k = threadIdx.x; k < chunks; k += kBnBlock) { a += (double)partial[((size_t)c*chunks + k)*2]; b += (double)partial[((size_t)c*chunks + k)*2 + 1]; }
-  for (int off = 32; off > 0; off >>= 1) { a += __shfl_xor(a, off, 64); b += __shfl_xor(b, off, 64); }
-  const int wv = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) { red[wv*2] = a; red[wv*2 + 1] = b; }
-  __syncthreads();
   s1 = 0.0; s2 = 0.0;
-#pragma unroll
-  for (int k = 0; k < kBnBlock/64; ++k) { s1 += red[k*2]; s2 += red[k*2 + 1]; }
+  for (int k = threadIdx.x; k < chunks; k += kBnBlock) { s1 += (double)partial[((size_t)c*chunks + k)*2]; s2 += (double)partial[((size_t)c*chunks + k)*2 + 1]; }
+  block_sum2<Waves::Sequential, kBnWaves>(s1, s2, red);
 }
-
-// Chan's combination of the stats sweep's chunks in fp64, about the mean of chunk 0 (`shift`): s1 = sum n_k (mean_k - shift), s2 = sum M2_k + n_k (mean_k - shift)^2,
+// Forward: Chan's combination of the stats sweep's chunks about the mean of chunk 0 (`shift`): s1 = sum n_k (mean_k - shift), s2 = sum M2_k + n_k (mean_k - shift)^2,
 // i.e. the shifted sums of the whole channel that `finish_stats` takes.
 __device__ __forceinline__ void combine_chunk_stats(const float* __restrict__ partial, int c, int chunks, long long total, double* red, double& shift, double& s1, double& s2) {
   const float* pc = partial + (size_t)c*chunks*3;
   shift = (double)pc[0] + (double)pc[1];
-  double a = 0.0, b = 0.0;
+  s1 = 0.0; s2 = 0.0;
   for (int k = threadIdx.x; k < chunks; k += kBnBlock) {
     long long lo, hi;
     chunk_range(total, chunks, k, lo, hi);
     const double n = hi > lo ? (double)(hi - lo) : 0.0, d = ((double)pc[k*3] + (double)pc[k*3 + 1]) - shift;
-    a += n*d; b += (double)pc[k*3 + 2] + n*d*d;
+    s1 += n*d; s2 += (double)pc[k*3 + 2] + n*d*d;
   }
-  for (int off = 32; off > 0; off >>= 1) { a += __shfl_xor(a, off, 64); b += __shfl_xor(b, off, 64); }
-  const int wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[wv*2] = a; red[wv*2 + 1] = b; }
-  __syncthreads();
-  s1 = 0.0; s2 = 0.0;
-#pragma unroll
-  for (int k = 0; k < kBnBlock/64; ++k) { s1 += red[k*2]; s2 += red[k*2 + 1]; }
+  block_sum2<Waves::Sequential, kBnWaves>(s1, s2, red);
 }
 
 struct BnStat { float mean, invstd; };
@@ -173,26 +136,17 @@ template <bool VEC>
 __device__ __forceinline__ void apply_range(const float* __restrict__ x, const float* __restrict__ residual, float* __restrict__ y, int C, int HW, int c,
                                             long long lo, long long hi, float mean, float sc, float beta, int relu) {
   constexpr int W = VEC ? 4 : 1;
-  for (long long i = lo + (long long)threadIdx.x*W; i < hi; i += kBnBlock*W) {
-    const int n = (int)(i/HW), p = (int)(i - (long long)n*HW);
-    const size_t off = ((size_t)n*C + c)*HW + p;
-    if (VEC) {
-      const f4 v = *(const f4*)(x + off);
-      f4 o;
+  channel_sweep<VEC>(lo, hi, C, HW, c, [&](size_t off, long long) {
+    fvec<W> o = ldv<W>(x + off);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) o[q] = fmaf(v[q] - mean, sc, beta);
-      if (residual) { const f4 r = *(const f4*)(residual + off); o += r; }
-      if (relu) {
+    for (int e = 0; e < W; ++e) o[e] = fmaf(o[e] - mean, sc, beta);
+    if (residual) o += ldv<W>(residual + off);
+    if (relu) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) o[q] = fmaxf(o[q], 0.f);
-      }
-      *(f4*)(y + off) = o;
-    } else {
-      float o = fmaf(x[off] - mean, sc, beta);
-      if (residual) o += residual[off];
-      y[off] = relu ? fmaxf(o, 0.f) : o;
+      for (int e = 0; e < W; ++e) o[e] = fmaxf(o[e], 0.f);
     }
-  }
+    stv<W>(y + off, o);
+  });
 }
 
 // Apply sweep of the chunked path: grid (chunks, C), the same ranges as the stats sweep.
@@ -201,7 +155,7 @@ __global__ __launch_bounds__(kBnBlock) void k_bn_apply(const float* __restrict__
                                                        const float* __restrict__ beta, const float* __restrict__ partial, int N, int C, int HW, int chunks,
                                                        float momentum, float eps, int relu, float* __restrict__ running_mean, float* __restrict__ running_var,
                                                        float* __restrict__ save_mean, float* __restrict__ save_invstd, float* __restrict__ y) {
-  __shared__ double red[2*kBnBlock/64];
+  __shared__ double red[2*kBnWaves];
   const int c = blockIdx.y, k = blockIdx.x;
   double shift, s1, s2;
   combine_chunk_stats(partial, c, chunks, (long long)N*HW, red, shift, s1, s2);
@@ -217,73 +171,72 @@ __global__ __launch_bounds__(kBnBlock) void k_bn_fwd_small(const float* __restri
                                                            const float* __restrict__ beta, int N, int C, int HW, float momentum, float eps, int relu,
                                                            float* __restrict__ running_mean, float* __restrict__ running_var,
                                                            float* __restrict__ save_mean, float* __restrict__ save_invstd, float* __restrict__ y) {
-  __shared__ float red[2*kBnBlock/64];
+  __shared__ float red[2*kBnWaves];
   const int c = blockIdx.x;
   const long long total = (long long)N*HW;
   float m, r, q;
-  range_stats<VEC, true>(x, C, HW, c, 0, total, red, m, r, q);   // (layer3/4 of the encoders hold <= kBnItemsPerBlock values per channel: nothing is read twice for the statistics)
+  range_stats<VEC>(x, C, HW, c, 0, total, red, m, r, q);   // (layer3/4 of the encoders hold <= kBnItemsPerBlock values per channel: nothing is read twice for the statistics)
   const BnStat st = finish_stats((double)r, (double)q, (double)m, N, HW, momentum, eps, c, threadIdx.x == 0, running_mean, running_var, save_mean, save_invstd);
   apply_range<VEC>(x, residual, y, C, HW, c, 0, total, st.mean, gamma[c]*st.invstd, beta[c], relu);
+}
+
+// dz of a step: g_y where the fused ReLU let y through
+template <int W>
+__device__ __forceinline__ fvec<W> bwd_dz(const float* __restrict__ y, const float* __restrict__ g_y, size_t off, int relu) {
+  const fvec<W> gv = ldv<W>(g_y + off);
+  fvec<W> yv = 1.f, dz;
+  if (relu) yv = ldv<W>(y + off);
+#pragma unroll
+  for (int e = 0; e < W; ++e) dz[e] = (yv[e] > 0.f) ? gv[e] : 0.f;
+  return dz;
 }
 
 template <bool VEC>
 __device__ __forceinline__ void bwd_reduce_range(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ g_y, int C, int HW, int c,
                                                  long long lo, long long hi, float mu, int relu, float& s1, float& s2) {
   constexpr int W = VEC ? 4 : 1;
-  for (long long i = lo + (long long)threadIdx.x*W; i < hi; i += kBnBlock*W) {
-    const int n = (int)(i/HW), p = (int)(i - (long long)n*HW);
-    const size_t off = ((size_t)n*C + c)*HW + p;
-    if (VEC) {
-      const f4 xv = *(const f4*)(x + off), gv = *(const f4*)(g_y + off);
-      f4 yv = {1.f, 1.f, 1.f, 1.f};
-      if (relu) yv = *(const f4*)(y + off);
+  channel_sweep<VEC>(lo, hi, C, HW, c, [&](size_t off, long long) {
+    const fvec<W> xv = ldv<W>(x + off), dz = bwd_dz<W>(y, g_y, off, relu);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) { const float dz = (yv[q] > 0.f) ? gv[q] : 0.f; s1 += dz; s2 = fmaf(dz, xv[q] - mu, s2); }
-    } else {
-      const float dz = (!relu || y[off] > 0.f) ? g_y[off] : 0.f;
-      s1 += dz; s2 = fmaf(dz, x[off] - mu, s2);
-    }
-  }
+    for (int e = 0; e < W; ++e) { s1 += dz[e]; s2 = fmaf(dz[e], xv[e] - mu, s2); }
+  });
+}
+
+// What both backward paths derive from the channel's sums s1 = sum dz, s2 = sum dz*(x - mean) (fp64: the chunked path's combine; the single launch's fp32 block
+// sums widen exactly): g_beta, g_gamma (by `writer`) and the coefficients of g_x = a*(dz - b - (x - mean)*k2).
+struct BnBwdCoef { float a, b, k2; };
+__device__ __forceinline__ BnBwdCoef bwd_coeffs(double s1, double s2, float gamma, float invstd, double M, int c, bool writer, float* g_gamma, float* g_beta) {
+  const double is = (double)invstd;
+  if (writer) { g_beta[c] = (float)s1; g_gamma[c] = (float)(s2*is); }
+  return {(float)((double)gamma*is), (float)(s1/M), (float)(s2*is*is/M)};
 }
 
 template <bool VEC>
 __device__ __forceinline__ void bwd_apply_range(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ g_y, float* __restrict__ g_x,
-                                                float* __restrict__ g_res, int C, int HW, int c, long long lo, long long hi, float mu, float a, float b,
-                                                float k2, int relu) {
+                                                float* __restrict__ g_res, int C, int HW, int c, long long lo, long long hi, float mu, BnBwdCoef k, int relu) {
   constexpr int W = VEC ? 4 : 1;
-  for (long long i = lo + (long long)threadIdx.x*W; i < hi; i += kBnBlock*W) {
-    const int n = (int)(i/HW), p = (int)(i - (long long)n*HW);
-    const size_t off = ((size_t)n*C + c)*HW + p;
-    if (VEC) {
-      const f4 xv = *(const f4*)(x + off), gv = *(const f4*)(g_y + off);
-      f4 yv = {1.f, 1.f, 1.f, 1.f};
-      if (relu) yv = *(const f4*)(y + off);
-      f4 dz, dx;
+  channel_sweep<VEC>(lo, hi, C, HW, c, [&](size_t off, long long) {
+    const fvec<W> xv = ldv<W>(x + off), dz = bwd_dz<W>(y, g_y, off, relu);
+    fvec<W> dx;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) { dz[q] = (yv[q] > 0.f) ? gv[q] : 0.f; dx[q] = a*(dz[q] - b - (xv[q] - mu)*k2); }
-      *(f4*)(g_x + off) = dx;
-      if (g_res) *(f4*)(g_res + off) = dz;
-    } else {
-      const float dz = (!relu || y[off] > 0.f) ? g_y[off] : 0.f;
-      g_x[off] = a*(dz - b - (x[off] - mu)*k2);
-      if (g_res) g_res[off] = dz;
-    }
-  }
+    for (int e = 0; e < W; ++e) dx[e] = k.a*(dz[e] - k.b - (xv[e] - mu)*k.k2);
+    stv<W>(g_x + off, dx);
+    if (g_res) stv<W>(g_res + off, dz);
+  });
 }
 
 template <bool VEC>
 __global__ __launch_bounds__(kBnBlock) void k_bn_bwd_reduce(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ g_y,
                                                             const float* __restrict__ mean, int N, int C, int HW, int chunks, int relu,
                                                             float* __restrict__ partial) {
-  __shared__ float red[2*kBnBlock/64];
+  __shared__ float red[2*kBnWaves];
   const int c = blockIdx.y, k = blockIdx.x;
   long long lo, hi;
   chunk_range((long long)N*HW, chunks, k, lo, hi);
   float s1 = 0.f, s2 = 0.f;
   bwd_reduce_range<VEC>(x, y, g_y, C, HW, c, lo, hi, mean[c], relu, s1, s2);
-  float r1, r2;
-  block_sum2(s1, s2, red, r1, r2);
-  if (threadIdx.x == 0) { partial[((size_t)c*chunks + k)*2] = r1; partial[((size_t)c*chunks + k)*2 + 1] = r2; }
+  block_sum2<Waves::Sequential, kBnWaves>(s1, s2, red);
+  if (threadIdx.x == 0) { partial[((size_t)c*chunks + k)*2] = s1; partial[((size_t)c*chunks + k)*2 + 1] = s2; }
 }
 
 template <bool VEC>
@@ -292,15 +245,14 @@ __global__ __launch_bounds__(kBnBlock) void k_bn_bwd_apply(const float* __restri
                                                            const float* __restrict__ partial, int N, int C, int HW, int chunks, int relu,
                                                            float* __restrict__ g_x, float* __restrict__ g_res, float* __restrict__ g_gamma,
                                                            float* __restrict__ g_beta) {
-  __shared__ double red[2*kBnBlock/64];
+  __shared__ double red[2*kBnWaves];
   const int c = blockIdx.y, k = blockIdx.x;
   double s1, s2;
   combine_partials(partial, c, chunks, red, s1, s2);
-  const double M = (double)N*HW, is = (double)invstd[c];
-  if (k == 0 && threadIdx.x == 0) { g_beta[c] = (float)s1; g_gamma[c] = (float)(s2*is); }
+  const BnBwdCoef co = bwd_coeffs(s1, s2, gamma[c], invstd[c], (double)N*HW, c, k == 0 && threadIdx.x == 0, g_gamma, g_beta);
   long long lo, hi;
   chunk_range((long long)N*HW, chunks, k, lo, hi);
-  bwd_apply_range<VEC>(x, y, g_y, g_x, g_res, C, HW, c, lo, hi, mean[c], (float)((double)gamma[c]*is), (float)(s1/M), (float)(s2*is*is/M), relu);
+  bwd_apply_range<VEC>(x, y, g_y, g_x, g_res, C, HW, c, lo, hi, mean[c], co, relu);
 }
 
 template <bool VEC>
@@ -308,17 +260,14 @@ __global__ __launch_bounds__(kBnBlock) void k_bn_bwd_small(const float* __restri
                                                            const float* __restrict__ gamma, const float* __restrict__ mean, const float* __restrict__ invstd,
                                                            int N, int C, int HW, int relu, float* __restrict__ g_x, float* __restrict__ g_res,
                                                            float* __restrict__ g_gamma, float* __restrict__ g_beta) {
-  __shared__ float red[2*kBnBlock/64];
+  __shared__ float red[2*kBnWaves];
   const int c = blockIdx.x;
   const long long total = (long long)N*HW;
   float s1 = 0.f, s2 = 0.f;
   bwd_reduce_range<VEC>(x, y, g_y, C, HW, c, 0, total, mean[c], relu, s1, s2);
-  float r1, r2;
-  block_sum2(s1, s2, red, r1, r2);
-  const double M = (double)total, is = (double)invstd[c];
-  if (threadIdx.x == 0) { g_beta[c] = r1; g_gamma[c] = (float)((double)r2*is); }
-  bwd_apply_range<VEC>(x, y, g_y, g_x, g_res, C, HW, c, 0, total, mean[c], (float)((double)gamma[c]*is), (float)((double)r1/M),
-                       (float)((double)r2*is*is/M), relu);
+  block_sum2<Waves::Sequential, kBnWaves>(s1, s2, red);
+  const BnBwdCoef co = bwd_coeffs((double)s1, (double)s2, gamma[c], invstd[c], (double)total, c, threadIdx.x == 0, g_gamma, g_beta);
+  bwd_apply_range<VEC>(x, y, g_y, g_x, g_res, C, HW, c, 0, total, mean[c], co, relu);
 }
 
 constexpr long long kBnSmall = 16384;   // N*HW up to which one block per channel does the whole layer in one launch
@@ -326,43 +275,34 @@ constexpr long long kBnSmall = 16384;   // N*HW up to which one block per channe
 hipError_t launch_bn_fwd(const float* x, const float* residual, const float* gamma, const float* beta, float* running_mean, float* running_var,
                          float momentum, float eps, int relu, float* y, float* save_mean, float* save_invstd, float* ws, int N, int C, int HW,
                          hipStream_t st) {
-  const bool vec = (HW % 4) == 0;
-  if ((long long)N*HW <= kBnSmall) {
-    if (vec) hipLaunchKernelGGL(k_bn_fwd_small<true>, dim3(C), dim3(kBnBlock), 0, st, x, residual, gamma, beta, N, C, HW, momentum, eps, relu, running_mean, running_var, save_mean, save_invstd, y);
-    else hipLaunchKernelGGL(k_bn_fwd_small<false>, dim3(C), dim3(kBnBlock), 0, st, x, residual, gamma, beta, N, C, HW, momentum, eps, relu, running_mean, running_var, save_mean, save_invstd, y);
-    return hipGetLastError();
-  }
   const int chunks = bn_chunks(N, HW);
-  if (vec) {
-    hipLaunchKernelGGL(k_bn_stats<true>, dim3(chunks, C), dim3(kBnBlock), 0, st, x, N, C, HW, chunks, ws);
-    hipLaunchKernelGGL(k_bn_apply<true>, dim3(chunks, C), dim3(kBnBlock), 0, st, x, residual, gamma, beta, ws, N, C, HW, chunks, momentum, eps, relu,
+  for_bool((HW % 4) == 0, [&](auto vec) {
+    constexpr bool VEC = decltype(vec)::value;
+    if ((long long)N*HW <= kBnSmall) {
+      hipLaunchKernelGGL(k_bn_fwd_small<VEC>, dim3(C), dim3(kBnBlock), 0, st, x, residual, gamma, beta, N, C, HW, momentum, eps, relu, running_mean, running_var,
+                         save_mean, save_invstd, y);
+      return;
+    }
+    hipLaunchKernelGGL(k_bn_stats<VEC>, dim3(chunks, C), dim3(kBnBlock), 0, st, x, N, C, HW, chunks, ws);
+    hipLaunchKernelGGL(k_bn_apply<VEC>, dim3(chunks, C), dim3(kBnBlock), 0, st, x, residual, gamma, beta, ws, N, C, HW, chunks, momentum, eps, relu,
                        running_mean, running_var, save_mean, save_invstd, y);
-  } else {
-    hipLaunchKernelGGL(k_bn_stats<false>, dim3(chunks, C), dim3(kBnBlock), 0, st, x, N, C, HW, chunks, ws);
-    hipLaunchKernelGGL(k_bn_apply<false>, dim3(chunks, C), dim3(kBnBlock), 0, st, x, residual, gamma, beta, ws, N, C, HW, chunks, momentum, eps, relu,
-                       running_mean, running_var, save_mean, save_invstd, y);
-  }
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_bn_bwd(const float* x, const float* y, const float* g_y, const float* gamma, const float* save_mean, const float* save_invstd,
                          int relu, float* g_x, float* g_res, float* g_gamma, float* g_beta, float* ws, int N, int C, int HW, hipStream_t st) {
-  const bool vec = (HW % 4) == 0;
-  if ((long long)N*HW <= kBnSmall) {
-    if (vec) hipLaunchKernelGGL(k_bn_bwd_small<true>, dim3(C), dim3(kBnBlock), 0, st, x, y, g_y, gamma, save_mean, save_invstd, N, C, HW, relu, g_x, g_res, g_gamma, g_beta);
-    else hipLaunchKernelGGL(k_bn_bwd_small<false>, dim3(C), dim3(kBnBlock), 0, st, x, y, g_y, gamma, save_mean, save_invstd, N, C, HW, relu, g_x, g_res, g_gamma, g_beta);
-    return hipGetLastError();
-  }
   const int chunks = bn_chunks(N, HW);
-  if (vec) {
-    hipLaunchKernelGGL(k_bn_bwd_reduce<true>, dim3(chunks, C), dim3(kBnBlock), 0, st, x, y, g_y, save_mean, N, C, HW, chunks, relu, ws);
-    hipLaunchKernelGGL(k_bn_bwd_apply<true>, dim3(chunks, C), dim3(kBnBlock), 0, st, x, y, g_y, gamma, save_mean, save_invstd, ws, N, C, HW, chunks, relu,
+  for_bool((HW % 4) == 0, [&](auto vec) {
+    constexpr bool VEC = decltype(vec)::value;
+    if ((long long)N*HW <= kBnSmall) {
+      hipLaunchKernelGGL(k_bn_bwd_small<VEC>, dim3(C), dim3(kBnBlock), 0, st, x, y, g_y, gamma, save_mean, save_invstd, N, C, HW, relu, g_x, g_res, g_gamma, g_beta);
+      return;
+    }
+    hipLaunchKernelGGL(k_bn_bwd_reduce<VEC>, dim3(chunks, C), dim3(kBnBlock), 0, st, x, y, g_y, save_mean, N, C, HW, chunks, relu, ws);
+    hipLaunchKernelGGL(k_bn_bwd_apply<VEC>, dim3(chunks, C), dim3(kBnBlock), 0, st, x, y, g_y, gamma, save_mean, save_invstd, ws, N, C, HW, chunks, relu,
                        g_x, g_res, g_gamma, g_beta);
-  } else {
-    hipLaunchKernelGGL(k_bn_bwd_reduce<false>, dim3(chunks, C), dim3(kBnBlock), 0, st, x, y, g_y, save_mean, N, C, HW, chunks, relu, ws);
-    hipLaunchKernelGGL(k_bn_bwd_apply<false>, dim3(chunks, C), dim3(kBnBlock), 0, st, x, y, g_y, gamma, save_mean, save_invstd, ws, N, C, HW, chunks, relu,
-                       g_x, g_res, g_gamma, g_beta);
-  }
+  });
   return hipGetLastError();
 }
 

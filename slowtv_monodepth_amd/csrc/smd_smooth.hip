@@ -44,14 +44,6 @@ __device__ __forceinline__ void img_at(const float* __restrict__ img, int h, int
   }
 }
 
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
 // Frame-only half (round 4): the edge weights {exp(-mean_c |dI/dx|), exp(-mean_c |dI/dy|)} of every pyramid level depend on the target
 // frames alone — `SmoothReg` resizes the image to each level and differentiates it (src/core/handlers.py:272-277, smooth.py:12-30,
 // 91-94) — so they are computed by a launch of their own that the trainer enqueues with the reconstruction's frame-only prep, under
@@ -176,7 +168,7 @@ __device__ __forceinline__ float lap1(float x0, float x1, float x2, int i, int n
 
 __global__ __launch_bounds__(256) void k_smooth_lap_main(const ScaleSet sc, int b, const float* __restrict__ img, int h, int w, int flags,
                                                          float* __restrict__ partial, int max_units, float* __restrict__ edge_w) {
-  __shared__ float red[4];
+  __shared__ float red[2*4];
   const int s = blockIdx.z, bi = blockIdx.y;
   const int hs = sc.hs[s], ws = sc.ws[s], n = hs*ws;
   const int pix = blockIdx.x*256 + threadIdx.x;
@@ -205,10 +197,10 @@ __global__ __launch_bounds__(256) void k_smooth_lap_main(const ScaleSet sc, int 
     }
     e = dxx*wx + dyy*wy; dsum = dc;
   }
-  const float totE = block_sum_256(e, red), totD = block_sum_256(dsum, red);
+  block_sum2<Waves::Sequential, 4>(e, dsum, red);
   if (threadIdx.x == 0) {
     float* pp = partial + (((size_t)s*b + bi)*max_units + blockIdx.x)*2;
-    pp[0] = totE; pp[1] = totD;
+    pp[0] = e; pp[1] = dsum;
   }
 }
 

@@ -103,17 +103,9 @@ __global__ __launch_bounds__(kUfBlock) void k_view_synth_bwd(const float* __rest
     ps[0] = dnx*uf; ps[1] = dnx*vf; ps[2] = dnx; ps[3] = dny*uf; ps[4] = dny*vf; ps[5] = dny;
     ps[6] = dz*uf; ps[7] = dz*vf; ps[8] = dz; ps[9] = gnx; ps[10] = gny; ps[11] = gz;
   }
-#pragma unroll
-  for (int k = 0; k < kPoseSums; ++k) {
-    const float tot = wave_sum(ps[k]);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = tot;
-  }
-  __syncthreads();
-  if (threadIdx.x < kPoseSums) {
-    float tot = 0.f;
-    for (int wv = 0; wv < kUfBlock/64; ++wv) tot += red[wv][threadIdx.x];
-    pose_partial[((size_t)bi*gridDim.x + blockIdx.x)*kPoseSums + threadIdx.x] = tot;
-  }
+  stage_wave_sums(ps, &red[0][0]);
+  // (0.f +: these sums have always started from +0, and a pose sum, unlike an accumulator, can be -0 in every wave)
+  if (threadIdx.x < kPoseSums) pose_partial[((size_t)bi*gridDim.x + blockIdx.x)*kPoseSums + threadIdx.x] = 0.f + sum_waves<Waves::Sequential, kUfBlock/64>(&red[0][0], kPoseSums, threadIdx.x);
 }
 
 hipError_t launch_view_synth_bwd(const float* input, const float* depth, const float* T, const float* K, const float* Kinv,
@@ -302,10 +294,7 @@ __global__ __launch_bounds__(kUfBlock) void k_recon_reduce_fwd(const float* __re
     }
     err[idx] = e; sel[idx] = (uint8_t)bsel;
   }
-  const float tot = wave_sum(e);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = tot;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  block_store_sum<Waves::Sequential, kUfBlock/64>(e, red, partial + blockIdx.x);
 }
 
 static inline int mask_mode_of(int flags, const float* mask) { return !mask ? 0 : ((flags & SMD_MASK_UNCERTAINTY) ? 2 : ((flags & SMD_MASK_EXPLAINABILITY) ? 1 : 0)); }

@@ -1291,7 +1291,10 @@ def _plain_decoder(dec, feat):
 
 # ---------------------------------------------------------------------------------------------------
 # Producer side: BatchNorm (+ residual, + ReLU) kernels against ATen's batch_norm / add / relu
-@pytest.mark.parametrize('shape', [(4, 8, 6, 20), (3, 5, 7, 9), (12, 64, 24, 80), (2, 130, 3, 5), (12, 6, 37, 41)])
+# (1, 2, 128, 128): N*HW = 16384, the last single-launch shape (a thread's register-kept values plus the re-read part); (1, 2, 101, 101): the same in 1-float steps;
+# (1, 2, 4097, 4): 16388, the first chunked one; (3, 2, 4, 2049): HW = 8196, sample boundaries inside a chunk and inside a thread's stride
+@pytest.mark.parametrize('shape', [(4, 8, 6, 20), (3, 5, 7, 9), (12, 64, 24, 80), (2, 130, 3, 5), (12, 6, 37, 41), (1, 2, 128, 128), (1, 2, 101, 101), (1, 2, 4097, 4),
+                                   (3, 2, 4, 2049)])
 @pytest.mark.parametrize('relu,res', [(False, False), (True, False), (True, True), (False, True)])
 def test_batch_norm_act_kernel(F, shape, relu, res):
     import torch.nn.functional as TF
@@ -1659,7 +1662,7 @@ def test_depthwise_conv7x7_kernel(F, shape):
         assert rel_to_max(a, e) < 2e-5, f'{nm}: {rel_to_max(a, e):.3e}'
 
 
-@pytest.mark.parametrize('shape', [(2, 3, 1, 1), (2, 96, 6, 20), (1, 7, 33, 65), (3, 128, 24, 40), (2, 1030, 5, 7)])
+@pytest.mark.parametrize('shape', [(2, 3, 1, 1), (2, 96, 6, 20), (1, 7, 33, 65), (3, 128, 24, 40), (2, 1030, 5, 7), (1, 5, 91, 91)])   # (the last: 8281 pixels, two chunks of the gamma / beta reduction)
 def test_channel_layer_norm_kernel(F, shape):
     import torch.nn.functional as TF
     gen = torch.Generator().manual_seed(31)
