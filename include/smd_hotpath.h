@@ -526,6 +526,35 @@ int smd_relu_pad_bwd(const float* x, const float* bias, const float* g_out, floa
                      int B, int C, int h, int w, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The SuperDepth decoder's sub-pixel convolution with what stands around it (additive to ABI 8; reference: src/networks/decoders/superdepth.py:13-26 —
+ * SubPixelConv: `Conv2d(ch_in, ch_in r^2, 3, groups=ch_in, padding=1)` then `PixelShuffle(r)` — between the ELU of the `conv_block` in front of it
+ * (decoders/utils.py:49-54) and, in a stage, superdepth.py:70-74 and :105-113: `ReLU`, `torch.cat` with the skip feature and the reflection padding of the
+ * next conv3x3 (decoders/utils.py:44-46); in a head, superdepth.py:93-97: the output activation).  All tensors fp32, r in {2, 4, 8}.
+ *   u = pre_act(x + pre_bias[c])                       x (B,C,h,w) a raw (bias-free) convolution output, pre_bias (C) or NULL, pre_act SMD_SP_PRE_NONE / _ELU
+ *   v[b,c,r y+dy,r x+dx] = bias[o] + sum_ij weight[o,0,i,j] u[b,c,y+i-1,x+j-1]      o = c r^2 + dy r + dx, u = 0 outside the plane;
+ *                                                      weight (C r^2,1,3,3), bias (C r^2): the layout of the reference's Conv2d
+ *   z = act(v)                                         act SMD_SP_NONE / _RELU / _SIGMOID
+ *   out = z (B,C,r h,r w)                              pad = 0 (then Cs = 0 and skip is ignored)
+ *       | reflect_pad1(cat(z, skip)) (B,C+Cs,r h+2,r w+2)   pad = 1; skip (B,Cs,r h,r w), or NULL with Cs = 0
+ * Neither u nor v nor the un-shuffled C r^2-channel tensor is written.  Backward: g_out (out's shape) and out itself (for the derivative of act; NULL is
+ * accepted with SMD_SP_NONE) -> g_x, g_pre_bias (C), g_weight, g_bias, g_skip; any of them may be NULL.  The pad adjoint is folded in on the fly, u is
+ * recomputed; a ReLU output of exactly 0 passes no gradient.  Every sum runs in a fixed order (no atomics): two runs on the same inputs are bit-equal.
+ * smd_subpixel_workspace_bytes: the backward's workspace (per-block sums of the two bias gradients and of the C r^2 9 weight-gradient sums, added in a
+ * second stage); 0 for sizes that are not served (a non-positive size, another r, skip channels without pad, a padded plane of 2^30 elements or more,
+ * 2^31 blocks or more).  The forward needs none. */
+#define SMD_SP_PRE_NONE 0
+#define SMD_SP_PRE_ELU 1
+#define SMD_SP_NONE 0
+#define SMD_SP_RELU 1
+#define SMD_SP_SIGMOID 2
+size_t smd_subpixel_workspace_bytes(int B, int C, int Cs, int h, int w, int r, int pad);
+int smd_subpixel_fwd(const float* x, const float* pre_bias, const float* weight, const float* bias, const float* skip, float* out,
+                     int B, int C, int Cs, int h, int w, int r, int pre_act, int act, int pad, void* stream);
+int smd_subpixel_bwd(const float* x, const float* pre_bias, const float* weight, const float* out, const float* g_out, float* g_x, float* g_pre_bias,
+                     float* g_weight, float* g_bias, float* g_skip, void* workspace, size_t workspace_bytes,
+                     int B, int C, int Cs, int h, int w, int r, int pre_act, int act, int pad, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Pose / intrinsics prologue — one launch each instead of ~45 eager ATen launches.
  *
  * smd_pose_*: `T_from_AAt(aa, t)` (src/tools/geometry.py:181-209), followed by `T.inverse()` where invert[i] != 0

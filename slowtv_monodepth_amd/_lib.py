@@ -128,6 +128,9 @@ PROTOTYPES = {
     'smd_up_cat_gate_pad_bwd': (_i, [_vp]*15 + [_sz] + [_i]*7 + [_vp]),
     'smd_relu_pad_fwd': (_i, [_vp]*3 + [_i]*4 + [_vp]),
     'smd_relu_pad_bwd': (_i, [_vp]*6 + [_sz] + [_i]*4 + [_vp]),
+    'smd_subpixel_workspace_bytes': (_sz, [_i]*7),
+    'smd_subpixel_fwd': (_i, [_vp]*6 + [_i]*9 + [_vp]),
+    'smd_subpixel_bwd': (_i, [_vp]*11 + [_sz] + [_i]*9 + [_vp]),
     'smd_pose_fwd': (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     'smd_pose_bwd': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     'smd_intrinsics_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

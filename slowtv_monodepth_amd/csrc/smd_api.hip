@@ -1206,6 +1206,33 @@ int smd_relu_pad_bwd(const float* x, const float* bias, const float* g_out, floa
 }
 
 // ------------------------------------------------------------------------------------------------
+// The SuperDepth decoder's sub-pixel convolution (smd_subpixel.hip): pre-activation + depth-wise 3x3 to r^2 channels + pixel shuffle + activation [+ cat + pad]
+size_t smd_subpixel_workspace_bytes(int B, int C, int Cs, int h, int w, int r, int pad) {
+  const smd::SubPixel s{B, C, Cs, h, w, r, 0, 0, pad};
+  if (!smd::subpixel_sizes_ok(s)) return 0;
+  return align256(smd::subpixel_workspace_floats(s)*sizeof(float));
+}
+int smd_subpixel_fwd(const float* x, const float* pre_bias, const float* weight, const float* bias, const float* skip, float* out,
+                     int B, int C, int Cs, int h, int w, int r, int pre_act, int act, int pad, void* stream) {
+  if (!x || !weight || !bias || !out || (Cs > 0 && !skip)) return fail(SMD_E_INVALID, "null pointer");
+  const smd::SubPixel s{B, C, Cs, h, w, r, pre_act, act, pad};
+  if (!smd::subpixel_sizes_ok(s)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d Cs=%d h=%d w=%d r=%d pre_act=%d act=%d pad=%d", B, C, Cs, h, w, r, pre_act, act, pad);
+  return check_launch(smd::launch_subpixel_fwd(s, x, pre_bias, weight, bias, skip, out, (hipStream_t)stream), "subpixel_fwd");
+}
+int smd_subpixel_bwd(const float* x, const float* pre_bias, const float* weight, const float* out, const float* g_out, float* g_x, float* g_pre_bias,
+                     float* g_weight, float* g_bias, float* g_skip, void* workspace, size_t workspace_bytes,
+                     int B, int C, int Cs, int h, int w, int r, int pre_act, int act, int pad, void* stream) {
+  if (!x || !weight || !g_out || !workspace || (act != 0 && !out) || (g_pre_bias && !pre_bias)) return fail(SMD_E_INVALID, "null pointer");
+  if (!g_x && !g_pre_bias && !g_weight && !g_bias && !g_skip) return fail(SMD_E_INVALID, "nothing to compute");
+  const smd::SubPixel s{B, C, Cs, h, w, r, pre_act, act, pad};
+  if (!smd::subpixel_sizes_ok(s)) return fail(SMD_E_INVALID, "invalid sizes B=%d C=%d Cs=%d h=%d w=%d r=%d pre_act=%d act=%d pad=%d", B, C, Cs, h, w, r, pre_act, act, pad);
+  if (g_skip && Cs == 0) return fail(SMD_E_INVALID, "invalid sizes: a skip gradient without skip channels");
+  if (workspace_bytes < smd_subpixel_workspace_bytes(B, C, Cs, h, w, r, pad)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return check_launch(smd::launch_subpixel_bwd(s, x, pre_bias, weight, out, g_out, g_x, g_pre_bias, g_weight, g_bias, g_skip, (float*)workspace,
+                                               (hipStream_t)stream), "subpixel_bwd");
+}
+
+// ------------------------------------------------------------------------------------------------
 // Depthwise 7x7 convolution (ConvNeXt)
 static bool dw_sizes_ok(int N, int C, int H, int W) {
   return N >= 1 && C >= 1 && H >= 1 && W >= 1 && (long long)N*C*smd::dwconv_tiles(H, W) < (1ll << 31) && (long long)H*W < (1ll << 30);

@@ -333,6 +333,15 @@ hipError_t launch_up_cat_gate_pad_fwd(const UpCatGate& s, const float* a, const 
 hipError_t launch_up_cat_gate_pad_bwd(const UpCatGate& s, const float* a, const float* bias, const float* skip, const float* w1, const float* w2,
                                       const float* gate, const float* mean, const float* hid, const float* g_out, float* g_a, float* g_skip, float* g_bias,
                                       float* g_w1, float* g_w2, float* ws, hipStream_t st);
+// smd_subpixel.hip: SuperDepth's sub-pixel convolution between a raw convolution output and the next convolution's padded input; r in {2, 4, 8},
+// pre_act 0: none, 1: ELU; act 0: none, 1: ReLU, 2: sigmoid; pad 1: reflect_pad1(cat(z, skip)) (Cs > 0 only then)
+struct SubPixel { int B, C, Cs, h, w, r, pre_act, act, pad; };
+bool subpixel_sizes_ok(const SubPixel& s);
+size_t subpixel_workspace_floats(const SubPixel& s);
+hipError_t launch_subpixel_fwd(const SubPixel& s, const float* x, const float* pre_bias, const float* weight, const float* bias, const float* skip, float* out,
+                               hipStream_t st);
+hipError_t launch_subpixel_bwd(const SubPixel& s, const float* x, const float* pre_bias, const float* weight, const float* out, const float* g_out, float* g_x,
+                               float* g_pre_bias, float* g_weight, float* g_bias, float* g_skip, float* ws, hipStream_t st);
 int bn_chunks(int N, int HW);
 hipError_t launch_bn_fwd(const float* x, const float* residual, const float* gamma, const float* beta, float* running_mean, float* running_var,
                          float momentum, float eps, int relu, float* y, float* save_mean, float* save_invstd, float* ws, int N, int C, int HW,

@@ -18,6 +18,8 @@ the `nets.<key>.` prefix (`src/core/trainer.py:58-60`), or the bare module's —
     with a `diffnet` decoder (diffnet.py:111-128): the modules carry the reference's own names and are registered twice, as it registers them —
     decoders.disp.convs.{upconv_i,outconv_k}.*          the same          (`convs`, the ModuleDict)
     decoders.disp.decoder.{0..8}.*                      the same          (`decoder`, the ModuleList of the same modules: upconv_4..0, outconv_0..3)
+    with a `superdepth` decoder (superdepth.py:66-99): `convs` is a plain dict there and here, only the ModuleList is registered —
+    decoders.disp.decoder.{0..9+len(out_sc)}.*          the same          (upconv_4_0, upconv_4_1, ..., upconv_0_1, then the heads in `out_sc` order)
     encoder.layer{L}.{B}.downsample.{0,1}.*             encoder.layers.{L-1}.{B}.down.{0,1}.*  (timm ResNet, features_only)
     encoder.stem_0 / stem_1 (or stem.0 / stem.1)        encoder.stem.0 / stem.1                (timm ConvNeXt, features_only)
     encoder.stages_{S}.downsample.{0,1}.*               encoder.stages.{S}.{0,1}.*
@@ -39,7 +41,7 @@ __all__ = ['from_reference_key', 'to_reference_key', 'load_reference_state_dict'
 
 
 def _decoder_from_ref(rest: str, out_sc, kind: str = 'monodepth'):
-    if kind == 'diffnet': return None                      # (the reference's own names)
+    if kind in ('diffnet', 'superdepth'): return None      # (the reference's own names)
     if kind == 'cadepth':
         m = re.fullmatch(r'decoder\.(\d+)\.(.*)', rest)
         if not m: return None
@@ -60,7 +62,7 @@ def _decoder_from_ref(rest: str, out_sc, kind: str = 'monodepth'):
 
 
 def _decoder_to_ref(rest: str, out_sc, kind: str = 'monodepth'):
-    if kind == 'diffnet': return None
+    if kind in ('diffnet', 'superdepth'): return None
     if kind == 'cadepth':
         m = re.fullmatch(r'up([01])\.(\d)\.0\.(weight|bias)', rest)
         if m: return f'decoder.{3*(4 - int(m.group(2))) + int(m.group(1))}.conv.{m.group(3)}'
@@ -148,6 +150,7 @@ def _dec_kind(module: nn.Module) -> str:
     """Which decoder the module holds (a DepthNet builds its disparity and its mask decoder from one registry key)."""
     if any(hasattr(m, 'de') and hasattr(m, 'up0') for m in module.modules()): return 'cadepth'
     if any(isinstance(getattr(m, 'convs', None), nn.ModuleDict) and 'upconv_4' in m.convs and hasattr(m, 'decoder') for m in module.modules()): return 'diffnet'
+    if any(isinstance(getattr(m, 'convs', None), dict) and 'upconv_4_0' in m.convs and hasattr(m, 'decoder') for m in module.modules()): return 'superdepth'
     return 'ddvnet' if any(hasattr(m, 'bins') and hasattr(m, 'up0') for m in module.modules()) else 'monodepth'
 
 

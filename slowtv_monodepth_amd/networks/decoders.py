@@ -1,6 +1,7 @@
 """Monodepth(2) decoder — registry key `monodepth` (reference: `src/networks/decoders/monodepth.py:14-89`) — and the CADepth decoder built on it —
 registry key `cadepth` (reference: `src/networks/decoders/cadepth.py`) — and the DDVNet decoder — registry key `ddvnet` (reference:
-`src/networks/decoders/ddvnet.py`) — and the DiffNet decoder — registry key `diffnet` (reference: `src/networks/decoders/diffnet.py`)."""
+`src/networks/decoders/ddvnet.py`) — and the DiffNet decoder — registry key `diffnet` (reference: `src/networks/decoders/diffnet.py`) — and the SuperDepth
+decoder — registry key `superdepth` (reference: `src/networks/decoders/superdepth.py`)."""
 from __future__ import annotations
 
 import contextlib
@@ -12,7 +13,8 @@ import torch.nn.functional as F
 
 from ..registry import register
 
-__all__ = ['MonodepthDecoder', 'CaDepthDecoder', 'DetailEmphasis', 'DDVNetDecoder', 'SelfAttentionBlock', 'DiffNetDecoder', 'AttentionBlock', 'ChannelAttention', 'ACT']
+__all__ = ['MonodepthDecoder', 'CaDepthDecoder', 'DetailEmphasis', 'DDVNetDecoder', 'SelfAttentionBlock', 'DiffNetDecoder', 'AttentionBlock', 'ChannelAttention', 'SuperdepthDecoder',
+           'SubPixelConv', 'ACT']
 
 ACT = {'sigmoid': nn.Sigmoid(), 'relu': nn.ReLU(inplace=True), 'none': nn.Identity(), None: nn.Identity()}
 
@@ -411,3 +413,121 @@ class DiffNetDecoder(nn.Module):
                 if i in self.out_sc or i > 0: xp = HF.elu_pad(c, bias=m1.bias, apply_elu=True)
             if i in self.out_sc: out[i] = MonodepthDecoder._head_stencil(self, self.convs[f'outconv_{i}'], xp)
         return out
+
+
+class SubPixelConv(nn.Module):
+    """Sub-pixel convolution (src/networks/decoders/superdepth.py:13-26): a depth-wise 3x3 convolution that makes `up_factor**2` channels of every input
+    channel, then `PixelShuffle(up_factor)`.  The reference's initialisation: zero bias, and the rows of the weight equal in groups of FOUR (its literal 4,
+    whatever `up_factor` is).  Same sub-module names as the reference's."""
+    def __init__(self, ch_in: int, up_factor: int):
+        super().__init__()
+        self.up_factor = up_factor
+        self.conv = nn.Conv2d(ch_in, ch_in*up_factor**2, kernel_size=(3, 3), groups=ch_in, padding=1)
+        self.shuffle = nn.PixelShuffle(up_factor)
+        self.init_weights()
+
+    def init_weights(self):
+        nn.init.zeros_(self.conv.bias)
+        self.conv.weight = nn.Parameter(self.conv.weight[::4].repeat_interleave(4, 0))
+
+    def forward(self, x):
+        return self.shuffle(self.conv(x))
+
+
+@register('superdepth')
+class SuperdepthDecoder(nn.Module):
+    """SuperDepth (https://arxiv.org/abs/1806.01260; reference: src/networks/decoders/superdepth.py:29-118): the Monodepth stages (256..16 channels) with a
+    `SubPixelConv(2)` + ReLU where Monodepth up-samples, and heads that shuffle scale i up by `2**i`: EVERY head returns a full-resolution map (the
+    reference's behaviour).  Same constructor arguments, sub-module names and registration as the reference — `convs` is a plain `OrderedDict`, only
+    `decoder`, a ModuleList of its values, is registered — so its state dict IS the reference's (`decoder.N.*` alone): `networks/checkpoint.py` passes the
+    names through.  `upsample_mode` is accepted and, as in the reference, unused.
+
+    On CUDA (fp32) everything between a stage's two convolutions — ELU, the depth-wise convolution, the shuffle, ReLU, the concatenation with the encoder
+    feature, the reflection padding — is `functional.subpixel_conv`, one pass from the raw convolution output to the next convolution's padded input; the
+    heads of scales 1..3 are `conv3x3_headn` and `subpixel_conv` with the output activation, the head of scale 0 is the Monodepth stencil.  The plain ATen path
+    (the reference's sequence) serves the CPU, fp16 autocast, `upsample_mode != 'nearest'`, `plain_path()`, and the heads with more than four channels.
+
+    Precision: on CUDA the glued path computes in fp32, also under bf16 autocast (the rule `CaDepthDecoder` and `DiffNetDecoder` follow): it then takes fp32
+    time and returns fp32 disparities while the encoder around it runs in bf16.  Autocast to fp16 takes the plain ATen path."""
+
+    def __init__(self, num_ch_enc, enc_sc, upsample_mode: str = 'nearest', use_skip: bool = True,
+                 out_sc=(0, 1, 2, 3), out_ch: int = 1, out_act: str = 'sigmoid'):
+        super().__init__()
+        if out_act not in ACT: raise KeyError(f'Invalid activation key. ({out_act} vs. {tuple(ACT.keys())}')
+        self.num_ch_enc, self.enc_sc = list(num_ch_enc), list(enc_sc)
+        self.upsample_mode, self.use_skip, self.out_sc, self.out_ch, self.out_act = upsample_mode, use_skip, list(out_sc), out_ch, out_act
+        self.activation = ACT[out_act]
+        self.num_ch_dec = [16, 32, 64, 128, 256]
+        self.convs = OrderedDict()
+        for i in range(4, -1, -1):
+            cin, cout = (self.num_ch_enc[-1] if i == 4 else self.num_ch_dec[i + 1]), self.num_ch_dec[i]
+            self.convs[f'upconv_{i}_0'] = nn.Sequential(conv_block(cin, cout), SubPixelConv(cout, up_factor=2), nn.ReLU(inplace=True))
+            cin = cout + (self.num_ch_enc[self.enc_sc.index(2**i)] if self._has_skip(i) else 0)
+            self.convs[f'upconv_{i}_1'] = conv_block(cin, cout)
+        for i in self.out_sc:
+            if i == 0: self.convs[f'outconv_{i}'] = nn.Sequential(conv3x3(self.num_ch_dec[i], out_ch), self.activation)
+            else: self.convs[f'outconv_{i}'] = nn.Sequential(conv_block(self.num_ch_dec[i], out_ch), SubPixelConv(out_ch, up_factor=2**i), self.activation)
+        self.decoder = nn.ModuleList(list(self.convs.values()))
+        self._glued = True
+
+    def _has_skip(self, i: int) -> bool: return self.use_skip and 2**i in self.enc_sc
+
+    @property
+    def act(self): return self.activation      # (the name `MonodepthDecoder._head_stencil` reads)
+
+    @contextlib.contextmanager
+    def plain_path(self):
+        """Within the block THIS decoder evaluates its plain ATen path wherever its tensors live (the yardstick the glued path is compared and timed against)."""
+        prev, self._glued = self._glued, False
+        try: yield self
+        finally: self._glued = prev
+
+    def forward(self, feat):
+        x = feat[-1]
+        amp_bf16 = torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
+        if self._glued and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and (amp_bf16 or not torch.is_autocast_enabled()) and self.upsample_mode == 'nearest':
+            with torch.autocast('cuda', enabled=False): return self._forward_glued([f.float() for f in feat])
+        out = {}
+        for i in range(4, -1, -1):
+            x = [self.convs[f'upconv_{i}_0'](x)]
+            if self._has_skip(i): x += [feat[self.enc_sc.index(2**i)]]
+            x = self.convs[f'upconv_{i}_1'](torch.cat(x, 1))
+            if i in self.out_sc: out[i] = self.convs[f'outconv_{i}'](x)
+        return out
+
+    def _act_name(self):
+        return 'sigmoid' if isinstance(self.activation, nn.Sigmoid) else ('relu' if isinstance(self.activation, nn.ReLU) else None)
+
+    def _forward_glued(self, feat):
+        """Same network, same parameters, fp32.  Per stage: the routed bias-free convolution on the padded input, `subpixel_conv` (its bias and ELU, the
+        sub-pixel convolution, ReLU, the skip, the padding), the second routed convolution, `elu_pad`, whose output the head and the next stage share."""
+        from .. import functional as HF
+        conv = MonodepthDecoder._conv_glued
+        out = {}
+        xp = HF.elu_pad(feat[-1], apply_elu=False)
+        for i in range(4, -1, -1):
+            m0, sp, m1 = self.convs[f'upconv_{i}_0'][0].conv, self.convs[f'upconv_{i}_0'][1].conv, self.convs[f'upconv_{i}_1'].conv
+            skip = feat[self.enc_sc.index(2**i)] if self._has_skip(i) else None
+            xin = HF.subpixel_conv(conv(m0, xp), sp.weight, sp.bias, 2, pre_bias=m0.bias, pre_act='elu', act='relu', skip=skip, pad=True)
+            c = conv(m1, xin)
+            if i in self.out_sc or i > 0: xp = HF.elu_pad(c, bias=m1.bias, apply_elu=True)
+            if i in self.out_sc: out[i] = self._head_glued(i, xp)
+        return out
+
+    # Static routing of the heads' sub-pixel convolution by up-sampling factor, from profiles/superdepth_times.txt (b = 12 at 192 x 640, one channel, kernel vs
+    # ATen): forward alone the kernel wins at every factor (r = 2: 0.017 vs 0.048 ms, r = 4: 0.018 vs 0.047, r = 8: 0.017 vs 0.046); forward + backward r = 2 wins
+    # (0.097 vs 0.170), r = 4 ties (0.181 vs 0.179, at a third of the peak memory) and r = 8 loses (0.575 vs 0.150: the input-gradient gather sums 9 r^2 = 576
+    # terms a pixel on a one-channel tensor too small to fill the device).  r >= 8 goes to ATen whenever a gradient may be asked for.
+    @staticmethod
+    def _head_plain(r): return r >= 8 and torch.is_grad_enabled()
+
+    def _head_glued(self, i, xp):
+        """The head of scale i on the padded stage output: scale 0 is the Monodepth stencil; scale i > 0 with at most four channels is the n-channel stencil
+        (bias included, no activation) and `subpixel_conv` with the ELU in front and the output activation behind; wider heads, and the r = 8 head while gradients are recorded (`_head_plain`), run on ATen."""
+        from .. import functional as HF
+        m = self.convs[f'outconv_{i}']
+        if i == 0: return MonodepthDecoder._head_stencil(self, m[0], xp)
+        if 1 <= self.out_ch <= 4 and isinstance(self.activation, (nn.Sigmoid, nn.ReLU, nn.Identity)) and not self._head_plain(2**i):
+            raw = HF.conv3x3_headn(xp, m[0].conv.weight, m[0].conv.bias, None)
+            return HF.subpixel_conv(raw, m[1].conv.weight, m[1].conv.bias, 2**i, pre_act='elu', act=self._act_name())
+        return self.activation(m[1](F.elu(F.conv2d(xp, m[0].conv.weight, m[0].conv.bias))))

@@ -113,6 +113,8 @@ class HipLossBackend:
         # sequence of the handlers' path that then runs): more supports than one pass takes, a single pyramid level; and any configuration that raised once
         n_supp, cfg_key = supp_imgs.shape[0], (supp_imgs.shape[0], len(depths.disps), tuple(imgs.shape), crit.use_min, crit.use_automask, intrinsics is not None, pose is not None)
         if n_supp > F.supports_per_pass() or len(depths.disps) < 2 or cfg_key in self._unserved: return None
+        # ... and more than one full-resolution level (the SuperDepth decoder: every head is full-resolution), which `loss_path_fused` declines
+        if sum(tuple(d.shape[-2:]) == tuple(imgs.shape[-2:]) for d in depths.disps) > 1: return None
         flags = F.recon_flags(crit.loss_name, crit.use_min, crit.use_automask)
         dl = [d.float() for d in depths.disps]
         if prepared is not None and not prepared.matches(imgs, supp_imgs, flags, [d.shape[-2] for d in dl], [d.shape[-1] for d in dl]): prepared = None
