@@ -555,6 +555,28 @@ int smd_subpixel_bwd(const float* x, const float* pre_bias, const float* weight,
                      int B, int C, int Cs, int h, int w, int r, int pre_act, int act, int pad, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Monodepth's flip-and-blend post-process (smd_blend.hip) — replaces `blend_stereo` (src/tools/geometry.py:94-129), the `flip` in front of it
+ * (src/core/predictors.py:83, src/networks/depth.py:148-156) and the disparity half of `to_scaled` behind it (src/tools/geometry.py:63-76), for every level
+ * of a pyramid in ONE launch:
+ *   m_l = ramp (ws[s],) = clamp(20 (linspace(0,1,w) - 0.05), 0, 1), built by the caller so that its bits are torch's; m_r[j] = m_l[w-1-j]; m_mu = (1 - m_l) - m_r
+ *   out = (m_r l + m_l r) + m_mu ((l + r)/2)           every product and sum rounded on its own, in ATen's order
+ *   out = scale out + offset                            with SMD_BLEND_SCALE: scale = 1/min - 1/max and offset = 1/max (0 without a maximum), each formed
+ *                                                       in double by the caller and rounded once to fp32, as ATen applies the reference's Python scalars
+ * l[s], r[s], out[s]: (planes, hs[s], ws[s]) fp32, contiguous; hs[s], ws[s] >= 1, S <= SMD_MAX_SCALES.  With SMD_BLEND_MIRROR r[s] is the prediction for the
+ * mirrored image as the network wrote it and column j reads r[s][.., w-1-j]: no flipped copy exists.  Without it r[s] is already flipped back.
+ * Backward (src/tools/geometry.py:121-126 differentiated): g_l[j] = k g[j] m_r[j] + (k g[j] m_mu[j])/2 and g_r[j'] = k g[j] m_l[j] + (k g[j] m_mu[j])/2 at
+ * j' = w-1-j with SMD_BLEND_MIRROR, else j; k = scale with SMD_BLEND_SCALE, else 1.  g_l, g_r: either array, or any entry, may be NULL (not both for every
+ * level).  Every output element is written once by one thread: no atomics, two runs are bit-equal.  No workspace.
+ * Pointers need only be 4-byte aligned: a four-column group moves as one 16-byte vector where every address it touches allows it, element by element
+ * elsewhere (so a width that is no multiple of 4 under SMD_BLEND_MIRROR, or rows that start off a 16-byte boundary, take the element path). */
+#define SMD_BLEND_MIRROR 0x1
+#define SMD_BLEND_SCALE 0x2
+int smd_flip_blend_fwd(const float* const* l, const float* const* r, const float* const* ramp, float* const* out, const int* hs, const int* ws,
+                       int S, int planes, int flags, float scale, float offset, void* stream);
+int smd_flip_blend_bwd(const float* const* g_out, const float* const* ramp, float* const* g_l, float* const* g_r, const int* hs, const int* ws,
+                       int S, int planes, int flags, float scale, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Pose / intrinsics prologue — one launch each instead of ~45 eager ATen launches.
  *
  * smd_pose_*: `T_from_AAt(aa, t)` (src/tools/geometry.py:181-209), followed by `T.inverse()` where invert[i] != 0

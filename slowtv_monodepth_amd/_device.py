@@ -48,13 +48,14 @@ def _aligned(t: torch.Tensor) -> torch.Tensor:
     return t if t.data_ptr() % ALIGN == 0 else t.clone(memory_format=torch.contiguous_format)
 
 
-def _check(name: str, t: torch.Tensor, shape=None) -> torch.Tensor:
+def _check(name: str, t: torch.Tensor, shape=None, align: bool = True) -> torch.Tensor:
+    """`align=False`: for an entry point that takes 4-byte aligned pointers (the header says so where one does), a contiguous storage-offset view goes as it is."""
     if not isinstance(t, torch.Tensor): raise TypeError(f'{name} must be a Tensor, got {type(t)}')
     if not t.is_cuda: raise RuntimeError(f'{name} must live on the GPU: the view-synthesis hot path has no CPU implementation')
     _tls.device = t.device
     if t.dtype != torch.float32: raise TypeError(f'{name} must be float32 (the loss path is fp32 only), got {t.dtype}')
     if shape is not None and tuple(t.shape) != tuple(shape): raise ValueError(f'{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}')
-    return _aligned(t)
+    return _aligned(t) if align else t.contiguous()
 
 
 def _check_fb(name: str, t: torch.Tensor, shape=None) -> torch.Tensor:

@@ -131,6 +131,8 @@ PROTOTYPES = {
     'smd_subpixel_workspace_bytes': (_sz, [_i]*7),
     'smd_subpixel_fwd': (_i, [_vp]*6 + [_i]*9 + [_vp]),
     'smd_subpixel_bwd': (_i, [_vp]*11 + [_sz] + [_i]*9 + [_vp]),
+    'smd_flip_blend_fwd': (_i, [_vp]*6 + [_i]*3 + [_f, _f, _vp]),
+    'smd_flip_blend_bwd': (_i, [_vp]*6 + [_i]*3 + [_f, _vp]),
     'smd_pose_fwd': (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     'smd_pose_bwd': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     'smd_intrinsics_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

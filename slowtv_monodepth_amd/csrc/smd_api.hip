@@ -1233,6 +1233,47 @@ int smd_subpixel_bwd(const float* x, const float* pre_bias, const float* weight,
 }
 
 // ------------------------------------------------------------------------------------------------
+// Monodepth's flip-and-blend post-process (smd_blend.hip): every level of a pyramid in one launch
+static int blend_fill(smd::BlendSet& bs, const float* const* ramp, const int* hs, const int* ws, int S, int planes, int flags) {
+  if (S < 1 || S > SMD_MAX_SCALES) return fail(SMD_E_INVALID, "S=%d outside [1, %d]", S, SMD_MAX_SCALES);
+  if (!ramp || !hs || !ws) return fail(SMD_E_INVALID, "null pointer");
+  if (planes < 1 || (flags & ~(SMD_BLEND_MIRROR | SMD_BLEND_SCALE))) return fail(SMD_E_INVALID, "invalid sizes planes=%d flags=0x%x", planes, flags);
+  for (int s = 0; s < S; ++s) {
+    if (hs[s] < 1 || ws[s] < 1) return fail(SMD_E_INVALID, "invalid sizes: level %d is %dx%d", s, hs[s], ws[s]);
+    if (!ramp[s]) return fail(SMD_E_INVALID, "null ramp pointer for level %d", s);
+  }
+  memset(&bs, 0, sizeof(bs));
+  if (smd::blend_plan(bs, hs, ws, S, planes) < 1) return fail(SMD_E_INVALID, "invalid sizes: a level of 2^31 elements or more");
+  for (int s = 0; s < S; ++s) bs.ramp[s] = ramp[s];
+  return SMD_OK;
+}
+int smd_flip_blend_fwd(const float* const* l, const float* const* r, const float* const* ramp, float* const* out, const int* hs, const int* ws,
+                       int S, int planes, int flags, float scale, float offset, void* stream) {
+  if (!l || !r || !out) return fail(SMD_E_INVALID, "null pointer");
+  smd::BlendSet bs;
+  if (int rc = blend_fill(bs, ramp, hs, ws, S, planes, flags)) return rc;
+  for (int s = 0; s < S; ++s) {
+    if (!l[s] || !r[s] || !out[s]) return fail(SMD_E_INVALID, "null pointer for level %d", s);
+    bs.a[s] = l[s]; bs.b[s] = r[s]; bs.o0[s] = out[s];
+  }
+  return check_launch(smd::launch_flip_blend_fwd(bs, flags, scale, offset, (hipStream_t)stream), "flip_blend_fwd");
+}
+int smd_flip_blend_bwd(const float* const* g_out, const float* const* ramp, float* const* g_l, float* const* g_r, const int* hs, const int* ws,
+                       int S, int planes, int flags, float scale, void* stream) {
+  if (!g_out) return fail(SMD_E_INVALID, "null pointer");
+  smd::BlendSet bs;
+  if (int rc = blend_fill(bs, ramp, hs, ws, S, planes, flags)) return rc;
+  bool any = false;
+  for (int s = 0; s < S; ++s) {
+    if (!g_out[s]) return fail(SMD_E_INVALID, "null pointer for level %d", s);
+    bs.a[s] = g_out[s]; bs.o0[s] = g_l ? g_l[s] : nullptr; bs.o1[s] = g_r ? g_r[s] : nullptr;
+    any = any || bs.o0[s] || bs.o1[s];
+  }
+  if (!any) return fail(SMD_E_INVALID, "nothing to compute");
+  return check_launch(smd::launch_flip_blend_bwd(bs, flags, scale, (hipStream_t)stream), "flip_blend_bwd");
+}
+
+// ------------------------------------------------------------------------------------------------
 // Depthwise 7x7 convolution (ConvNeXt)
 static bool dw_sizes_ok(int N, int C, int H, int W) {
   return N >= 1 && C >= 1 && H >= 1 && W >= 1 && (long long)N*C*smd::dwconv_tiles(H, W) < (1ll << 31) && (long long)H*W < (1ll << 30);

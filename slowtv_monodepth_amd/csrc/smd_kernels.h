@@ -342,6 +342,21 @@ hipError_t launch_subpixel_fwd(const SubPixel& s, const float* x, const float* p
                                hipStream_t st);
 hipError_t launch_subpixel_bwd(const SubPixel& s, const float* x, const float* pre_bias, const float* weight, const float* out, const float* g_out, float* g_x,
                                float* g_pre_bias, float* g_weight, float* g_bias, float* g_skip, float* ws, hipStream_t st);
+// smd_blend.hip: Monodepth's flip-and-blend post-process over a pyramid in one launch.  Forward: a = l, b = r, o0 = out; backward: a = g_out, o0 = g_l, o1 = g_r
+// (either may be null).  A block is one unit of kBlendItems four-column groups of one level; unit0[s] is the first unit of level s, unit0[S] the grid size.
+constexpr int kBlendItems = 512;
+struct BlendSet {
+  const float* a[SMD_MAX_SCALES];
+  const float* b[SMD_MAX_SCALES];
+  float* o0[SMD_MAX_SCALES];
+  float* o1[SMD_MAX_SCALES];
+  const float* ramp[SMD_MAX_SCALES];
+  int rows[SMD_MAX_SCALES], w[SMD_MAX_SCALES], ng[SMD_MAX_SCALES], unit0[SMD_MAX_SCALES + 1];
+  int S;
+};
+long blend_plan(BlendSet& bs, const int* hs, const int* ws, int S, int planes);
+hipError_t launch_flip_blend_fwd(const BlendSet& bs, int flags, float scale, float offset, hipStream_t st);
+hipError_t launch_flip_blend_bwd(const BlendSet& bs, int flags, float scale, hipStream_t st);
 int bn_chunks(int N, int HW);
 hipError_t launch_bn_fwd(const float* x, const float* residual, const float* gamma, const float* beta, float* running_mean, float* running_var,
                          float momentum, float eps, int relu, float* y, float* save_mean, float* save_invstd, float* ws, int N, int C, int HW,

@@ -2,7 +2,7 @@
 
 `T_from_AAt` on GPU tensors is the `smd_pose_*` kernel pair (the training step goes through
 `functional.pose_matrices` / `functional.intrinsics` directly, which also fold in the inverse transforms and K^-1);
-on host tensors — dataset poses, fixtures — it is the same formula in PyTorch.  `to_scaled` / `to_inv` / `resize_K` /
+on host tensors — dataset poses, fixtures — it is the same formula in PyTorch.  `to_scaled` / `to_inv` / `blend_stereo` / `resize_K` /
 `build_K` are the reference's small helpers kept for API parity (the training step uses the K0 and intrinsics kernels).
 `ViewSynth` is the class-level drop-in whose forward/backward are HIP kernels (`smd_view_synth_*`).  The fused fast
 path (`handlers.image_recon`) never instantiates point clouds or sampling grids at all.
@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from . import ops
 
-__all__ = ['to_scaled', 'to_inv', 'T_from_AAt', 'resize_K', 'build_K', 'ViewSynth']
+__all__ = ['to_scaled', 'to_inv', 'blend_stereo', 'T_from_AAt', 'resize_K', 'build_K', 'ViewSynth']
 
 
 def to_inv(depth: torch.Tensor) -> torch.Tensor:
@@ -29,6 +29,22 @@ def to_scaled(disp: torch.Tensor, min: float = 0.01, max: float | None = 100) ->
     i_max, i_min = 1/min, (1/max) if max else 0
     disp = (i_max - i_min)*disp + i_min
     return disp, to_inv(disp)
+
+
+def blend_stereo(disp_l: torch.Tensor, disp_r: torch.Tensor) -> torch.Tensor:
+    """Monodepth's stereo blending of (*b,*1,h,w) disparities (src/tools/geometry.py:94-129): the 5 % leftmost columns from `disp_r` (the prediction for the
+    mirrored image, ALREADY flipped back), the 5 % rightmost from `disp_l`, the mean in between, over a smooth ramp.  float32 on the GPU runs the
+    `smd_flip_blend_*` kernel with its mirrored read switched off; everything else is the ATen sequence (`blend.plain_flip_blend`)."""
+    from .blend import flip_blend
+    s1, s2 = disp_l.shape, disp_r.shape
+    n = disp_l.ndim
+    if s1 != s2: raise ValueError(f'Non-matching shapes. ({s1} vs. {s2})')
+    if n == 2: disp_l, disp_r = disp_l[None, None], disp_r[None, None]
+    if n == 3: disp_l, disp_r = disp_l[None], disp_r[None]
+    disp = flip_blend(disp_l, disp_r, mirror=False)
+    if n == 2: disp = disp[0, 0]
+    if n == 3: disp = disp[0]
+    return disp
 
 
 def T_from_AAt(aa: torch.Tensor, t: torch.Tensor) -> torch.Tensor:

@@ -17,7 +17,8 @@ class DepthNet(nn.Module):
     masks {s: (b,num_ch_mask,h/2^s,w/2^s)} of a second decoder on the same features (src/networks/depth.py:108-114).
 
     Same constructor kwargs as the reference.  `mask_name`: 'explainability' (sigmoid heads) or 'uncertainty' (relu heads), one
-    channel per support frame.  Virtual stereo and stereo blending are not served and raise `NotImplementedError`.
+    channel per support frame.  Virtual stereo and stereo blending are not served by the constructor and raise `NotImplementedError`;
+    `forward_blended` is the blended forward as a method of its own.
     """
     def __init__(self, enc_name: str = 'resnet18', pretrained: bool = True, dec_name: str = 'monodepth', out_scales=(0, 1, 2, 3),
                  mask_name=None, num_ch_mask=None, use_virtual_stereo: bool = False, use_stereo_blend: bool = False):
@@ -47,4 +48,13 @@ class DepthNet(nn.Module):
         feat = self.encoder(x)
         out = {'depth_feats': feat}
         for k, dec in self.decoders.items(): out[k] = dict(sorted(dec(feat).items()))
+        return out
+
+    def forward_blended(self, x):
+        """`forward(x)` with every `disp*` pyramid blended with the prediction for the mirrored image: two passes, as the reference's `use_stereo_blend`
+        network runs them (src/networks/depth.py:148-156), and ONE `flip_blend_pyramid` call per pyramid, which reads the second pass's disparities
+        mirrored instead of flipping them back.  Differentiable; every other key is the first pass's."""
+        from ..blend import flip_blend_pyramid
+        out, mirrored = self.forward(x), self.forward(x.flip(dims=[-1]))
+        for k in [k for k in out if k.startswith('disp')]: out[k] = flip_blend_pyramid(out[k], mirrored[k])
         return out

@@ -12,7 +12,7 @@ import logging
 import torch.optim.lr_scheduler as sched
 
 __all__ = ['register', 'NET_REG', 'LOSS_REG', 'DATA_REG', 'SCHED_REG', 'PRED_REG', 'DEC_REG',
-           'trigger_nets', 'trigger_losses', 'trigger_decoders']
+           'trigger_nets', 'trigger_losses', 'trigger_decoders', 'trigger_preds']
 
 log = logging.getLogger('slowtv_monodepth_amd.registry')
 
@@ -66,3 +66,7 @@ def trigger_decoders() -> None:
 
 def trigger_losses() -> None:
     from . import losses, regularizers  # noqa: F401
+
+
+def trigger_preds() -> None:
+    from . import predictors  # noqa: F401
