@@ -73,8 +73,8 @@ int smd_abi_version(void);
  * same results: rows per strip, the tapered partition, shared LDS ring vs. per-wave loads in the forward, the backward's two row loops,
  * guest work vs. launches of their own.  They exist so that the parity tests can pin both sides of each such choice and compare; the
  * library never reads the environment.  Names: fwd_rh bwd_rh fwd_taper_b bwd_taper_b fwd_taper_rh bwd_taper_rh fwd_ni fwd_share bwd_skip
- * bwd_wps bwd_guest_finalize bwd_direct_level loss_path_guests bwd_live bwd_scales_block (and, in -DSMD_EXPERIMENTS builds only: fwd_ahead bwd_pair smooth_chain).
- * smd_set_knob: 0, SMD_E_INVALID for an unknown name, SMD_E_UNSUPPORTED for an experiments-only knob in the product build. */
+ * bwd_wps bwd_guest_finalize bwd_direct_level loss_path_guests bwd_live bwd_scales_block conv_two_tiles metrics_store_pred.
+ * smd_set_knob: 0, SMD_E_INVALID for a name that is not in this list. */
 int smd_set_knob(const char* name, int value);
 void smd_reset_knobs(void);
 
@@ -128,7 +128,7 @@ size_t smd_packed_supports_bytes(int b, int n, int h, int w);
  * pyramid of the K0-fused forward (its row table is built here); NULL / S = 0 for the depth-input forward. */
 int smd_image_recon_prep(const float* tgt, const float* supp, float* supp_packed, const int* hs, const int* ws, int S,
                          int b, int n, int h, int w, int flags, void* stream);
-/* Supports one forward launch holds in registers (4 unless SMD_FWD_NI overrides it): `err` may be NULL only when n <= this. */
+/* Supports one forward launch holds in registers (4 unless the knob fwd_ni overrides it): `err` may be NULL only when n <= this. */
 int smd_image_recon_supports_per_pass(void);
 int smd_image_recon_fwd(const float* depth, const float* tgt, const float* supp, const float* T, const float* K,
                         const float* K_inv, const float* noise, uint64_t seed, float* supp_packed, float* err, uint8_t* sel, float* loss,

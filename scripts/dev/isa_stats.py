@@ -18,7 +18,7 @@ def isa(src):
 def loop_stats(lines, key, rows_per_iter, what, nested=False):
     found = [i for i, l in enumerate(lines) if l.startswith(key)]
     if not found:
-        print(f'{what}\n  (not in this build: experiments-only kernels need -DSMD_EXPERIMENTS)\n'); return
+        print(f'{what}\n  (not in this build)\n'); return
     start = found[0]
     end = [i for i, l in enumerate(lines) if i > start and 's_endpgm' in l][0]
     body = lines[start:end]
@@ -73,18 +73,15 @@ def regs(lines, key):
 if __name__ == '__main__':
     f, bw = isa('smd_recon_fwd.hip'), isa('smd_recon_bwd.hip')
     print('Instruction statistics of the fused kernels\' row loops (hipcc ROCm 7.2, gfx950), produced by scripts/dev/isa_stats.py\n')
-    for key, what in (('_ZN3smd12k_recon_mainILi2ELb1ELb1ELb0ELb1ELi1ELb1EEE', 'k_recon_main<2, true, true, false, true, 1, true>  (two supports, K0 fused, shared target ring: the bench\'s forward kernel; the static count includes the once-per-four-rows epoch block)'),
-                      ('_ZN3smd12k_recon_mainILi2ELb1ELb1ELb0ELb1ELi1ELb0EEE', 'k_recon_main<2, true, true, false, true, 1, false> (the same without the shared ring: SMD_FWD_SHARE=0, or a pyramid that is not four scales)'),
-                      ('_ZN3smd12k_recon_mainILi2ELb1ELb1ELb0ELb0ELi1ELb0EEE', 'k_recon_main<2, true, true, false, false, 1, false> (two supports, depth read from a K0 launch)'),
-                      ('_ZN3smd12k_recon_mainILi4ELb1ELb1ELb0ELb1ELi1ELb1EEE', 'k_recon_main<4, true, true, false, true, 1, true>  (four supports, cfg 5)')):
+    for key, what in (('_ZN3smd12k_recon_mainILi2ELb1ELb1ELb0ELb1ELb1EEE', 'k_recon_main<2, true, true, false, true, true>  (two supports, K0 fused, shared target ring: the bench\'s forward kernel; the static count includes the once-per-four-rows epoch block)'),
+                      ('_ZN3smd12k_recon_mainILi2ELb1ELb1ELb0ELb1ELb0EEE', 'k_recon_main<2, true, true, false, true, false> (the same without the shared ring: knob fwd_share = 0, or a pyramid that is not four scales)'),
+                      ('_ZN3smd12k_recon_mainILi2ELb1ELb1ELb0ELb0ELb0EEE', 'k_recon_main<2, true, true, false, false, false> (two supports, depth read from a K0 launch)'),
+                      ('_ZN3smd12k_recon_mainILi4ELb1ELb1ELb0ELb1ELb1EEE', 'k_recon_main<4, true, true, false, true, true>  (four supports, cfg 5)')):
         loop_stats(f, key, 2, what); print('  ' + regs(f, key) + '\n')
     for key, what in (('_ZN3smd11k_recon_bwdILb1ELi0ELi2ELb1ELb0EEE', 'k_recon_bwd<true, 0, 2, true, false> (one support per wave, plain row loop: the steady-state body of the peeled pipeline, every row does the full adjoint)'),
                       ('_ZN3smd11k_recon_bwdILb1ELi2ELi2ELb1ELb0EEE', 'k_recon_bwd<true, 2, 2, true, false> (one support per wave, liveness-gated row loop; the static count includes the clear / dead-row paths)'),
                       ('_ZN3smd11k_recon_bwdILb1ELi0ELi4ELb1ELb0EEE', 'k_recon_bwd<true, 0, 4, true, false> (cfg 5: four supports, one per wave)')):
         loop_stats(bw, key, 3, what, nested=True); print('  ' + regs(bw, key) + '\n')
-    key = '_ZN3smd16k_recon_bwd_pairILb1ELi1EEE'
-    loop_stats(bw, key, 3, 'k_recon_bwd_pair<true, 1> (experiment: TWO supports per wave, per row step and PAIR; "vector memory" includes the scratch instructions of its spills)', nested=False)
-    print('  ' + regs(bw, key) + '\n')
     print('History (same method): round 1 forward 425 per row for two supports; backward 421 per support row step at the start of round 2 (73 of them v_mov),\n'
           '328 after the (row mod 3) slot rewrite, 300 / 313 at the end of round 2; round 3 left the backward\'s row loop as it was (301 / 313: the launch structure changed).\n'
           'Forward with the shared target ring: of the 16 vector-memory instructions counted per row step, 3 are the LDS-DMA pieces of the epoch block, which runs once\n'

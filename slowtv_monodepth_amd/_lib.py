@@ -182,12 +182,11 @@ def call(name: str, *args):
 
 def set_knob(name: str, value: int) -> bool:
     """Pin a launch-shape knob of the library (`smd_set_knob`: partitions / code paths that must give identical results; the parity tests
-    compare both sides).  -> False if this build does not have the knob (experiments-only), ValueError for an unknown name."""
+    compare both sides).  -> True; ValueError for a name the library does not know."""
     global knob_epoch
-    rc = lib.smd_set_knob(name.encode(), int(value))
-    if rc == -1: raise ValueError(lib.smd_last_error().decode())
+    if lib.smd_set_knob(name.encode(), int(value)) != 0: raise ValueError(lib.smd_last_error().decode())
     knob_epoch += 1
-    return rc == 0
+    return True
 
 
 def reset_knobs() -> None:

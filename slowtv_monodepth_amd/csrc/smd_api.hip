@@ -39,8 +39,7 @@ int max_strips(int h, int w, int cols) { return smd::ceil_div(w, cols)*smd::ceil
 
 // Launch-shape knobs (smd_set_knob; unset = the built-in heuristics).  They select between partitions / code paths that must give the same
 // results — the parity tests pin them to prove exactly that (tapered vs. plain partition, shared ring vs. per-wave loads, the two row loops
-// of the backward) — and are NOT read from the environment: nothing on the call path calls getenv.  (A -DSMD_EXPERIMENTS build additionally
-// seeds them from SMD_<NAME> environment variables once, for the scripts under scripts/dev.)
+// of the backward) — and are NOT read from the environment: nothing in the library calls getenv.
 //   fwd_rh / bwd_rh rows per strip (>= 4); fwd_taper_b / bwd_taper_b samples at the end of the dispatch order that get short strips (0: none)
 //   and fwd_taper_rh / bwd_taper_rh their height; fwd_ni supports per forward launch (1..4); fwd_share (default 1: with four scales a block
 //   of the hot forward is the four scales of one strip and the target-side rows reach it through an LDS ring); bwd_skip (0 / 2: the
@@ -52,33 +51,17 @@ int max_strips(int h, int w, int cols) { return smd::ceil_div(w, cols)*smd::ceil
 //   them; default 0: measured neutral, profiles/r06_conv_mfma_ablations.txt; same bits either way).
 //   metrics_store_pred (default 1: smd_depth_metrics writes the resampled prediction to its workspace in the first pass and re-reads it; 0: every pass
 //   recomputes the four taps at the valid pixels; same bits either way; 86 vs 104 us at b = 12, 375x1242, 5 % density: profiles/val_metrics_times.txt).
-//   Experiments builds only: fwd_ahead (2: tap gathers two rows ahead, measured slower), bwd_pair (two supports per wave, dropped), smooth_chain.
-struct KnobDef { const char* name; bool experiment; };
-constexpr KnobDef kKnobs[] = {{"fwd_rh", false}, {"bwd_rh", false}, {"fwd_taper_b", false}, {"bwd_taper_b", false}, {"fwd_taper_rh", false},
-                              {"bwd_taper_rh", false}, {"fwd_ni", false}, {"fwd_share", false}, {"bwd_skip", false}, {"bwd_wps", false},
-                              {"bwd_guest_finalize", false}, {"bwd_direct_level", false}, {"loss_path_guests", false}, {"bwd_live", false}, {"bwd_scales_block", false}, {"conv_two_tiles", false}, {"metrics_store_pred", false},
-                              {"fwd_ahead", true}, {"bwd_pair", true}, {"smooth_chain", true}};
+constexpr const char* kKnobs[] = {"fwd_rh", "bwd_rh", "fwd_taper_b", "bwd_taper_b", "fwd_taper_rh", "bwd_taper_rh", "fwd_ni", "fwd_share", "bwd_skip", "bwd_wps",
+                                  "bwd_guest_finalize", "bwd_direct_level", "loss_path_guests", "bwd_live", "bwd_scales_block", "conv_two_tiles", "metrics_store_pred"};
 constexpr int kNumKnobs = sizeof(kKnobs)/sizeof(kKnobs[0]);
 constexpr int kKnobUnset = INT_MIN;
 struct KnobTable {
   int v[kNumKnobs];
-  KnobTable() {
-    for (int i = 0; i < kNumKnobs; ++i) v[i] = kKnobUnset;
-#ifdef SMD_EXPERIMENTS
-    for (int i = 0; i < kNumKnobs; ++i) {   // once, at load time: SMD_FWD_RH=12 etc. for the dev scripts
-      char env[64] = "SMD_";
-      size_t k = 4;
-      for (const char* c = kKnobs[i].name; *c && k + 1 < sizeof(env); ++c) env[k++] = (char)((*c >= 'a' && *c <= 'z') ? *c - 32 : *c);
-      env[k] = 0;
-      const char* e = getenv(env);
-      if (e && *e) v[i] = atoi(e);
-    }
-#endif
-  }
+  KnobTable() { for (int i = 0; i < kNumKnobs; ++i) v[i] = kKnobUnset; }
 };
 KnobTable g_knobs;
 int knob_index(const char* name) {
-  for (int i = 0; i < kNumKnobs; ++i) if (strcmp(kKnobs[i].name, name) == 0) return i;
+  for (int i = 0; i < kNumKnobs; ++i) if (strcmp(kKnobs[i], name) == 0) return i;
   return -1;
 }
 int knob(const char* name, int dflt) {
@@ -91,7 +74,7 @@ StripPlan plan(int b, int S, int h, int w, int cols) {
   p.rh = smd::pick_rows_per_strip(b, S, h, w, cols, 0);
   const int ov = knob(cols == smd::kFwdCols ? "fwd_rh" : "bwd_rh", 0);
   if (ov >= 1) p.rh = ov < kMinStripRows ? kMinStripRows : ov;
-  if (cols == smd::kFwdCols && p.rh > 58) p.rh = 58;   // the K0-fused forward keeps the strip's rh + 3 + look-ahead row-table entries one per lane
+  if (cols == smd::kFwdCols && p.rh > 58) p.rh = 58;   // the K0-fused forward keeps the strip's rh + 4 row-table entries one per lane
   p.nsx = smd::ceil_div(w, cols);
   p.nsy = smd::ceil_div(h, p.rh);
   return p;
@@ -100,7 +83,7 @@ StripPlan plan(int b, int S, int h, int w, int cols) {
 // Tapered partition of the fused kernels (smd_kernels.h: ReconMainArgs::b1): the last `b2` samples of the dispatch order get
 // strips of `rh2` = rh/2 rows.  A launch is two to three "generations" of waves on the 4096 wave slots of the chip and a wave
 // lives 30-40 us, so with equal units the last ones dispatched run almost alone for tens of microseconds (wave traces:
-// scripts/dev/wave_trace.py; time-averaged occupancy 2.96 -> 3.19 waves per SIMD with the taper, forward 93 -> 87-89 us at
+// profiles/r04_fwd_wave_traces.txt; time-averaged occupancy 2.96 -> 3.19 waves per SIMD with the taper, forward 93 -> 87-89 us at
 // cfg 2).  Default: a sixth of the batch, when the batch has at least four samples; the knobs *_taper_b / *_taper_rh override (b = 0: off).
 void taper(int& b1, int& rh2, int& nsy2, int b, int h, const StripPlan& pl, const char* env_b, const char* env_rh) {
   int b2 = knob(env_b, -1), r2 = knob(env_rh, -1);
@@ -208,9 +191,6 @@ int smd_abi_version(void) { return SMD_ABI_VERSION; }
 int smd_set_knob(const char* name, int value) {
   const int i = name ? knob_index(name) : -1;
   if (i < 0) return fail(SMD_E_INVALID, "unknown knob '%s'", name ? name : "(null)");
-#ifndef SMD_EXPERIMENTS
-  if (kKnobs[i].experiment) return fail(SMD_E_UNSUPPORTED, "knob '%s' exists in -DSMD_EXPERIMENTS builds only", name);
-#endif
   g_knobs.v[i] = value;
   return SMD_OK;
 }
@@ -338,7 +318,6 @@ static int recon_fwd_impl(const float* depth, float* depth_out, const smd::Scale
     a.comb = lp->comb;
     if (lp->guests) { a.sm = lp->job; a.guest_blocks = smd::smooth_main_blocks(a.sc, b); }
   }
-  a.lookahead = knob("fwd_ahead", 1) == 2 ? 2 : 1;
   a.share = (knob("fwd_share", 1) != 0 && a.S == 4 && a.rh % 4 == 0 && (a.b1 >= a.b || a.rh2 % 4 == 0)) ? 1 : 0;
   for (int i0 = 0; i0 < n; i0 += kMaxPerPass) {
     a.i0 = i0; a.ni = (n - i0 < kMaxPerPass) ? n - i0 : kMaxPerPass;
@@ -442,12 +421,6 @@ static int recon_bwd_impl(const float* depth, float* supp_packed, const float* T
   const int spb = smd::kWavesPerBlock/a.wps;
   a.scales_block = (n > 1 && S == 4 && smd::kWavesPerBlock == 4 && (spb == 2 || spb == 4) && (pl.nsx*pl.nsy) % spb == 0
                     && (a.b1 >= b || (pl.nsx*a.nsy2) % spb == 0) && knob("bwd_scales_block", 1) != 0) ? 1 : 0;
-#ifdef SMD_EXPERIMENTS
-  // Two supports per wave (knob bwd_pair; experiment of round 4): the strips of a block must be those of the one-support-per-wave kernel
-  // with wps = n, so that the K0-adjoint guest epilogue finds the same per-block pose entries.
-  a.pair = (knob("bwd_pair", 0) != 0 && (n == 2 || n == 4) && (flags & SMD_USE_MIN) && a.skip_level == 0) ? 1 : 0;
-  if (a.pair) a.wps = n;
-#endif
   if (guest) {   // the caller's next launch finalises the pose sums: no in-launch hand-off (the kernel skips it when `arrive` is null)
     a.arrive = nullptr;
     const int spb = smd::kWavesPerBlock/a.wps;

@@ -5,20 +5,6 @@
 // kernels: one wave owns a 64-column strip and streams down the rows, so the 3x3 windows live in registers
 // (horizontal taps = neighbouring lanes, vertical taps = forward-accumulated row sums).
 #pragma once
-// Experiment / diagnosis switches (ablations, wave traces, dropped kernel variants, launch-shape knobs read from the environment) exist
-// only in -DSMD_EXPERIMENTS builds (`make EXPERIMENTS=1`; scripts/dev builds those).  The product library ignores them.
-#ifndef SMD_EXPERIMENTS
-#undef SMD_ABLATE
-#undef SMD_ABLATE_BWD
-#undef SMD_FWD_PRIO
-#undef SMD_BWD_FASTPATH
-#undef SMD_NO_DPP
-#undef SMD_BWD_PEEL
-#undef SMD_BWD_ROWSEL
-#undef SMD_BWD_STATEFUL
-#undef SMD_FWD_CAM_REGS
-#undef SMD_TRACE_WAVES
-#endif
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
@@ -54,20 +40,10 @@ typedef float f3 __attribute__((ext_vector_type(3)));               // one RGB t
 //   lane_right(x)[l] = x[l+1]  (0 for lane 63)
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ float lane_left(float x) {
-#ifdef SMD_NO_DPP
-  float v = __shfl_up(x, 1, 64);
-  return (threadIdx.x & 63) == 0 ? 0.f : v;
-#else
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x138 /*wave_shr:1*/, 0xf, 0xf, true));
-#endif
 }
 __device__ __forceinline__ float lane_right(float x) {
-#ifdef SMD_NO_DPP
-  float v = __shfl_down(x, 1, 64);
-  return (threadIdx.x & 63) == 63 ? 0.f : v;
-#else
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x130 /*wave_shl:1*/, 0xf, 0xf, true));
-#endif
 }
 
 // Weighted horizontal 3-tap: q + wl*q[l-1] + wr*q[l+1].  With (wl, wr) = reflect_weights() this is the
@@ -333,21 +309,14 @@ __device__ __forceinline__ void bst4(rsrc_t r, unsigned voff, unsigned soff, f4 
 #define SMD_DPP_SHR " wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
 #define SMD_DPP_SHL " wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
 __device__ __forceinline__ void hsum2(float a, float b, float& ra, float& rb) {
-#ifdef SMD_NO_DPP
-  ra = (a + lane_left(a)) + lane_right(a); rb = (b + lane_left(b)) + lane_right(b);
-#else
   asm volatile("s_nop 1\n\t"
                "v_add_f32_dpp %0, %2, %2" SMD_DPP_SHR
                "v_add_f32_dpp %1, %3, %3" SMD_DPP_SHR
                "v_add_f32_dpp %0, %2, %0" SMD_DPP_SHL
                "v_add_f32_dpp %1, %3, %1" SMD_DPP_SHL
                : "=&v"(ra), "=&v"(rb) : "v"(a), "v"(b));
-#endif
 }
 __device__ __forceinline__ void hsum3(float a, float b, float c, float& ra, float& rb, float& rc) {
-#ifdef SMD_NO_DPP
-  ra = (a + lane_left(a)) + lane_right(a); rb = (b + lane_left(b)) + lane_right(b); rc = (c + lane_left(c)) + lane_right(c);
-#else
   asm volatile("s_nop 1\n\t"
                "v_add_f32_dpp %0, %3, %3" SMD_DPP_SHR
                "v_add_f32_dpp %1, %4, %4" SMD_DPP_SHR
@@ -356,7 +325,6 @@ __device__ __forceinline__ void hsum3(float a, float b, float c, float& ra, floa
                "v_add_f32_dpp %1, %4, %1" SMD_DPP_SHL
                "v_add_f32_dpp %2, %5, %2" SMD_DPP_SHL
                : "=&v"(ra), "=&v"(rb), "=&v"(rc) : "v"(a), "v"(b), "v"(c));
-#endif
 }
 
 // SSIM error of one channel from UN-normalised (x9) window sums: ssim = N/D with N and D both scaled by 81*81.

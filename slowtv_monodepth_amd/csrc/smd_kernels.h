@@ -130,7 +130,6 @@ struct ReconMainArgs {     // k_recon_main: warp + SSIM/L1 + min/mean over suppo
   float inv_n;
   uint32_t seed_lo, seed_hi;
   int first_pass, last_pass;
-  int lookahead;           // 1 or 2 row steps between a tap gather and its first use (2: the hot K0-fused instantiation with N <= 2 only)
   int share;               // 1: a block is the FOUR scales of one strip and the target-side rows reach them through one LDS ring (S == 4, strip heights multiples of 4)
   // Fused loss path (K0-fused single-pass instantiations only): blocks [main_blocks, main_blocks + guest_blocks) of the grid are GUEST blocks
   // running the smoothness sweep over `sc` (sm); comb: the reconstruction loss also takes part in the in-launch weighted sum.
@@ -162,7 +161,6 @@ struct ReconBwdArgs {
   int scales_block;       // wps == 1, S == 4: a block is the four SCALES of one strip (they read the same target-side rows and gather near the same texels) instead of four strips of one scale
   float wscale, hscale;
   int skip_level;         // 0..2, see k_recon_bwd
-  int pair;               // 1: two supports per wave (k_recon_bwd_pair; n = 2 or 4, min-reprojection, plain row loop)
   const unsigned* live;   // the forward's liveness table (smd_kernels.h: packed_live_offset_floats), or null: every wave runs its row loop
   int fwd_rh, fwd_b1, fwd_rh2;   // ... and the forward's partition: rows per forward strip of the first fwd_b1 samples / of the rest (the table is indexed by forward strips)
   float* g_direct;        // K0 fused: rows of scale `direct_scale` (a pyramid level that already has the image size: its K0 adjoint is the

@@ -1,8 +1,8 @@
 // smd_recon_bwd.hip — hand-written adjoint of the fused view-synthesis photometric loss (gfx950).
 //
 // Same wave-strip streaming as the forward (smd_recon_fwd.hip): 60 interior columns + 2 halo lanes per side, rows
-// r0-2 .. r1+1, one support per wave (the state of one support is ~90 registers; two at once were built in round 4 —
-// k_recon_bwd_pair below — and are slower: profiles/r04_pair_backward.txt).  Since round 3 the supports of a strip are handled by
+// r0-2 .. r1+1, one support per wave (the state of one support is ~90 registers; two at once were built in round 4, were
+// slower and are gone: profiles/r04_pair_backward.txt).  Since round 3 the supports of a strip are handled by
 // DIFFERENT waves of one block, concurrently (n = 2: a block is 2 strips x 2 supports): a work unit is half as long (a launch is only
 // ~3 generations of waves, so its tail is a fraction of a unit), the waves of a strip pull the same target-side rows (`sel`, target
 // pixel, window terms, depth) through one L1, and the per-pixel sum of dL/d depth over the supports is formed once, from LDS, by the
@@ -23,14 +23,10 @@
 #include "smd_kernels.h"
 #include "smd_pose_fin.h"
 
-// The row-loop variants (plain / gated, and whatever the experiment switches select) promise the SAME gradients bit for bit: every
+// The row-loop variants (plain / gated) promise the SAME gradients bit for bit: every
 // fused multiply-add in this file is written as one (fmaf); left to -ffp-contract=fast the compiler decides per instantiation which
 // a*b + c it fuses, and two instantiations of the same source then differ in the last bit.
 #pragma clang fp contract(off)
-
-#ifndef SMD_ABLATE_BWD
-#define SMD_ABLATE_BWD 0   // diagnosis builds only (scripts/dev/ablate_bwd.sh): bit 0 no tap gathers, bit 1 no row loads, bit 2 no g_depth traffic, bit 3 no LDS
-#endif
 
 namespace smd {
 
@@ -38,9 +34,6 @@ namespace smd {
 // v_mul_dpp + v_fmac_dpp (the shift rides on the multiply's first operand) + a plain add; pure outputs, so the results land
 // directly in the caller's registers.  One hazard nop covers all of them.
 __device__ __forceinline__ void hsum_w3(float a, float b, float c, float wl, float wr, float& ra, float& rb, float& rc) {
-#ifdef SMD_NO_DPP
-  ra = hsum3(a, wl, wr); rb = hsum3(b, wl, wr); rc = hsum3(c, wl, wr);
-#else
   float ta, tb, tc;
   asm volatile("s_nop 1\n\t"
                "v_mul_f32_dpp %0, %3, %6 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
@@ -52,7 +45,6 @@ __device__ __forceinline__ void hsum_w3(float a, float b, float c, float wl, flo
                : "=&v"(ta), "=&v"(tb), "=&v"(tc)
                : "v"(a), "v"(b), "v"(c), "v"(wl), "v"(wr));
   ra = ta + a; rb = tb + b; rc = tc + c;
-#endif
 }
 
 // Select between two wave-uniform floats on the scalar unit (a float ?: would be a v_cndmask per use).
@@ -79,24 +71,13 @@ __device__ __forceinline__ float usel(bool c, float x, float y) {
 constexpr int kHist = 7;   // values per lane and row slot of the LDS history: dx/dsx[3], dx/dsy[3], depth
 constexpr int kSelBatch = 10;   // `sel` rows requested at once by the prologue (8 + 2 rows of a tapered strip in one batch, 16 + 2 in two)
 
-// Experiment switches of the row loop (scripts/dev/bwd_lib_variants.sh builds one library per combination; the defaults are what won):
-#ifndef SMD_BWD_PEEL
-#define SMD_BWD_PEEL 1       // 1: the pipeline's fill (two A-only steps, two A+B steps) is peeled off and the steady-state body has no range checks
-#endif
-#ifndef SMD_BWD_ROWSEL
-#define SMD_BWD_ROWSEL 1     // the plain loop (SKIP = 0) reads `sel` one row per step, as part of the row's loads, instead of scanning the strip up front
-#endif
-#ifndef SMD_BWD_STATEFUL
-#define SMD_BWD_STATEFUL 0   // the plain loop keeps sliding vertical sums P = r(j-2) + r(j-1) (the forward's scheme) instead of re-adding three raw rows
-#endif
-
 // XTRA: the instantiation also serves the two rare cases that cost every row step two scalar branches at the end of its basic block — a
-// gradient that reaches the depth from another consumer (g_in) and a wave that takes several supports in turn (n > 4, or SMD_BWD_WPS < n).
+// gradient that reaches the depth from another consumer (g_in) and a wave that takes several supports in turn (n > 4, or the knob bwd_wps < n).
 template <bool SSIM, int SKIP, bool ACC, bool XTRA>
 struct BwdCtx {
-  static constexpr bool kScan = (SKIP >= 1) || !SMD_BWD_ROWSEL;        // `sel` of the whole strip scanned before the row loop
-  static constexpr bool kSliding = (SKIP == 0) && SMD_BWD_STATEFUL;    // (a gated loop skips rows: no running state)
-  static constexpr bool kPeel = SMD_BWD_PEEL;
+  // the gated loop scans `sel` of the whole strip before the row loop and consults the row masks in every step; the plain loop runs every stage
+  // of every step and reads `sel` one row per step, with the row's loads
+  static constexpr bool GATED = SKIP >= 1;
   const ReconBwdArgs& a;
   // wave-uniform
   int h, w, r0, r1, pb0, pb1;
@@ -114,20 +95,16 @@ struct BwdCtx {
   bool interior, col_ok;
   float wla, wra, hx0, hy0, hz0;
   unsigned sel_key;
-  unsigned selbits;            // kScan: bit i = the pixel (row rb + i, this lane's column) routes gradient to the current support
-  unsigned SELR[3];            // !kScan: `sel` of the rows in flight, [row mod 3]
+  unsigned selbits;            // GATED: bit i = the pixel (row rb + i, this lane's column) routes gradient to the current support
+  unsigned SELR[3];            // !GATED: `sel` of the rows in flight, [row mod 3]
   float* hist;                 // this lane's column of the wave's LDS history: 3 row slots x {gx, gy} x 3 channels
   float* gacc;                 // ACC: this lane's column of the wave's dL/d depth rows (this wave's supports), one slot per strip row (LDS)
   // state
   float X[3][3], Y[3][3];      // [row mod 3][channel]: re-synthesised warped pixel / target pixel
-  float Px[3], Pxx[3], Pxy[3]; // kSliding: vertical sums of rows j-1 + j-2 once row j is in
   float HC[3][3][3];           // [row mod 3][channel][{A, B, C}]: h-summed partials d/d(Sx, Sxx (x2), Sxy) of a centre row
   f3 t0, t1, t2, t3, py;       // loads in flight for the next row
   float pfx, pfy;
   float Dn;                    // depth of row j+1 (for the next issue); it then waits in LDS for stage C three steps later
-#if (SMD_ABLATE_BWD & 8)
-  float GH[3][6];
-#endif
   float ps[9];                 // per-lane sums of {dnx, dnx*v, dny, dny*v, dz, dz*v, gnx, gny, gz}
 
   // Coordinates + gathers + target pixel of row jr.  Instruction for instruction the forward's `issue`: same taps, same weights.
@@ -141,39 +118,26 @@ struct BwdCtx {
     const float x0 = floorf(cx), y0 = floorf(cy);
     pfx = cx - x0; pfy = cy - y0;
     const unsigned o = __umul24((unsigned)fmaf(y0, wpf, x0), 12u);
-#if (SMD_ABLATE_BWD & 1)
-    const float fo = __builtin_bit_cast(float, (o & 0x7fffffu) | 0x3f000000u);
-    t0 = f3{fo, fo*0.5f, fo*0.25f}; t1 = f3{fo*0.3f, fo, fo}; t2 = f3{fo, fo*0.7f, fo}; t3 = f3{fo*0.9f, fo, fo*0.1f};
-#else
     t0 = bld3(rs_pk, o, so_tex); t1 = bld3(rs_pk, o + 12u, so_tex);
     t2 = bld3(rs_pk, o, so_tex + rowbytes); t3 = bld3(rs_pk, o + 12u, so_tex + rowbytes);
-#endif
-#if (SMD_ABLATE_BWD & 2)
-    py = f3{pfx, pfy, 0.5f};
-#else
     py = bld3(rs_pk, lane4*3u, so_y + (unsigned)jr*w4*3u);
-#endif
   }
 
   // ReflectionPad2d(1) by data, above and below the image: row -1 is row 1, row h is row h-2 (rows further out only feed the dummy
-  // centre rows -1 / h of the peeled form, whose coefficients are exact zeros: any valid row will do)
+  // centre rows -1 / h, whose coefficients are exact zeros: any valid row will do)
   // (branch-free on the scalar unit — s_abs / s_sub / s_max: written as nested conditionals the compiler emitted two scalar BRANCHES per call,
   // four per row step, each one splitting the step's basic block)
   __device__ __forceinline__ int reflect_row(int r) const { const int t = abs(r); return max((h - 1) - abs((h - 1) - t), 0); }
   __device__ __forceinline__ bool bit(unsigned m, int row) const { return (m >> (unsigned)(row - rb)) & 1u; }
   __device__ __forceinline__ bool routes(unsigned v) const { return (v == sel_key) == use_min; }   // min-reprojection: sel == support; mean: sel != "masked"
 
-  // kScan: `sel` of the centre rows pb0 .. pb1, once per support pass: which pixels / rows route gradient to the current support.  All of
+  // GATED: `sel` of the centre rows pb0 .. pb1, once per support pass: which pixels / rows route gradient to the current support.  All of
   // a strip's rows are requested before the first is looked at (two batches of ten: 8 + 2 rows of a tapered strip, 16 + 2 of a full
   // one), and so are the depths of the first two rows of the pipeline: one round trip for the whole prologue.
   __device__ __forceinline__ void sel_rows(int base, unsigned (&v)[kSelBatch]) const {
 #pragma unroll
     for (int k = 0; k < kSelBatch; ++k)
-#if (SMD_ABLATE_BWD & 2)
-      v[k] = (lane1 + (unsigned)(base + k)) & 1u;
-#else
       v[k] = bld8(rs_sel, lane1, (unsigned)min(max(base + k, 0), h - 1)*(unsigned)w);
-#endif
   }
   __device__ __forceinline__ void sel_bits(int base, const unsigned (&v)[kSelBatch]) {
 #pragma unroll
@@ -183,7 +147,7 @@ struct BwdCtx {
         const bool on = col_ok && routes(v[k]);
         const unsigned sh = (unsigned)(p - rb);
         selbits |= (on ? 1u : 0u) << sh;
-        if (SKIP >= 1) L |= (__builtin_amdgcn_ballot_w64(on) != 0 ? 1u : 0u) << sh;
+        L |= (__builtin_amdgcn_ballot_w64(on) != 0 ? 1u : 0u) << sh;
       }
     }
   }
@@ -192,7 +156,7 @@ struct BwdCtx {
     selbits = 0u; L = 0xffffffffu; N = 0xffffffffu;
     unsigned va[kSelBatch], vb[kSelBatch];
     const bool two = pb1 - pb0 >= kSelBatch;
-    if (kScan) {
+    if (GATED) {
       L = 0u;
       sel_rows(pb0, va);
       if (two) sel_rows(pb0 + kSelBatch, vb);
@@ -206,36 +170,30 @@ struct BwdCtx {
       for (int c = 0; c < 3; ++c) { X[r][c] = 0.f; Y[r][c] = 0.f; HC[r][c][0] = 0.f; HC[r][c][1] = 0.f; HC[r][c][2] = 0.f; }
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) { Px[c] = 0.f; Pxx[c] = 0.f; Pxy[c] = 0.f; }
-#pragma unroll
     for (int k = 0; k < 9; ++k) ps[k] = 0.f;
     t0 = f3{0.f, 0.f, 0.f}; t1 = t0; t2 = t0; t3 = t0; py = t0; pfx = 0.f; pfy = 0.f;
     // The first row's gathers go out BEFORE the scan is evaluated (its ~100 scalar / vector instructions then run under their latency;
     // a gated wave whose first row turns out dead wastes five loads)
     issue(reflect_row(jstart), Dfirst);
     hist[(0*kHist + 6)*64] = Dfirst;               // row jstart lives in slot 0
-    if (kScan) {
+    if (GATED) {
       sel_bits(pb0, va);
       if (two) sel_bits(pb0 + kSelBatch, vb);
       for (int base = pb0 + 2*kSelBatch; base <= pb1; base += kSelBatch) { sel_rows(base, va); sel_bits(base, va); }   // strips taller than 18 rows (single support only)
-      if (SKIP >= 1) N = L | (L << 1) | (L >> 1); else L = 0xffffffffu;
+      N = L | (L << 1) | (L >> 1);
     }
   }
 
   // One row step: stage A on row j (slot PH), stage B on centre row p = j-1, stage C on row q = j-2.
-  // DOB / DOC: 0 / 1 = the stage is compiled out / in (peeled form: the first two steps of a strip only synthesise, the next two also
-  // have a centre row, from the fifth on every step carries all three stages and the body has no range checks); 2 = decided per step
-  // from the rows' ranges (the compact form: one body per phase).
-  // GATED: the step consults the row masks (false: every stage of the step runs — the plain loop, and the gated loop's fast path through
-  // stretches where everything is live).
-  template <int PH, int DOB, int DOC, bool GATED>
+  // DOB / DOC: the stage is compiled in (the pipeline's fill is peeled off: the first two steps of a strip only synthesise, the next two
+  // also have a centre row, from the fifth on every step carries all three stages and the body has no range checks).
+  template <int PH, bool DOB, bool DOC>
   __device__ __forceinline__ void step(int j_) {
     const int j = __builtin_amdgcn_readfirstlane(j_);   // pin the row counter to an SGPR (row offsets are scalar operands of the buffer accesses)
     constexpr int SN = PH, SP = (PH + 2) % 3, SQ = (PH + 1) % 3;
     constexpr float c1 = 81.f*kC1;     // window sums stay un-normalised (x9), see smd_recon_fwd.hip
     const int p = j - 1, q = j - 2;
-    const bool inB = SSIM && DOB != 0 && (DOB == 1 || (p >= pb0 && p <= pb1));
-    const bool inC = DOC != 0 && (DOC == 1 || (q >= r0 && q < r1));
+    constexpr bool inB = SSIM && DOB, inC = DOC;
     const bool doB = inB && (!GATED || bit(L, p));
     const bool doC = inC && (!GATED || bit(N, q));
     const bool doA = !GATED || bit(N, j);
@@ -243,18 +201,12 @@ struct BwdCtx {
     const bool doD = !GATED || bit(N, j + 2);      // row j+2 is needed: request its depth now
 
     f4 ta; f3 tb;                                   // read only where doB holds
-#if !(SMD_ABLATE_BWD & 2)
-    if (!kScan) SELR[SP] = bld8(rs_sel, lane1, (unsigned)min(max(p, 0), h - 1)*(unsigned)w);
-#endif
+    if (!GATED) SELR[SP] = bld8(rs_sel, lane1, (unsigned)min(max(p, 0), h - 1)*(unsigned)w);
     if (doB) {
-#if (SMD_ABLATE_BWD & 2)
-      ta = f4{pfx + 1.f, pfy + 1.f, 1.5f, 0.3f}; tb = f3{0.2f, 0.4f, 0.1f};
-#else
       const unsigned pc = (unsigned)min(max(p, 0), h - 1);               // (dummy centre rows read a real row: their weight is an exact zero, their values must be finite)
       ta = bld4(rs_pk, lane4*4u, so_ta + pc*w4*4u);
       const f2 tb2 = bld2(rs_pk, lane4*4u, so_tb + pc*w4*4u);   // {c1, c2}; the third entry is the forward's static error
       tb = f3{tb2.x, tb2.y, 0.f};
-#endif
     }
     // ================= stage A: row j — the warped pixel and its bilinear partials from the taps issued one step earlier
     if (doA) {
@@ -265,50 +217,29 @@ struct BwdCtx {
         const float ddy = bot - top;
         X[SN][c] = fmaf(pfy, ddy, top);
         Y[SN][c] = py[c];
-#if (SMD_ABLATE_BWD & 8)
-        GH[SN][c] = fmaf(pfy, ds - dn, dn); GH[SN][3 + c] = ddy;
-#else
         hist[(SN*kHist + c)*64] = fmaf(pfy, ds - dn, dn);   // dx/dsx; the border-clamp mask is applied in stage C
         hist[(SN*kHist + 3 + c)*64] = ddy;                  // dx/dsy
-#endif
       }
     }
     // Next row's loads.  SKIP = 0: unconditionally (also after the last row, where nothing consumes them).  Rows outside the image are
     // reflected ones (ReflectionPad2d(1): row -1 is row 1, row h is row h-2), re-synthesised like any other row: no special case in vector code.
     if (doI) issue(reflect_row(j + 1), Dn);
     const float Dkeep = Dn;                          // depth of row j+1: parked in LDS at the end of the step (slot SQ is read first)
-    if (doD) {
-#if (SMD_ABLATE_BWD & 2)
-      Dn = 1.f + pfx;
-#else
-      Dn = bld(rs_depth, lane4, (unsigned)reflect_row(j + 2)*w4);
-#endif
-    }
+    if (doD) Dn = bld(rs_depth, lane4, (unsigned)reflect_row(j + 2)*w4);
 
     // ================= stage B: centre row p — SSIM partials, h-summed with the adjoint reflection weights
     if (SSIM) {
       // window sums of centre p from its three raw rows (slots SQ = p-1, SP = p, SN = p+1); the image's top and bottom rows get their
       // reflected neighbour by data ("row -1" is a re-synthesised row 1, "row h" a re-synthesised row h-2)
-      float Vx[3], Vxx[3], Vxy[3];
-      if (kSliding) {   // the forward's sliding scheme: V = P + r(j), then P' = r(j-1) + r(j); every step, whatever its centre row
+      if (doB) {
+        float Vx[3], Vxx[3], Vxy[3];
+        float g2;
+        if (GATED) g2 = ((selbits >> (unsigned)(p - rb)) & 1u) ? g_ssim : 0.f;
+        else g2 = (col_ok && routes(SELR[SP])) ? g_ssim : 0.f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-          const float xn = X[SN][c], xo = X[SP][c];
-          const float xx = xn*xn, xy = xn*Y[SN][c];
-          Vx[c] = Px[c] + xn; Vxx[c] = Pxx[c] + xx; Vxy[c] = Pxy[c] + xy;
-          Px[c] = xo + xn; Pxx[c] = fmaf(xo, xo, xx); Pxy[c] = fmaf(xo, Y[SP][c], xy);
-        }
-      }
-      if (doB) {
-        float g2;
-        if (kScan) g2 = ((selbits >> (unsigned)(p - rb)) & 1u) ? g_ssim : 0.f;
-        else g2 = (col_ok && routes(SELR[SP])) ? g_ssim : 0.f;
-        if (!kSliding) {
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            const float xq = X[SQ][c], xp = X[SP][c], xn = X[SN][c];
-            Vx[c] = (xq + xp) + xn; Vxx[c] = fmaf(xn, xn, fmaf(xp, xp, xq*xq)); Vxy[c] = fmaf(xn, Y[SN][c], fmaf(xp, Y[SP][c], xq*Y[SQ][c]));
-          }
+          const float xq = X[SQ][c], xp = X[SP][c], xn = X[SN][c];
+          Vx[c] = (xq + xp) + xn; Vxx[c] = fmaf(xn, xn, fmaf(xp, xp, xq*xq)); Vxy[c] = fmaf(xn, Y[SN][c], fmaf(xp, Y[SP][c], xq*Y[SQ][c]));
         }
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -350,17 +281,13 @@ struct BwdCtx {
         float lo_q = usel(q == 0, 0.f, usel(q == 1, 2.f, 1.f)), hi_q = usel(q == h - 1, 0.f, usel(q == h - 2, 2.f, 1.f));
         if (h == 2) { lo_q = usel(q == 1, 2.f, 0.f); hi_q = usel(q == 0, 2.f, 0.f); }
         float gl;
-        if (kScan) gl = ((selbits >> (unsigned)(q - rb)) & 1u) ? g_l1 : 0.f;
+        if (GATED) gl = ((selbits >> (unsigned)(q - rb)) & 1u) ? g_l1 : 0.f;
         else gl = (col_ok && routes(SELR[SQ])) ? g_l1 : 0.f;
         D2 = hist[(SQ*kHist + 6)*64];
         float gpx = 0.f, gpy = 0.f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-#if (SMD_ABLATE_BWD & 8)
-          const float gxq = GH[SQ][c], gyq = GH[SQ][3 + c];
-#else
           const float gxq = hist[(SQ*kHist + c)*64], gyq = hist[(SQ*kHist + 3 + c)*64];
-#endif
           const float xq = X[SQ][c], yq = Y[SQ][c];
           const float d = xq - yq;
           float gxc = (d != 0.f) ? __builtin_copysignf(gl, d) : 0.f;     // gl*sign(d)
@@ -396,10 +323,6 @@ struct BwdCtx {
         if (GATED && !doC) D2 = bld(rs_depth, lane4, qro);     // a skipped row never had its depth parked
       }
       if (a.k0_scale != 0.f) gD *= (D2 < 1.f/kEps32) ? -D2*D2*a.k0_scale : 0.f;
-#if (SMD_ABLATE_BWD & 4)
-      if (gD == 12345.678f) bst(rs_gd, lane4, qro, gD);
-      else
-#endif
       if (ACC) {
         // The supports of a strip are summed from LDS by the strip's last wave (k_recon_bwd): each lane parks its own column, one
         // slot per strip row; no read-modify-write of g_depth, one global store per pixel.
@@ -411,40 +334,18 @@ struct BwdCtx {
     if (doI) hist[(SQ*kHist + 6)*64] = Dkeep;      // row j+1's slot: stage C reads it at step j+3 (no second load of the depth)
   }
 
-  // -DSMD_BWD_FASTPATH (experiment, off): a gated wave takes the branch-free body wherever its masks say that everything the step touches is
-  // live — rows j, j+1, j+2 needed, centre row j-1 live, row j-2 needed; one scalar test per step.
-  template <int PH, int DOB, int DOC>
-  __device__ __forceinline__ void step_any(int j) {
-    if (SKIP == 0) { step<PH, DOB, DOC, false>(j); return; }
-#ifdef SMD_BWD_FASTPATH   // (off: with both bodies in one loop the register allocator spills ~70 values at 128 VGPRs — as round 3's per-wave choice did)
-    if (DOB == 1 && DOC == 1) {                                   // steady state of the peeled pipeline: j - 2 >= r0 > rb
-      const unsigned nb = N >> (unsigned)(j - 2 - rb);            // bit 0: row j-2 ... bit 4: row j+2
-      if ((nb & 0x1du) == 0x1du && bit(L, j - 1)) { step<PH, DOB, DOC, false>(j); return; }
-    }
-#endif
-    step<PH, DOB, DOC, true>(j);
-  }
-
-  __device__ __forceinline__ void run(int jstart) {
+  __device__ __forceinline__ void run(int jstart) {   // jstart = r0 - 2: r1 - r0 + 4 >= 5 steps
     begin(jstart);
     const int jend = r1 + 1;
     int j = jstart;
-    if (kPeel) {                           // jstart = r0 - 2: r1 - r0 + 4 >= 5 steps
-      step_any<0, 0, 0>(j); ++j;
-      step_any<1, 0, 0>(j); ++j;
-      step_any<2, 1, 0>(j); ++j;
-      step_any<0, 1, 0>(j); ++j;
-      for (;;) {
-        step_any<1, 1, 1>(j); if (++j > jend) break;
-        step_any<2, 1, 1>(j); if (++j > jend) break;
-        step_any<0, 1, 1>(j); if (++j > jend) break;
-      }
-    } else {
-      for (;;) {
-        step_any<0, 2, 2>(j); if (++j > jend) break;
-        step_any<1, 2, 2>(j); if (++j > jend) break;
-        step_any<2, 2, 2>(j); if (++j > jend) break;
-      }
+    step<0, false, false>(j); ++j;
+    step<1, false, false>(j); ++j;
+    step<2, true, false>(j); ++j;
+    step<0, true, false>(j); ++j;
+    for (;;) {
+      step<1, true, true>(j); if (++j > jend) break;
+      step<2, true, true>(j); if (++j > jend) break;
+      step<0, true, true>(j); if (++j > jend) break;
     }
   }
 };
@@ -456,9 +357,6 @@ constexpr int kAccRows = 16;   // tallest strip of the multi-support instantiati
 // NS = waves per strip: wave (strip in block, k) handles supports k, k + NS, ... of its strip (NS = 1: every support, one after
 // the other — balanced waves whatever the selection masks look like; NS = min(n, 4): half / a quarter as long work units).
 // ACC: more than one support — the strip's dL/d depth rows are summed in LDS.
-#ifdef SMD_TRACE_WAVES
-__device__ unsigned long long g_wave_trace_bwd[1 << 16][3];
-#endif
 // Does any pixel within one row / column of the strip (rows r0 .. r1-1, columns c0 .. c0+59) select `key`?  Conservative in the rows (a forward strip's
 // mask covers all of its rows), exact in the columns.  The footprint overlaps at most 3 x 3 forward strips in every partition the heuristics choose:
 // lane l < 9 fetches entry (l / 3, l mod 3) — indices beyond the footprint repeat its last strip — masks it with the lanes of its columns, and one
@@ -483,9 +381,6 @@ __device__ __forceinline__ bool strip_is_live(const ReconBwdArgs& a, int s, int 
 
 template <bool SSIM, int SKIP, int NS, bool ACC, bool XTRA>
 __global__ __launch_bounds__(64*kWavesPerBlock, 4) void k_recon_bwd(const ReconBwdArgs a) {
-#ifdef SMD_TRACE_WAVES
-  const unsigned long long trace_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
   static_assert(ACC || NS == 1, "several waves per strip need the LDS sum");
   constexpr int SPB = (kWavesPerBlock/NS > 0) ? kWavesPerBlock/NS : 1;   // strips per block
   // (a wave's region is at least the epilogue's scratch, which aliases it: single-support strips have no dL/d depth rows)
@@ -583,11 +478,10 @@ __global__ __launch_bounds__(64*kWavesPerBlock, 4) void k_recon_bwd(const ReconB
     cx.so_ta = (unsigned)((packed_texel_floats(a.b, a.n, h, w) + packed_ypix_floats(a.b, h, w))*4) + (unsigned)bi*hw4*4u;
     cx.so_tb = cx.so_ta + (unsigned)(packed_tpix_floats(a.b, h, w)*4);
 
-    // rows outside the image are reflected ones (BwdCtx::reflect_row).  Peeled form: every strip runs rows r0-2 .. r1+1 with centre
-    // rows r0-1 .. r1 (-1 and h: dummy rows, exact zeros); compact form: the image's top strip starts at row -1 (= row 1) and no dummy rows
-    const bool peel = BwdCtx<SSIM, SKIP, ACC, XTRA>::kPeel;
-    const int jstart = peel ? r0 - 2 : max(r0 - 2, -1);
-    cx.pb0 = peel ? r0 - 1 : max(r0 - 1, 0); cx.pb1 = peel ? r1 : min(r1, h - 1);   // centre rows whose coefficients are needed
+    // rows outside the image are reflected ones (BwdCtx::reflect_row): every strip runs rows r0-2 .. r1+1 with centre rows r0-1 .. r1
+    // (-1 and h: dummy rows, exact zeros)
+    const int jstart = r0 - 2;
+    cx.pb0 = r0 - 1; cx.pb1 = r1;   // centre rows whose coefficients are needed
 
     for (int i = kw; i < a.n; i += NS) {
       cx.add_gin = has_gin && i == 0;
@@ -621,15 +515,6 @@ __global__ __launch_bounds__(64*kWavesPerBlock, 4) void k_recon_bwd(const ReconB
     }
   }
 
-#ifdef SMD_TRACE_WAVES   // diagnosis builds only (scripts/dev/wave_trace.py bwd): when and where this wave ran its row loop
-  if (lane == 0) {
-    const unsigned widx = blockIdx.x*kWavesPerBlock + wid;
-    if (widx < (1u << 16)) {
-      g_wave_trace_bwd[widx][0] = trace_t0; g_wave_trace_bwd[widx][1] = __builtin_amdgcn_s_memrealtime();
-      g_wave_trace_bwd[widx][2] = ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 20) << 32) | __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);
-    }
-  }
-#endif
   // ---- epilogue chain, no block barrier (every wave of a block would idle through two memory round trips): a wave that is
   // done bumps LDS counters; the LAST wave of a strip sums the strip's dL/d depth rows, the LAST wave of the block counts the
   // block's arrival at agent scope, and the wave that completes a sample reduces its pose sums (Guideline 16 of
@@ -677,10 +562,6 @@ __global__ __launch_bounds__(64*kWavesPerBlock, 4) void k_recon_bwd(const ReconB
   if (lane == 0) __hip_atomic_store(a.arrive + bi, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next call on this buffer
 }
 
-#ifdef SMD_EXPERIMENTS
-#include "experiments/smd_recon_bwd_pair.inc"   // k_recon_bwd_pair (dropped in round 4; knob bwd_pair)
-#endif
-
 // The same epilogue as a launch of its own, for the un-fused ViewSynth backward (smd_unfused.hip), whose partials come from a
 // one-thread-per-pixel kernel: one block of four waves per sample.
 __global__ __launch_bounds__(256) void k_pose_finalize(const ReconBwdArgs a, int entries) {
@@ -707,28 +588,7 @@ static void launch_bwd_t(dim3 grid, dim3 block, hipStream_t st, const ReconBwdAr
   else hipLaunchKernelGGL((k_recon_bwd<SSIM, SKIP, NS, ACC, false>), grid, block, 0, st, a);
 }
 
-#ifdef SMD_EXPERIMENTS
-template <bool SSIM, int NP>
-static void launch_bwd_pair_t(dim3 grid, hipStream_t st, const ReconBwdArgs& a) {
-  note_variant(1, "smd::k_recon_bwd_pair<%s, %d>", SSIM ? "true" : "false", NP);
-  hipLaunchKernelGGL((k_recon_bwd_pair<SSIM, NP>), grid, dim3(64*kPairWaves), 0, st, a);
-}
-#endif
-
 hipError_t launch_recon_bwd(const ReconBwdArgs& a, hipStream_t st) {
-#ifndef SMD_EXPERIMENTS
-  if (a.pair) return hipErrorInvalidValue;
-#else
-  if (a.pair) {   // two supports per wave: n = 2 or 4, min-reprojection, plain row loop (smd_api.hip decides)
-    if (!(a.n == 2 || a.n == 4) || !(a.flags & SMD_USE_MIN) || a.rh > kAccRows || a.rh2 > kAccRows) return hipErrorInvalidValue;
-    const int np = a.n/2, spbp = kPairWaves/np;
-    dim3 gridp(recon_grid_blocks(a.nsx*a.nsy, a.b1, a.S, spbp) + (a.b1 < a.b ? recon_grid_blocks(a.nsx*a.nsy2, a.b - a.b1, a.S, spbp) : 0u));
-    const bool ssimp = !(a.flags & SMD_LOSS_L1);
-    if (ssimp) { if (np == 1) launch_bwd_pair_t<true, 1>(gridp, st, a); else launch_bwd_pair_t<true, 2>(gridp, st, a); }
-    else { if (np == 1) launch_bwd_pair_t<false, 1>(gridp, st, a); else launch_bwd_pair_t<false, 2>(gridp, st, a); }
-    return hipGetLastError();
-  }
-#endif
   const int ns = a.wps, spb = kWavesPerBlock/ns;
   if (ns < 1 || ns > 4 || ns > a.n) return hipErrorInvalidValue;
   dim3 grid(recon_grid_blocks(a.nsx*a.nsy, a.b1, a.S, spb) + (a.b1 < a.b ? recon_grid_blocks(a.nsx*a.nsy2, a.b - a.b1, a.S, spb) : 0u)), block(64*ns*spb);
@@ -749,9 +609,3 @@ hipError_t launch_recon_bwd(const ReconBwdArgs& a, hipStream_t st) {
 }
 
 }  // namespace smd
-
-#ifdef SMD_TRACE_WAVES
-extern "C" int smd_debug_wave_trace_bwd(unsigned long long* host_out, int max_waves) {
-  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(smd::g_wave_trace_bwd), (size_t)max_waves*3*sizeof(unsigned long long), 0, hipMemcpyDeviceToHost);
-}
-#endif

@@ -29,13 +29,6 @@
 #include "smd_kernels.h"
 #include "smd_smooth_dev.h"
 
-#ifndef SMD_FWD_PRIO
-#define SMD_FWD_PRIO 0   // experiment: s_setprio by remaining rows in the shared-ring forward (see step())
-#endif
-#ifndef SMD_ABLATE
-#define SMD_ABLATE 0   // diagnosis builds only (scripts/dev/ablate.sh): bit 0 no tap gathers, bit 1 no row loads (incl. K0), bit 2 no stores, bit 3 no ta/tb loads, bit 4 no target-row load
-#endif
-
 namespace smd {
 
 // ATen area_pixel_compute_source_index (align_corners=False) + index / lambda split, as the K0 kernel (smd_depth.hip)
@@ -282,10 +275,6 @@ struct MainPend {          // gathers in flight for one pair of supports
   float fx[(N > 1) ? 2 : 1], fy[(N > 1) ? 2 : 1];
 };
 
-// LA: look-ahead of the tap gathers in row steps.  1: the taps of row j+1 are requested while row j is scored.  2 (N <= 2 only): the
-// taps of row j+2 — two sets of pending registers, each tied to the row buffer (XA / XB) its row will be blended into, so the
-// unrolled loop still never moves a register; 28 more VGPRs (3 waves per SIMD instead of 4) for twice the distance between a
-// gather and its first use.
 // SH (round 3): the block's four waves are the FOUR SCALES of one strip.  What a row step reads on the target side — the target
 // pixel of the new row, {S_y, c} and the identity error of the centre row: 40 bytes per pixel, the same for every scale — is
 // fetched ONCE per block into an LDS ring by LDS-DMA (`buffer_load_dwordx3/x4 ... lds`: no registers, lane l lands at
@@ -296,10 +285,9 @@ struct MainPend {          // gathers in flight for one pair of supports
 constexpr int kRingSlotFloats = 3*64*4;
 constexpr int kRingFloats = 8*kRingSlotFloats;
 
-template <int N, bool SSIM, bool SINGLE, bool AUX, bool DISP, int LA, bool SH = false>
+template <int N, bool SSIM, bool SINGLE, bool AUX, bool DISP, bool SH = false>
 struct MainCtx {
-  static_assert(LA == 1 || (LA == 2 && N <= 2), "two rows of look-ahead only with a single pair of supports");
-  static_assert(!SH || (SSIM && SINGLE && !AUX && DISP && LA == 1), "the shared target ring exists for the hot instantiation only");
+  static_assert(!SH || (SSIM && SINGLE && !AUX && DISP), "the shared target ring exists for the hot instantiation only");
   static constexpr int NG = (N + 1)/2;
   const ReconMainArgs& a;
   int bi, s, h, w, r0, r1, jlast;
@@ -346,12 +334,8 @@ struct MainCtx {
   Cam2 cam[N];
   // per-lane column part of the homography rows.  Up to two supports: registers.  Three and four (168-VGPR budget, 3 waves per
   // SIMD): parked in this lane's LDS column and read back every row step — the allocator otherwise spills nine loop-invariant
-  // values to scratch and reloads 5.5 of them per row step through the texture path (round 3; -DSMD_FWD_CAM_REGS restores it).
-#ifdef SMD_FWD_CAM_REGS
-  static constexpr bool kCamLds = false;
-#else
+  // values to scratch and reloads 5.5 of them per row step through the texture path (round 3).
   static constexpr bool kCamLds = N > 2;
-#endif
   float hx0[kCamLds ? 1 : N], hy0[kCamLds ? 1 : N], hz0[kCamLds ? 1 : N];
   const float* camcol;     // kCamLds: [support][3][64 lanes] of this wave, + lane
   unsigned so_tex[N], so_y, so_ta, so_tb;   // wave-uniform byte offsets into `packed`: texel image of support k, this sample's ypix / ta / tb
@@ -362,10 +346,10 @@ struct MainCtx {
   static constexpr int NT = SINGLE ? (N < kLiveSupports ? N : kLiveSupports) : kLiveSupports;
   unsigned long long livem[NT];
   float Px[N][3], Pxx[N][3], Pxy[N][3];
-  MainPend<N> P[LA];
+  MainPend<N> P;
   f3 py;                   // target row in flight
   float Dcur, Dnext;       // depth of rows j and j+1
-  float vfn;               // (float)(j + LA): the row whose taps the next issue requests
+  float vfn;               // (float)(j + 1): the row whose taps the next issue requests
   // DISP (K0 fused): the depth of a row is computed here from the network's low-resolution sigmoid
   // disparity — bilinear up-sampling (`ops.interpolate_like`, src/tools/ops.py:311-314) + `to_scaled` / `to_inv`
   // (src/tools/geometry.py:62-90) — and written out once for the backward, instead of being read from a K0 launch's output.
@@ -432,9 +416,7 @@ struct MainCtx {
   }
 
   // ---- coordinates + the four tap loads of one pair of supports -----------------------------------------
-  template <int PS>
   __device__ __forceinline__ void issue(int g, float D, float vf) {
-    MainPend<N>& P = this->P[PS];
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
       const int k = 2*g + kk;
@@ -451,13 +433,8 @@ struct MainCtx {
         const float x0 = floorf(cx), y0 = floorf(cy);
         P.fx[kk] = cx - x0; P.fy[kk] = cy - y0;
         const unsigned o = __umul24((unsigned)fmaf(y0, wpf, x0), 12u);   // texel index exact in fp32: (h+1)*(w+1) < 2^24 (checked by the C ABI)
-#if (SMD_ABLATE & 1)
-        const float fo = __builtin_bit_cast(float, (o & 0x7fffffu) | 0x3f000000u);
-        P.t[kk][0] = f3{fo, fo*0.5f, fo*0.25f}; P.t[kk][1] = f3{fo*0.3f, fo, fo}; P.t[kk][2] = f3{fo, fo*0.7f, fo}; P.t[kk][3] = f3{fo*0.9f, fo, fo*0.1f};
-#else
         P.t[kk][0] = bld3(rs_pk, o, so_tex[k]); P.t[kk][1] = bld3(rs_pk, o + 12u, so_tex[k]);
         P.t[kk][2] = bld3(rs_pk, o, so_tex[k] + rowbytes); P.t[kk][3] = bld3(rs_pk, o + 12u, so_tex[k] + rowbytes);
-#endif
       }
     }
   }
@@ -466,30 +443,16 @@ struct MainCtx {
   // unconditionally — also after the last row of the strip, where nothing consumes them: the tap coordinates are clamped, a
   // depth row below the image reads 0 (buffer bounds), and a conditional issue would make every pending register a loop phi
   // with a second copy (36 more VGPRs).
-  template <int PS>
   __device__ __forceinline__ void issue_next_row(int j) {
-#if (SMD_ABLATE & 2)
-    issue<PS>(0, Dnext, vfn);
-    py = f3{vfn*0.001f, 0.5f, vfn*0.002f};
-    Dcur = Dnext;
-    Dnext = 1.f + vfn*0.01f;
-#else
-    const float Dn = DISP ? finish_depth(j + LA) : Dnext;
-    issue<PS>(0, Dn, vfn);
-#if (SMD_ABLATE & 16)
-    py = f3{vfn*0.001f, 0.5f, vfn*0.002f};
-#else
+    const float Dn = DISP ? finish_depth(j + 1) : Dnext;
+    issue(0, Dn, vfn);
     if (!SH) py = bld3(rs_pk, lane4*3u, so_y + (unsigned)(j + 1)*w4*3u);
-#endif
     Dcur = Dn;
-    if (DISP) load_dtaps<false>(j + LA + 1); else Dnext = bld(rs_depth, lane4, (unsigned)(j + LA + 1)*w4);
-#endif
+    if (DISP) load_dtaps<false>(j + 2); else Dnext = bld(rs_depth, lane4, (unsigned)(j + 2)*w4);
     vfn += 1.f;
   }
 
-  template <int PS>
   __device__ __forceinline__ void finish(int g, float (&Xn)[N][3], int j) {
-    const MainPend<N>& P = this->P[PS];
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
       const int k = 2*g + kk;
@@ -515,8 +478,7 @@ struct MainCtx {
 
   // One row step: row j is the NEW row, centre row v = j-1.  EMIT = false only updates the sliding sums.
   // VIRT (j == h): the new row is the reflected row h-2: the target row is read again, the warped row is P - x(h-1).
-  // PS: the pending set tied to Xn (LA = 2: 0 for XA, 1 for XB; LA = 1: always 0)
-  template <bool EMIT, bool VIRT, int PS>
+  template <bool EMIT, bool VIRT>
   __device__ __forceinline__ void step(int j, float (&Xo)[N][3], float (&Xn)[N][3], float (&Yo)[3], float (&Yn)[3]) {
     const int v = j - 1;
     constexpr float c1 = 81.f*kC1;
@@ -525,12 +487,8 @@ struct MainCtx {
     float nz = 0.f;
     if (EMIT && !SH) {   // what the centre row shares across scales and supports: {S_y[3], cy2[3], identity error, -}
       const unsigned to = (unsigned)v*w4*4u;
-#if (SMD_ABLATE & (2 | 8))
-      t0 = f4{4.5f + vfn*0.01f, 4.4f, 4.3f, 0.2f}; t1 = f3{0.25f, 0.3f, 0.05f}; (void)to;
-#else
       if (SSIM) t0 = bld4(rs_pk, lane4*4u, so_ta + to);
       t1 = bld3(rs_pk, lane4*4u, so_tb + to);
-#endif
       if (AUX && has_noise) nz = nz_sb[(size_t)v*w + (lane4 >> 2)];
     }
     if (!SH && !VIRT) { Yn[0] = py.x; Yn[1] = py.y; Yn[2] = py.z; }
@@ -540,7 +498,7 @@ struct MainCtx {
     int bsel = a.i0;
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
-      if (!VIRT) finish<PS>(g, Xn, j);
+      if (!VIRT) finish(g, Xn, j);
       else {
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) { const int k = 2*g + kk; if (k < N) {
@@ -550,20 +508,7 @@ struct MainCtx {
       if (SH && g == 0) {
         // the taps of this row have just been waited for.  First step of an epoch: meet the other scales, then send for this
         // wave's row of the next epoch; every step: this row's slot of the ring.
-        if ((j & 3) == 0) {
-          epoch_sync(); dma_epoch((j >> 2) + 1);
-#if SMD_FWD_PRIO
-          // issue priority by the rows a wave still has to do (the arbiter otherwise serves the OLDEST wave of a SIMD first: the four waves of
-          // a SIMD then finish one after the other, and at the end of the launch the last ones run alone, latency-bound; wave traces in
-          // profiles/r04_fwd_wave_traces.txt): a wave with more rows ahead of it goes first, so co-resident waves finish closer together
-          const int rem = jlast - j;
-#if SMD_FWD_PRIO == 2   // the inverse: the fewer rows left, the higher the priority (oldest-first, made stronger)
-          if (rem < 4) __builtin_amdgcn_s_setprio(3); else if (rem < 8) __builtin_amdgcn_s_setprio(2); else if (rem < 12) __builtin_amdgcn_s_setprio(1);
-#else
-          if (rem < 4) __builtin_amdgcn_s_setprio(0); else if (rem < 8) __builtin_amdgcn_s_setprio(1); else if (rem < 12) __builtin_amdgcn_s_setprio(2);
-#endif
-#endif
-        }
+        if ((j & 3) == 0) { epoch_sync(); dma_epoch((j >> 2) + 1); }
         const float* slot = ring_lane + (j & 7)*kRingSlotFloats;
         if (!VIRT) { const f4 yv = *reinterpret_cast<const f4*>(slot); Yn[0] = yv.x; Yn[1] = yv.y; Yn[2] = yv.z; }
         if (EMIT) {
@@ -575,8 +520,8 @@ struct MainCtx {
       __builtin_amdgcn_sched_barrier(0);
       // keep the memory pipe busy: next pair of this row, or the first pair of the next row
       if (!VIRT) {
-        if (g + 1 < NG) issue<PS>(g + 1, Dcur, vfn - 1.f);
-        else issue_next_row<PS>(j);
+        if (g + 1 < NG) issue(g + 1, Dcur, vfn - 1.f);
+        else issue_next_row(j);
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -630,12 +575,8 @@ struct MainCtx {
         else if (fabsf(est - e) < 1e-5f)
           est = fmaf(kEps32, gauss_noise(a.seed_lo, a.seed_hi, (uint32_t)(((unsigned)s*(unsigned)a.b + (unsigned)bi)*(hw4 >> 2) + cro1 + lane1)), est);
         if (est < e) { e = est; bsel = SMD_SEL_MASKED; }
-#if (SMD_ABLATE & 4)
-        if (e == 123.456f) bst(rs_err, st4, cro, e + (float)bsel);
-#else
         if (has_err) bst(rs_err, st4, cro, e);      // the error map is an optional output (logging / tests): one store less per row
         bst8(rs_sel, st1, cro1, (unsigned)bsel);
-#endif
 #pragma unroll
         for (int k = 0; k < NT; ++k) livem[k] |= __ballot(bsel == k);   // one v_cmp + one scalar or per support (halo lanes included: they hold real neighbours)
         lsum += interior ? e : 0.f;
@@ -643,23 +584,20 @@ struct MainCtx {
     }
   }
 
-  template <int PS>
   __device__ __forceinline__ void init(float (&X)[N][3], float (&Y)[3], int j) {   // P = r(jstart) alone
     Y[0] = py.x; Y[1] = py.y; Y[2] = py.z;
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
-      finish<PS>(g, X, j);
-      if (g + 1 < NG) issue<PS>(g + 1, Dcur, vfn - 1.f);
-      else issue_next_row<PS>(j);
+      finish(g, X, j);
+      if (g + 1 < NG) issue(g + 1, Dcur, vfn - 1.f);
+      else issue_next_row(j);
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) { const int k = 2*g + kk; if (k < N) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) { Px[k][c] = X[k][c]; Pxx[k][c] = X[k][c]*X[k][c]; Pxy[k][c] = X[k][c]*Y[c]; } } }
     }
   }
-  // Everything in flight before the first row is blended: the taps of row jstart into set PSF (the set of the buffer `init` fills),
-  // with LA = 2 also those of row jstart + 1 into the other set, the target row jstart, the depth pipeline LA rows ahead.
-  template <int PSF>
+  // Everything in flight before the first row is blended: the taps of row jstart, the target row jstart, the depth pipeline one row ahead.
   __device__ __forceinline__ void prologue(int jstart) {
     if (SH) {   // the epoch of the first row step (r0 = 0: the loop starts at row 1 and only meets an epoch boundary at row 4 — both epochs)
       dma_epoch(r0 >> 2);
@@ -669,22 +607,15 @@ struct MainCtx {
     if (DISP) { load_dtaps<true>(jstart); Dnext = finish_depth(jstart); }
     else Dnext = bld(rs_depth, lane4, (unsigned)jstart*w4);
     Dcur = Dnext;
-    issue<PSF>(0, Dnext, vfn);
+    issue(0, Dnext, vfn);
     py = bld3(rs_pk, lane4*3u, so_y + (unsigned)jstart*w4*3u);
     vfn += 1.f;
-    if (LA == 2) {
-      float D1;
-      if (DISP) { load_dtaps<false>(jstart + 1); D1 = finish_depth(jstart + 1); }
-      else D1 = bld(rs_depth, lane4, (unsigned)(jstart + 1)*w4);
-      issue<(LA == 2) ? 1 - PSF : 0>(0, D1, vfn);
-      vfn += 1.f;
-    }
-    if (DISP) load_dtaps<false>(jstart + LA); else Dnext = bld(rs_depth, lane4, (unsigned)(jstart + LA)*w4);
+    if (DISP) load_dtaps<false>(jstart + 1); else Dnext = bld(rs_depth, lane4, (unsigned)(jstart + 1)*w4);
     if (SH) epoch_sync();   // (waits for what `init` needs next anyway)
   }
 };
 
-template <int N, bool SSIM, bool SINGLE, bool AUX, bool DISP, int LA, bool SH>
+template <int N, bool SSIM, bool SINGLE, bool AUX, bool DISP, bool SH>
 __device__ __forceinline__ float recon_main_body(const ReconMainArgs& a) {   // -> this lane's share of the loss sum (0 for a wave without a strip)
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -702,7 +633,7 @@ __device__ __forceinline__ float recon_main_body(const ReconMainArgs& a) {   // 
   if (tail) bi_ += a.b1;
   const int sxi = strip % a.nsx, syi = strip/a.nsx;
 
-  using Ctx = MainCtx<N, SSIM, SINGLE, AUX, DISP, LA, SH>;
+  using Ctx = MainCtx<N, SSIM, SINGLE, AUX, DISP, SH>;
   __shared__ __attribute__((aligned(16))) float ring_mem[SH ? kRingFloats : 4];
   __shared__ float cam_lds[Ctx::kCamLds ? kWavesPerBlock*N*3*64 : 1];   // own-lane columns: written and read by the same lane, no synchronisation
   Ctx cx{a};
@@ -749,7 +680,7 @@ __device__ __forceinline__ float recon_main_body(const ReconMainArgs& a) {   // 
     cx.dx0 = (unsigned)x0*4u; cx.dx1 = (unsigned)x1*4u;
     cx.a_scale = a.a_scale; cx.a_off = a.a_off;
     cx.rowtab = a.rowtab + (size_t)s_*(a.h + 4);
-    cx.tab_base = max(cx.r0 - 1, 0);                       // rows tab_base .. r1 + LA + 1 are looked up: at most rh + LA + 3 <= 64 entries
+    cx.tab_base = max(cx.r0 - 1, 0);                       // rows tab_base .. r1 + 2 are looked up: at most rh + 4 <= 64 entries
     { const uint4 e = cx.rowtab[min(cx.tab_base + lane, a.h + 3)]; cx.tab_x = e.x; cx.tab_y = e.y; cx.tab_z = e.z; }
   }
   cx.nz_sb = (AUX && a.noise) ? a.noise + sb : nullptr;
@@ -759,9 +690,6 @@ __device__ __forceinline__ float recon_main_body(const ReconMainArgs& a) {   // 
   cx.lsum = 0.f;
 #pragma unroll
   for (int k = 0; k < Ctx::NT; ++k) cx.livem[k] = 0ull;
-#if SMD_FWD_PRIO == 1
-  if (SH) __builtin_amdgcn_s_setprio(3);
-#endif
   if (SH) {
     cx.ring_lds = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)(__attribute__((address_space(3))) float*)ring_mem);
     cx.ring_lane = ring_mem + lane*4;
@@ -769,25 +697,23 @@ __device__ __forceinline__ float recon_main_body(const ReconMainArgs& a) {   // 
     cx.ring_last = (cx.r1 == a.h) ? a.h : cx.jlast;
   }
 
-  // The pending set of a row is tied to the buffer the row is blended into: XA <-> set 0, XB <-> set (LA == 2 ? 1 : 0).
-  constexpr int SA = 0, SB = (LA == 2) ? 1 : 0;
   const int jstart = max(cx.r0 - 1, 0);
   float XA[N][3], XB[N][3], YA[3], YB[3];
   int j = jstart + 1;
   if (cx.r0 > 0) {
-    cx.template prologue<SB>(jstart);
-    cx.template init<SB>(XB, YB, jstart);
-    cx.template step<false, false, SA>(j, XB, XA, YB, YA);
+    cx.prologue(jstart);
+    cx.init(XB, YB, jstart);
+    cx.template step<false, false>(j, XB, XA, YB, YA);
     ++j;
   } else {
-    cx.template prologue<SA>(jstart);
-    cx.template init<SA>(XA, YA, jstart);
+    cx.prologue(jstart);
+    cx.init(XA, YA, jstart);
   }
   bool cur_is_a = true;
   for (; j <= cx.jlast; j += 2) {
-    cx.template step<true, false, SB>(j, XA, XB, YA, YB);
+    cx.template step<true, false>(j, XA, XB, YA, YB);
     if (j + 1 > cx.jlast) { cur_is_a = false; break; }
-    cx.template step<true, false, SA>(j + 1, XB, XA, YB, YA);
+    cx.template step<true, false>(j + 1, XB, XA, YB, YA);
   }
   if (cx.r1 == a.h) {   // the strip owns the last image row: one more step whose new row is the reflected row h-2
     if (!cur_is_a) {
@@ -798,7 +724,7 @@ __device__ __forceinline__ float recon_main_body(const ReconMainArgs& a) {   // 
 #pragma unroll
         for (int c = 0; c < 3; ++c) XA[k][c] = XB[k][c];
     }
-    cx.template step<true, true, SB>(a.h, XA, XB, YA, YB);
+    cx.template step<true, true>(a.h, XA, XB, YA, YB);
   }
   if (a.live != nullptr && (SINGLE || a.last_pass)) {   // this strip's entry of the liveness table: lane k stores support k's column mask (zeros beyond NT)
     unsigned long long mine = 0ull;
@@ -864,14 +790,8 @@ __device__ __forceinline__ void recon_main_reduce(const ReconMainArgs& a, MainTa
 
 // register budget: up to two supports are held to 128 VGPRs (4 waves per SIMD: the K0-fused instantiation uses 126, nothing spilled), three and four to
 // 168 (3 waves; the four-support instantiation uses 158).  A fifth wave (96 VGPRs) spills 28 values: profiles/r04_fwd_shape_sweep.txt
-#ifdef SMD_TRACE_WAVES   // diagnosis builds only (scripts/dev/wave_trace.py): when and where every wave of the last launch ran
-__device__ unsigned long long g_wave_trace[1 << 16][3];
-#endif
-template <int N, bool SSIM, bool SINGLE, bool AUX, bool DISP, int LA = 1, bool SH = false>
-__global__ __launch_bounds__(64*kWavesPerBlock, ((N <= 2 && LA == 1) ? 4 : 3)) void k_recon_main(const ReconMainArgs a) {
-#ifdef SMD_TRACE_WAVES
-  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-#endif
+template <int N, bool SSIM, bool SINGLE, bool AUX, bool DISP, bool SH = false>
+__global__ __launch_bounds__(64*kWavesPerBlock, (N <= 2 ? 4 : 3)) void k_recon_main(const ReconMainArgs a) {
   __shared__ MainTail tail;
   const bool reduce = (SINGLE || a.last_pass) && a.partial != nullptr;
   if (reduce) {                       // the only block barrier, at the start, where every wave still is
@@ -884,30 +804,16 @@ __global__ __launch_bounds__(64*kWavesPerBlock, ((N <= 2 && LA == 1) ? 4 : 3)) v
     // reduction chain ends long before the main blocks do.
     if (a.guest_blocks != 0 && (int)blockIdx.x >= a.main_blocks) { smooth_main_block(a.sc, a.b, a.sm, (int)blockIdx.x - a.main_blocks); return; }
   }
-  const float lane_sum = recon_main_body<N, SSIM, SINGLE, AUX, DISP, LA, SH>(a);
-#ifdef SMD_TRACE_WAVES
-  if ((threadIdx.x & 63) == 0) {
-    const unsigned widx = blockIdx.x*kWavesPerBlock + (threadIdx.x >> 6);
-    if (widx < (1u << 16)) {
-      g_wave_trace[widx][0] = t0; g_wave_trace[widx][1] = __builtin_amdgcn_s_memrealtime();
-      g_wave_trace[widx][2] = ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 20) << 32) | __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);
-    }
-  }
-#endif
+  const float lane_sum = recon_main_body<N, SSIM, SINGLE, AUX, DISP, SH>(a);
   if (reduce) recon_main_reduce(a, tail, lane_sum);
 }
-#ifdef SMD_TRACE_WAVES
-extern "C" int smd_debug_wave_trace(unsigned long long* host_out, int max_waves) {
-  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_wave_trace), (size_t)max_waves*3*sizeof(unsigned long long), 0, hipMemcpyDeviceToHost);
-}
-#endif
 
 // A launch records which instantiation it is (smd_last_kernel_variant): the label bench.py prints is the kernel that ran.
-template <int N, bool SSIM, bool SINGLE, bool AUX, bool DISP, int LA = 1, bool SH = false>
+template <int N, bool SSIM, bool SINGLE, bool AUX, bool DISP, bool SH = false>
 static void launch_main_t(dim3 grid, dim3 block, hipStream_t st, const ReconMainArgs& a) {
   auto tf = [](bool v) { return v ? "true" : "false"; };
-  note_variant(0, "smd::k_recon_main<%d, %s, %s, %s, %s, %d, %s>", N, tf(SSIM), tf(SINGLE), tf(AUX), tf(DISP), LA, tf(SH));
-  hipLaunchKernelGGL((k_recon_main<N, SSIM, SINGLE, AUX, DISP, LA, SH>), grid, block, 0, st, a);
+  note_variant(0, "smd::k_recon_main<%d, %s, %s, %s, %s, %s>", N, tf(SSIM), tf(SINGLE), tf(AUX), tf(DISP), tf(SH));
+  hipLaunchKernelGGL((k_recon_main<N, SSIM, SINGLE, AUX, DISP, SH>), grid, block, 0, st, a);
 }
 
 int recon_main_blocks(const ReconMainArgs& a) {
@@ -929,8 +835,7 @@ hipError_t launch_recon_main(const ReconMainArgs& a_in, hipStream_t st) {
   // hot: every support in one launch, no extras; otherwise the general instantiation (carried min / sum, noise tensor, warp output)
 #define SMD_MAIN(N_) do { \
     if (ssim && single && !aux) { \
-      if (disp && N_ <= 2 && a.lookahead == 2) launch_main_t<(N_ <= 2 ? N_ : 2), true, true, false, true, 2>(grid, block, st, a); \
-      else if (disp && a.share) launch_main_t<N_, true, true, false, true, 1, true>(grid, block, st, a); \
+      if (disp && a.share) launch_main_t<N_, true, true, false, true, true>(grid, block, st, a); \
       else if (disp) launch_main_t<N_, true, true, false, true>(grid, block, st, a); \
       else launch_main_t<N_, true, true, false, false>(grid, block, st, a); \
     } else if (ssim) { \

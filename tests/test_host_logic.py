@@ -43,13 +43,20 @@ def test_library_exports_every_declared_symbol():
         got = ['p' if t in (C.c_void_p, C.c_char_p) else ('f' if t is C.c_float else 'i') for t in proto]
         assert got == kinds, f'{name}: ctypes prototype {got} does not match the header {kinds}'
     assert _lib.lib.smd_abi_version() == 8
-    # launch-shape knobs (the parity tests' pins): known name, unknown name, experiments-only name in the product build; and nothing reads the environment
-    assert _lib.set_knob('fwd_rh', 12) is True and _lib.set_knob('bwd_pair', 1) is False
-    with pytest.raises(ValueError): _lib.set_knob('no_such_knob', 1)
+    # launch-shape knobs (the parity tests' pins): known name, unknown name, the names of the removed experiment knobs; and nothing reads the environment
+    assert _lib.set_knob('fwd_rh', 12) is True
+    for name in ('no_such_knob', 'bwd_pair', 'fwd_ahead', 'smooth_chain'):
+        with pytest.raises(ValueError): _lib.set_knob(name, 1)
+    # the header's list of names is the library's table: every listed name is accepted, and the table holds no name the list lacks
+    listed = re.search(r'Names:(.*?)\.\n', header, flags=re.S).group(1).replace('*', ' ').split()
+    assert len(listed) >= 17 and len(set(listed)) == len(listed)
+    for name in listed: assert _lib.set_knob(name, 1) is True, name
+    table = re.search(r'kKnobs\[\] = \{(.*?)\};', (ROOT/'slowtv_monodepth_amd'/'csrc'/'smd_api.hip').read_text(), flags=re.S).group(1)
+    assert set(re.findall(r'"(\w+)"', table)) == set(listed)
     _lib.reset_knobs()
     import subprocess
     syms = subprocess.run(['nm', '-D', '--undefined-only', str(_lib.lib_path)], capture_output=True, text=True).stdout
-    assert 'getenv' not in syms, 'the product library must not read the environment (knobs: smd_set_knob; experiments: make EXPERIMENTS=1)'
+    assert 'getenv' not in syms, 'the product library must not read the environment (knobs: smd_set_knob)'
     assert _lib.lib.smd_image_recon_workspace_bytes(12, 2, 4, 192, 640) > 2*12*4*12*4   # at least the pose partials
     assert _lib.lib.smd_image_recon_workspace_bytes(0, 2, 4, 192, 640) == 0
     # image part (texels + target pixels + two window-term planes) + the tail: K0 row table for SMD_MAX_SCALES pyramid levels + 1 + b arrival counters (padded to 16 B),
