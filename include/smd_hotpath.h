@@ -577,6 +577,31 @@ int smd_flip_blend_bwd(const float* const* g_out, const float* const* ramp, floa
                        int S, int planes, int flags, float scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * FeatDepth's feature regularisers (smd_featreg.hip) — replace `FeatPeakReg` and `FeatSmoothReg` (src/regularizers/smooth.py:100-176, on compute_grad and
+ * compute_laplacian, :12-48) and the per-scale loop around them (src/core/handlers.py:304-305) for every level of a feature pyramid in ONE launch:
+ *   dx[i][j] = |x[i][j] - x[i][j+1]|, dy[i][j] = |x[i][j] - x[i+1][j]|, each with a ZERO last column / row; the second-order differences dxx, dyx (along j)
+ *   and dxy, dyy (along i) are the same differences of those padded maps, so dxx[..][w-2] = |dx[..][w-2] - 0| and their last column / row is 0 again
+ *   peaky_s  = -(mean(wx dx) + mean(wy dy))                         smooth_s = mean(wxx dxx) + mean(wyy dyy) + mean(wxy dxy) + mean(wyx dyx)
+ *   w* = exp(-(mean over the 3 channels of the same difference of img)) with SMD_FEATREG_PEAKY_EDGES / SMD_FEATREG_SMOOTH_EDGES, else 1
+ *   *out_peaky = mean_s(peaky_s / 2^s), *out_smooth = mean_s(smooth_s / 2^s)        (S = 1: the regulariser itself)
+ * feat[s]: (B, Cs[s], hs[s], ws[s]) fp32, img[s]: (B, 3, hs[s], ws[s]) fp32 (the image already resized to the level), contiguous; every size >= 1,
+ * S <= SMD_MAX_SCALES.  SMD_FEATREG_PEAKY / SMD_FEATREG_SMOOTH select what is computed (at least one); an output that is not selected is written as 0.
+ * Forward: one sweep that writes two fp64 sums per block to the workspace, then a one-block second stage in a fixed order: no atomics, no full-size
+ * intermediates, two runs are bit-equal.  smd_feat_regs_workspace_bytes: 0 for sizes that are not served (a level of 2^31 elements or more).
+ * Backward: g_peaky, g_smooth are DEVICE scalars; either may be NULL (not both), and the gradient written is then exactly the other loss's.  g_feat[s] is
+ * written once per element as a gather (sign(0) = 0, the padded zeros are constants); every level passed needs its g_feat.  No workspace.
+ * Pointers need only be 4-byte aligned: a level whose rows are 16-byte aligned moves in 16-byte vectors, any other element by element. */
+#define SMD_FEATREG_PEAKY_EDGES 0x1
+#define SMD_FEATREG_SMOOTH_EDGES 0x2
+#define SMD_FEATREG_PEAKY 0x4
+#define SMD_FEATREG_SMOOTH 0x8
+size_t smd_feat_regs_workspace_bytes(const int* Cs, const int* hs, const int* ws, int S, int B);
+int smd_feat_regs_fwd(const float* const* feat, const float* const* img, const int* Cs, const int* hs, const int* ws, int S, int B, int flags,
+                      float* out_peaky, float* out_smooth, void* workspace, size_t workspace_bytes, void* stream);
+int smd_feat_regs_bwd(const float* const* feat, const float* const* img, const float* g_peaky, const float* g_smooth, float* const* g_feat,
+                      const int* Cs, const int* hs, const int* ws, int S, int B, int flags, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Pose / intrinsics prologue — one launch each instead of ~45 eager ATen launches.
  *
  * smd_pose_*: `T_from_AAt(aa, t)` (src/tools/geometry.py:181-209), followed by `T.inverse()` where invert[i] != 0

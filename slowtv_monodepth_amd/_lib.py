@@ -133,6 +133,9 @@ PROTOTYPES = {
     'smd_subpixel_bwd': (_i, [_vp]*11 + [_sz] + [_i]*9 + [_vp]),
     'smd_flip_blend_fwd': (_i, [_vp]*6 + [_i]*3 + [_f, _f, _vp]),
     'smd_flip_blend_bwd': (_i, [_vp]*6 + [_i]*3 + [_f, _vp]),
+    'smd_feat_regs_workspace_bytes': (_sz, [_vp]*3 + [_i]*2),
+    'smd_feat_regs_fwd': (_i, [_vp]*5 + [_i]*3 + [_vp]*3 + [_sz, _vp]),
+    'smd_feat_regs_bwd': (_i, [_vp]*8 + [_i]*3 + [_vp]),
     'smd_pose_fwd': (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     'smd_pose_bwd': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     'smd_intrinsics_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

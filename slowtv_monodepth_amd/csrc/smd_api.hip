@@ -1247,6 +1247,57 @@ int smd_flip_blend_bwd(const float* const* g_out, const float* const* ramp, floa
 }
 
 // ------------------------------------------------------------------------------------------------
+// FeatDepth's feature regularisers (smd_featreg.hip): every level of a feature pyramid in one launch
+static int feat_regs_fill(smd::FeatRegSet& fs, const float* const* feat, const float* const* img, const int* Cs, const int* hs, const int* ws, int S, int B, int flags) {
+  if (S < 1 || S > SMD_MAX_SCALES) return fail(SMD_E_INVALID, "S=%d outside [1, %d]", S, SMD_MAX_SCALES);
+  if (!feat || !img || !Cs || !hs || !ws) return fail(SMD_E_INVALID, "null pointer");
+  const int all = SMD_FEATREG_PEAKY_EDGES | SMD_FEATREG_SMOOTH_EDGES | SMD_FEATREG_PEAKY | SMD_FEATREG_SMOOTH;
+  if (B < 1 || (flags & ~all) || !(flags & (SMD_FEATREG_PEAKY | SMD_FEATREG_SMOOTH))) return fail(SMD_E_INVALID, "invalid sizes B=%d flags=0x%x", B, flags);
+  for (int s = 0; s < S; ++s) {
+    if (Cs[s] < 1 || hs[s] < 1 || ws[s] < 1) return fail(SMD_E_INVALID, "invalid sizes: level %d is %dx%dx%d", s, Cs[s], hs[s], ws[s]);
+    if (!feat[s] || !img[s]) return fail(SMD_E_INVALID, "null pointer for level %d", s);
+  }
+  memset(&fs, 0, sizeof(fs));
+  if (smd::feat_regs_plan(fs, Cs, hs, ws, S, B) < 1) return fail(SMD_E_INVALID, "invalid sizes: a level of 2^31 elements or more");
+  for (int s = 0; s < S; ++s) {
+    fs.L[s].x = feat[s]; fs.L[s].img = img[s];
+    fs.L[s].vec_x = ws[s] % 4 == 0 && (uintptr_t)feat[s] % 16 == 0;
+    fs.L[s].vec_img = ws[s] % 4 == 0 && (uintptr_t)img[s] % 16 == 0;
+  }
+  return SMD_OK;
+}
+size_t smd_feat_regs_workspace_bytes(const int* Cs, const int* hs, const int* ws, int S, int B) {
+  if (!Cs || !hs || !ws || S < 1 || S > SMD_MAX_SCALES || B < 1) return 0;
+  for (int s = 0; s < S; ++s) if (Cs[s] < 1 || hs[s] < 1 || ws[s] < 1) return 0;
+  smd::FeatRegSet fs;
+  memset(&fs, 0, sizeof(fs));
+  const long units = smd::feat_regs_plan(fs, Cs, hs, ws, S, B);
+  return units < 1 ? 0 : align256((size_t)units*2*sizeof(double));
+}
+int smd_feat_regs_fwd(const float* const* feat, const float* const* img, const int* Cs, const int* hs, const int* ws, int S, int B, int flags,
+                      float* out_peaky, float* out_smooth, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!out_peaky || !out_smooth || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  smd::FeatRegSet fs;
+  if (int rc = feat_regs_fill(fs, feat, img, Cs, hs, ws, S, B, flags)) return rc;
+  if (workspace_bytes < (size_t)fs.units*2*sizeof(double)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return check_launch(smd::launch_feat_regs_fwd(fs, flags, (double*)workspace, out_peaky, out_smooth, (hipStream_t)stream), "feat_regs_fwd");
+}
+int smd_feat_regs_bwd(const float* const* feat, const float* const* img, const float* g_peaky, const float* g_smooth, float* const* g_feat,
+                      const int* Cs, const int* hs, const int* ws, int S, int B, int flags, void* stream) {
+  if (!g_feat) return fail(SMD_E_INVALID, "null pointer");
+  if (!g_peaky && !g_smooth) return fail(SMD_E_INVALID, "nothing to compute");
+  if ((g_peaky && !(flags & SMD_FEATREG_PEAKY)) || (g_smooth && !(flags & SMD_FEATREG_SMOOTH))) return fail(SMD_E_INVALID, "a gradient for a loss that was not computed (flags=0x%x)", flags);
+  smd::FeatRegSet fs;
+  if (int rc = feat_regs_fill(fs, feat, img, Cs, hs, ws, S, B, flags)) return rc;
+  for (int s = 0; s < S; ++s) {
+    if (!g_feat[s]) return fail(SMD_E_INVALID, "null g_feat pointer for level %d", s);
+    fs.L[s].gx = g_feat[s];
+    fs.L[s].vec_gx = ws[s] % 4 == 0 && (uintptr_t)g_feat[s] % 16 == 0;
+  }
+  return check_launch(smd::launch_feat_regs_bwd(fs, flags, g_peaky, g_smooth, (hipStream_t)stream), "feat_regs_bwd");
+}
+
+// ------------------------------------------------------------------------------------------------
 // Depthwise 7x7 convolution (ConvNeXt)
 static bool dw_sizes_ok(int N, int C, int H, int W) {
   return N >= 1 && C >= 1 && H >= 1 && W >= 1 && (long long)N*C*smd::dwconv_tiles(H, W) < (1ll << 31) && (long long)H*W < (1ll << 30);

@@ -355,6 +355,25 @@ struct BlendSet {
 long blend_plan(BlendSet& bs, const int* hs, const int* ws, int S, int planes);
 hipError_t launch_flip_blend_fwd(const BlendSet& bs, int flags, float scale, float offset, hipStream_t st);
 hipError_t launch_flip_blend_bwd(const BlendSet& bs, int flags, float scale, hipStream_t st);
+// smd_featreg.hip: FeatDepth's two feature regularisers over a feature pyramid in one launch.  A block is one unit: a tile of (256 >> tg_log2) rows by
+// (1 << tg_log2) four-column groups of one image and one chunk of kFeatChunk channels; L[s].unit0 is the first unit of level s, `units` the grid size.
+// coef = 1/(B C h w 2^s S): what a level's sum is multiplied with.  vec_*: that operand's rows are 16-byte aligned (w % 4 == 0 and an aligned base).
+constexpr int kFeatChunk = 32;
+struct FeatLevel {
+  const float* x;
+  const float* img;
+  float* gx;
+  double coef;
+  int C, h, w, tg_log2, tiles_x, tiles_y, nchunk, unit0;
+  bool vec_x, vec_img, vec_gx;
+};
+struct FeatRegSet {
+  FeatLevel L[SMD_MAX_SCALES];
+  int S, units;
+};
+long feat_regs_plan(FeatRegSet& fs, const int* Cs, const int* hs, const int* ws, int S, int B);
+hipError_t launch_feat_regs_fwd(const FeatRegSet& fs, int flags, double* part, float* out_p, float* out_s, hipStream_t st);
+hipError_t launch_feat_regs_bwd(const FeatRegSet& fs, int flags, const float* g_peaky, const float* g_smooth, hipStream_t st);
 int bn_chunks(int N, int HW);
 hipError_t launch_bn_fwd(const float* x, const float* residual, const float* gamma, const float* beta, float* running_mean, float* running_var,
                          float momentum, float eps, int relu, float* y, float* save_mean, float* save_invstd, float* ws, int N, int C, int HW,

@@ -16,7 +16,8 @@ import torch
 
 from . import functional as F
 
-__all__ = ['image_recon', 'disp_smooth', 'disp_mask', 'disp_occ', 'feat_recon', 'autoenc_recon', 'stereo_const', 'depth_regr', 'ScaleDict', 'LazyDepths']
+__all__ = ['image_recon', 'disp_smooth', 'disp_mask', 'disp_occ', 'feat_recon', 'autoenc_recon', 'stereo_const', 'depth_regr', 'feat_smooth', 'feat_smooth_pair',
+           'ScaleDict', 'LazyDepths']
 
 
 class ScaleDict(dict):
@@ -204,6 +205,57 @@ def disp_smooth(crit, disps: dict, imgs: torch.Tensor, *, want_aux: bool = True,
     if getattr(crit, 'use_blur', False): loss, dg, ig = F.disp_smooth_blurred(disps, imgs, use_edges=crit.use_edges, want_aux=want_aux)
     else: loss, dg, ig = F.disp_smooth_fused(disps, imgs, use_edges=crit.use_edges, want_aux=want_aux, use_laplacian=getattr(crit, 'use_laplacian', False), prepared=prepared)
     return loss, ({'disp_grad': dg, 'image_grad': ig} if want_aux and dg is not None else {})
+
+
+def _resized(imgs: torch.Tensor, feats):
+    """The images resized bilinearly (`align_corners=False`) to every feature level (`ops.interpolate_like`, src/core/handlers.py:304); no gradient flows into them."""
+    with torch.no_grad():
+        return [imgs if tuple(imgs.shape[-2:]) == tuple(f.shape[-2:]) else
+                torch.nn.functional.interpolate(imgs, size=tuple(f.shape[-2:]), mode='bilinear', align_corners=False) for f in feats]
+
+
+def _feat_groups(feats, imgs, supp_feats, supp_imgs):
+    """The two groups the regularisers run over: the target features, and the supports flattened to (n*b, ...), each with its resized images."""
+    feats, supp = list(feats), [f.flatten(0, 1) for f in supp_feats]
+    return (feats, _resized(imgs.detach(), feats)), (supp, _resized(supp_imgs.detach().flatten(0, 1), supp))
+
+
+def _fused_feat_regs(feats, imgs) -> bool:
+    from .featreg import _served
+    return _served(feats, imgs)
+
+
+def feat_smooth(crit, feats, imgs: torch.Tensor, supp_feats, supp_imgs: torch.Tensor):
+    """Feature peakiness / second-order smoothness over the raw multi-scale encoder features (src/core/handlers.py:284-311): `mean_s(crit(feat_s, img_s) / 2^s)`
+    over the target features plus the same over the supports flattened to (n*b, ...), the images resized bilinearly to every level.
+
+    :param crit: `FeatPeakReg` or `FeatSmoothReg`; exactly those classes on fp32 GPU tensors run `featreg.feat_regs_pyramid`, one launch per group (a subclass
+        may compute something else and takes the per-scale loop, as does the CPU).
+    :param feats: list of (b,c_s,h_s,w_s); imgs (b,3,h,w); supp_feats: list of (n,b,c_s,h_s,w_s); supp_imgs (n,b,3,h,w).
+    :return: (loss, {})"""
+    from .featreg import feat_regs_pyramid
+    from .regularizers import FeatPeakReg, FeatSmoothReg
+    total = None
+    for fs, ims in _feat_groups(feats, imgs, supp_feats, supp_imgs):
+        if type(crit) in (FeatPeakReg, FeatSmoothReg) and _fused_feat_regs(fs, ims):
+            peaky = type(crit) is FeatPeakReg
+            l = feat_regs_pyramid(fs, ims, crit.use_edges, crit.use_edges, want_peaky=peaky, want_smooth=not peaky)[0 if peaky else 1]
+        else:
+            l = torch.stack([crit(f, i)[0]/2**s for s, (f, i) in enumerate(zip(fs, ims))]).mean()
+        total = l if total is None else total + l
+    return total, {}
+
+
+def feat_smooth_pair(peaky, smooth, feats, imgs: torch.Tensor, supp_feats, supp_imgs: torch.Tensor):
+    """`feat_smooth(peaky, ...)` and `feat_smooth(smooth, ...)` from ONE pass per group: both regularisers read the same features and the same resized images.
+    -> (l_peaky, l_smooth), or None when the fused operator does not serve these criteria or tensors (the caller then runs `feat_smooth` twice)."""
+    from .featreg import feat_regs_pyramid
+    from .regularizers import FeatPeakReg, FeatSmoothReg
+    if type(peaky) is not FeatPeakReg or type(smooth) is not FeatSmoothReg: return None
+    groups = _feat_groups(feats, imgs, supp_feats, supp_imgs)
+    if not all(_fused_feat_regs(fs, ims) for fs, ims in groups): return None
+    (tp, ts), (sp, ss) = (feat_regs_pyramid(fs, ims, peaky.use_edges, smooth.use_edges) for fs, ims in groups)
+    return tp + sp, ts + ss
 
 
 def _scale_mean_or_crit(crit, xs: dict, cls, mode: str):

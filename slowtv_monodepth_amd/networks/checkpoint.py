@@ -26,6 +26,9 @@ the `nets.<key>.` prefix (`src/core/trainer.py:58-60`), or the bare module's —
     encoder.stages_{S}.blocks.{B}.{conv_dw,norm,mlp.fc1,mlp.fc2,gamma}
                                                         encoder.stages.{S}.{B+2*(S>0)}.{dw,norm,fc1,fc2,gamma}
 
+    an `AutoencoderNet` (autoencoder.py:45-49: ONE decoder, registered as `decoder`; its encoder translates as above):
+    decoder.decoder.{N}.*                               decoder.{what `decoders.disp.decoder.{N}.*` becomes}
+
 `to_reference_state_dict` is the inverse; `load_reference_state_dict` / `reference_checkpoint` use them.  The decoder half is
 checked against the reference's own `MonodepthDecoder` in tests/test_reference_boundary.py (build container); timm is not in
 this image, so the encoder half is pinned by a round-trip test and by timm's published module names.
@@ -118,14 +121,14 @@ def _encoder_to_ref(rest: str, convnext: bool):
 
 def _split(key: str):
     """'(prefix)(encoder.|decoders.<name>.)(rest)' -> (prefix, part, rest); part is None for keys that need no translation."""
-    m = re.match(r'(.*?)(encoder\.|decoders\.(?:disp|mask)\.)(.*)', key)
+    m = re.match(r'(.*?)((?<![a-z])encoder\.|decoders\.(?:disp|mask)\.|(?:^|(?<=autoencoder\.))decoder\.)(.*)', key)   # (`autoencoder.` is no `encoder.`; a bare `decoder.` is the AutoencoderNet's)
     return (m.group(1), m.group(2), m.group(3)) if m else (key, None, '')
 
 
 def from_reference_key(key: str, out_sc=(0, 1, 2, 3), dec_kind: str = 'monodepth') -> str:
     prefix, part, rest = _split(key)
     if part is None: return key
-    if part.startswith('decoders.'):
+    if part.startswith('decoder'):
         new = _decoder_from_ref(rest, list(out_sc), dec_kind)
         return prefix + part + (new if new is not None else rest)
     return prefix + part + _encoder_from_ref(rest)
@@ -134,7 +137,7 @@ def from_reference_key(key: str, out_sc=(0, 1, 2, 3), dec_kind: str = 'monodepth
 def to_reference_key(key: str, out_sc=(0, 1, 2, 3), convnext: bool = False, dec_kind: str = 'monodepth') -> str:
     prefix, part, rest = _split(key)
     if part is None: return key
-    if part.startswith('decoders.'):
+    if part.startswith('decoder'):
         new = _decoder_to_ref(rest, list(out_sc), dec_kind)
         return prefix + part + (new if new is not None else rest)
     return prefix + part + _encoder_to_ref(rest, convnext)
@@ -157,7 +160,7 @@ def _dec_kind(module: nn.Module) -> str:
 def _is_convnext(module: nn.Module, key: str) -> bool:
     """Is the encoder that owns `key` a ConvNeXt trunk?  (a DepthNet and a PoseNet of one trainer may differ)"""
     if 'encoder.' not in key: return False
-    owner_path = key.split('encoder.')[0].rstrip('.')
+    owner_path = re.split(r'(?<![a-z])encoder\.', key)[0].rstrip('.')
     try: owner = module.get_submodule(owner_path) if owner_path else module
     except AttributeError: return False
     return hasattr(getattr(owner, 'encoder', None), 'stages')

@@ -171,15 +171,18 @@ class MonoDepthModule(nn.Module):
         self.backend = loss_backend or HipLossBackend()
         self.metrics = parsers.get_metrics()   # validation depth metrics (src/core/trainer.py:48); their buffers are non-persistent: the state dict is unchanged
         self._w_cache = {}     # the frozen loss weights as host numbers, re-read whenever a state dict (checkpoint, --resume) rewrote them: `_loss_weight`
-        # Losses whose inputs only networks outside this package produce (the autoencoder network and the
-        # virtual-stereo decoder head are out of scope; their handlers and criteria exist and are parity-tested on their own):
+        # Losses whose inputs a network that is not configured would produce (the `autoencoder` network), or that no network of this package produces
+        # (the virtual-stereo decoder head is out of scope; its handler and criterion exist and are parity-tested on their own):
         # refuse at construction instead of failing with a KeyError in the middle of the first step.
-        needs = {'feat_recon': ('autoencoder', 'an `autoencoder` network (fwd["autoenc_feats"])'),
-                 'autoenc_recon': ('autoencoder', 'an `autoencoder` network (fwd["autoenc_imgs_up"])'),
-                 'stereo_const': (None, 'a depth network with `use_virtual_stereo` (fwd["disp_stereo"], its up-sampled forms and y["T_stereo"])')}
-        for k, (net_key, what) in needs.items():
+        needs = {'feat_recon': ('autoencoder', 'an `autoencoder` network (fwd["autoenc_feats"])', 'feat_recon'),
+                 'autoenc_recon': ('autoencoder', 'an `autoencoder` network (fwd["autoenc_imgs_up"])', 'autoenc_recon'),
+                 'feat_peaky': ('autoencoder', 'an `autoencoder` network (fwd["autoenc_feats"])', 'feat_smooth'),
+                 'feat_smooth': ('autoencoder', 'an `autoencoder` network (fwd["autoenc_feats"])', 'feat_smooth'),
+                 'stereo_const': (None, 'a depth network with `use_virtual_stereo` (fwd["disp_stereo"], its up-sampled forms and y["T_stereo"])', 'stereo_const')}
+        for k, (net_key, what, handler) in needs.items():
             if k in self.losses and (net_key is None or net_key not in self.nets):
-                raise NotImplementedError(f'loss "{k}" needs {what}, which this package does not build; the handler `handlers.{k}` can be called directly')
+                which = 'which this package does not build' if net_key is None else 'which `cfg.net` does not configure'
+                raise NotImplementedError(f'loss "{k}" needs {what}, {which}; the handler `handlers.{handler}` can be called directly')
         # Predictive masks: the criterion that consumes them and the decoder that produces them must be configured together (reference cfg/default.yaml
         # sets `net.depth.mask_name` and `loss.img_recon.mask_name` side by side); refuse a half here instead of a shape error inside the loss.
         depth_mask = getattr(self.nets['depth'], 'mask_name', None) if 'depth' in self.nets else None
@@ -205,6 +208,7 @@ class MonoDepthModule(nn.Module):
         self._side_streams = {}
         self._prep_streams = {}
         self._prepared = None
+        self._feat_pair = None     # (loss key, features, value): the second feature regulariser's loss, computed with the first's (`_feat_reg`)
         # frame-only half of the reconstruction loss ahead of the networks: 'own' = on its own side stream at the start of the step,
         # 'pose' = on the pose network's side stream behind that network, False = inline, inside the loss (after the networks)
         self.prep_ahead = tcfg.get('prep_ahead', os.environ.get('SMD_PREP_AHEAD', 'pose'))
@@ -255,6 +259,14 @@ class MonoDepthModule(nn.Module):
                         if isinstance(v, torch.Tensor): v.record_stream(main)
                     for v in (produced.get('_pose_leaves') or ())[:2]: v.record_stream(main)   # read by the loss path's backward on the main stream
                 fwd.update(produced)
+            elif key == 'autoencoder':   # the target, then the supports flattened to (n*b, ...) (src/core/trainer.py:267-273)
+                n = len(idxs_all)
+                supp = x['supp_imgs'].flatten(0, 1)
+                if self.channels_last: supp = supp.contiguous(memory_format=torch.channels_last)
+                with self._autocast(imgs.device.type): out, out_supp = net(imgs), net(supp)
+                fwd.update(out)
+                fwd['supp_autoenc_feats'] = [f.unflatten(0, (n, -1)) for f in out_supp['autoenc_feats']]
+                fwd['supp_autoenc_imgs'] = {s: v.unflatten(0, (n, -1)) for s, v in out_supp['autoenc_imgs'].items()}
             else:
                 raise KeyError(f'Unrecognized key: {key}.')
         if side is not None: main.wait_stream(side)
@@ -295,6 +307,11 @@ class MonoDepthModule(nn.Module):
             fn = getattr(self.backend, 'upsample_masks', None)
             if fn is not None: fwd['mask_up'] = fn(fwd['mask'], tuple(x['imgs'].shape[-2:]))
             else: fwd['mask_up'] = {k: torch.nn.functional.interpolate(v, size=tuple(x['imgs'].shape[-2:]), mode='bilinear', align_corners=False) for k, v in fwd['mask'].items()}
+        if 'autoenc_imgs' in fwd:   # the autoencoder's reconstructions at the image size (src/core/trainer.py:326-331)
+            size, n = tuple(x['imgs'].shape[-2:]), len(x['supp_idxs'])
+            up = lambda v: v.float() if tuple(v.shape[-2:]) == size else torch.nn.functional.interpolate(v.float(), size=size, mode='bilinear', align_corners=False)
+            fwd['autoenc_imgs_up'] = {s: up(v) for s, v in fwd['autoenc_imgs'].items()}
+            fwd['supp_autoenc_imgs_up'] = {s: up(v.flatten(0, 1)).unflatten(0, (n, -1)) for s, v in fwd['supp_autoenc_imgs'].items()}
         # a stereo support (index 0) brings its known pose with the batch instead of a predicted one (src/core/trainer.py:347)
         leaves, Ts_all = fwd.get('_pose_leaves'), fwd.get('_Ts_all')
         if (leaves is not None and Ts_all is not None and [int(i) for i in x['supp_idxs']] == list(leaves[3])
@@ -328,12 +345,15 @@ class MonoDepthModule(nn.Module):
                 elif k == 'feat_recon':      # feature-metric reconstruction on an autoencoder's features, src/core/trainer.py:405-411
                     if 'autoenc_feats' not in fwd: raise KeyError('Missing autoencoder features "autoenc_feats" (no `autoencoder` network is configured).')
                     from . import handlers
-                    l, ld = handlers.feat_recon(crit, self.synth, fwd['depth_up'], fwd.get('mask_up'), fwd['autoenc_feats'], fwd['supp_autoenc_feats'],
-                                                fwd['Ts'], fwd.get('K', y['K']))
+                    l, ld = getattr(self.backend, 'feat_recon', handlers.feat_recon)(crit, self.synth, fwd['depth_up'], fwd.get('mask_up'), fwd['autoenc_feats'],
+                                                                                     fwd['supp_autoenc_feats'], fwd['Ts'], fwd.get('K', y['K']))
                 elif k == 'autoenc_recon':   # src/core/trainer.py:413-418
                     if 'autoenc_imgs_up' not in fwd: raise KeyError('Missing autoencoder reconstructions "autoenc_imgs_up" (no `autoencoder` network is configured).')
                     from . import handlers
-                    l, ld = handlers.autoenc_recon(crit, fwd['autoenc_imgs_up'], y['imgs'], fwd['supp_autoenc_imgs_up'], y['supp_imgs'])
+                    l, ld = getattr(self.backend, 'autoenc_recon', handlers.autoenc_recon)(crit, fwd['autoenc_imgs_up'], y['imgs'], fwd['supp_autoenc_imgs_up'], y['supp_imgs'])
+                elif k in ('feat_peaky', 'feat_smooth'):   # the feature regularisers on the autoencoder's raw features, src/core/trainer.py:441-447
+                    if 'autoenc_feats' not in fwd: raise KeyError('Missing autoencoder features "autoenc_feats" (no `autoencoder` network is configured).')
+                    l, ld = self._feat_reg(k, crit, fwd, y), {}
                 elif k == 'stereo_const':    # virtual-stereo consistency, src/core/trainer.py:420-428
                     if 'disp_stereo' not in fwd: raise KeyError('Missing virtual stereo prediction "disp_stereo".')
                     if 'T_stereo' not in y: raise KeyError('Missing stereo pair "T_stereo".')
@@ -353,6 +373,23 @@ class MonoDepthModule(nn.Module):
             loss_dict[f'loss_{k}'] = l
             loss_dict.update(ld)
         return loss, loss_dict
+
+    def _feat_reg(self, k: str, crit, fwd: dict, y: dict):
+        """`handlers.feat_smooth` for the loss key `k`.  With BOTH `feat_peaky` and `feat_smooth` configured the two read the same features and images: the
+        first key computes both in one pass per group (`handlers.feat_smooth_pair`) and leaves the other's value for the second key, within this step only
+        (`step` clears it; the entry also remembers whose features it was computed from)."""
+        from . import handlers
+        args = (fwd['autoenc_feats'], y['imgs'], fwd['supp_autoenc_feats'], y['supp_imgs'])
+        other = 'feat_smooth' if k == 'feat_peaky' else 'feat_peaky'
+        kept, self._feat_pair = self._feat_pair, None
+        if kept is not None and kept[0] == k and kept[1] is fwd['autoenc_feats']: return kept[2]
+        if other in self.losses and list(self.losses).index(other) > list(self.losses).index(k):
+            crits = (crit, self.losses[other]) if k == 'feat_peaky' else (self.losses[other], crit)
+            pair = handlers.feat_smooth_pair(*crits, *args)
+            if pair is not None:
+                self._feat_pair = (other, fwd['autoenc_feats'], pair[1 if k == 'feat_peaky' else 0])
+                return pair[0 if k == 'feat_peaky' else 1]
+        return handlers.feat_smooth(crit, *args)[0]
 
     def _loss_weight(self, k: str) -> float:
         """`self.weights[k]` as a host float for the single-node loss path (the kernel takes the weights as scalars).  The `ParameterDict` is part of the state
@@ -408,7 +445,7 @@ class MonoDepthModule(nn.Module):
         finally:
             # the prep-ahead state belongs to THIS step: a later `module.forward(x)` (validation, inference) must neither launch the
             # prep for the previous batch nor keep that batch (and its 150 MB packed buffer) alive
-            self._y = self._prepared = self._K_inv = None
+            self._y = self._prepared = self._K_inv = self._feat_pair = None
         return loss, loss_dict, fwd
 
     def _default_metrics(self) -> bool:
