@@ -26,12 +26,17 @@ def _run(F, c, ops):
 def test_value_edges(F, c):
     ops = c.operands(torch.Generator().manual_seed(len(c.name)*7919 + 17))
     ref = {k: v.detach() for k, v in c.ref({k: v.clone() for k, v in ops.items()}, V.F64).items() if v is not None}
+    yard = V.yardstick(c, ops)      # ATen's fp32 sequence on the CPU, for the bounds that are measured against it (never the kernel's own output)
     A, B = _run(F, c, ops), _run(F, c, ops)
-    for k, e in V.errors(c, A, ref).items(): print(f'{c.name}: {k}: {e:.3g} of its bound {c.tol.get(k, c.tol.get("*"))}')
+    for k, e in V.errors(c, A, ref, ops, yard).items():
+        bound = c.tol.get(k, c.tol.get('*'))
+        what = f'{bound[0]} bound' if bound[0] == 'elem' else bound
+        if bound[0] in V.YARD_KINDS: what = f'{bound}, torch fp32 {V.excess(yard[k], ref[k], ("rel", 1.0)):.2e} of the maximum'
+        print(f'{c.name}: {k}: {e:.3g} of its bound {what}')
     for k, v in A.items():
         if bool(ref[k].isfinite().all()): assert_finite(v, f'{c.name}: {k}')
         else: assert V.same_pattern(v.double(), ref[k].double().reshape(v.shape)), f'{c.name}: {k}: the non-finite elements are not where the reference has them'
-    V.judge(c, A, ref)
+    V.judge(c, A, ref, ops, yard)
     assert set(A) == set(B)
     for k, v in A.items():
         bits = torch.int32 if v.dtype == torch.float32 else torch.int16      # (the bit patterns: NaNs and signed zeros included)
