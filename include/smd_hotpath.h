@@ -61,6 +61,7 @@ extern "C" {
 #define SMD_REGR_LOG_L1 0x1
 #define SMD_REGR_BERHU 0x2
 #define SMD_REGR_INVERT 0x4    /* RegressionLoss(invert=True): both inputs through to_inv first (:70) */
+#define SMD_REGR_AUTOMASK 0x8  /* smd_hints_regr_*: RegressionLoss(use_automask=True): the Depth-Hints automask of src/core/handlers.py:236-256 from `err` */
 
 #define SMD_MAX_SCALES 8
 #define SMD_MAX_SUPPORTS 8
@@ -600,6 +601,26 @@ int smd_feat_regs_fwd(const float* const* feat, const float* const* img, const i
                       float* out_peaky, float* out_smooth, void* workspace, size_t workspace_bytes, void* stream);
 int smd_feat_regs_bwd(const float* const* feat, const float* const* img, const float* g_peaky, const float* g_smooth, float* const* g_feat,
                       const int* Cs, const int* hs, const int* ws, int S, int B, int flags, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Depth-Hints proxy-depth regression over every scale (smd_hints.hip) — replaces `handlers.depth_regr` (src/core/handlers.py:201-259) once the photometric
+ * errors are known, without the (S*b, ...) expansions of the depths, the hints and the mask:
+ *   m[s][i] = hints[i] > 0 && (no SMD_REGR_AUTOMASK || err[1+s][i] > err[0][i])      e[s][i] = m ? crit(depth[s][i], hints[i]) : 0      loss = sum(e) / sum(m)
+ * depth (S,b,h,w), hints (b,h,w) (0 = no hint), err (S+1,b,h,w) with SMD_REGR_AUTOMASK, else NULL: err[0] the photometric error of the supports warped by
+ * the hints, err[1+s] by depth[s] (`compute_photo`, src/losses/reconstruction.py:79-96; smd_image_recon_fwd's `err` over the stack [hints, depth_0 ..]).
+ * flags: SMD_REGR_{L1,LOG_L1,BERHU} | SMD_REGR_INVERT | SMD_REGR_AUTOMASK; crit, `to_inv` and berHu's threshold 0.2 * max|diff| over ALL S*b*h*w elements
+ * (masked or not) are smd_regression_*'s, element by element.  sum(m) = 0 gives NaN, as the reference does.  S <= SMD_MAX_SCALES, b*h*w < 2^31.
+ * Outputs: loss (1); mask0 (b,h,w) uint8 0/1, the mask of scale 0 (`mask_regr`); bits ((b*h*w + 3)/4 32-bit words: bit 4 s + k of word g is m[s][4 g + k]), the
+ * whole mask for the backward; stats (8 floats) for the backward.  The hints are read once per pixel for all scales.  fp64 block sums in the workspace and
+ * a one-block second stage in a fixed order: no atomics, two runs are bit-equal; berHu takes a second sweep once the maximum is known.
+ * Backward: ONE sweep, g_depth (S,b,h,w) from `bits` and `stats` (it does not read err); g_loss is a DEVICE scalar.  No workspace.
+ * Pointers need only their element's alignment (the workspace: 8 bytes): with b*h*w % 4 == 0 and 16-byte aligned bases four pixels move as one 16-byte
+ * vector, otherwise element by element. */
+size_t smd_hints_regr_workspace_bytes(int S, int b, int h, int w);
+int smd_hints_regr_fwd(const float* depth, const float* hints, const float* err, int S, int b, int h, int w, int flags, float* loss, uint8_t* mask0,
+                       uint32_t* bits, float* stats, void* workspace, size_t workspace_bytes, void* stream);
+int smd_hints_regr_bwd(const float* depth, const float* hints, const uint32_t* bits, const float* stats, const float* g_loss, float* g_depth,
+                       int S, int b, int h, int w, int flags, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Pose / intrinsics prologue — one launch each instead of ~45 eager ATen launches.

@@ -19,7 +19,7 @@ lib_path = Path(os.environ.get('SMD_HOTPATH_LIB', _HERE/'libsmd_hotpath.so'))
 
 FLAGS = {'use_min': 0x1, 'use_automask': 0x2, 'loss_l1': 0x4, 'need_k_grad': 0x8, 'use_edges': 0x10, 'loss_l2': 0x20, 'packed_ready': 0x40,
          'mask_explainability': 0x80, 'mask_uncertainty': 0x100, 'use_laplacian': 0x200, 'bwd_skip_rows': 0x400, 'edges_ready': 0x800, 'bwd_no_live': 0x1000}
-REGR_FLAGS = {'l1': 0x0, 'log_l1': 0x1, 'berhu': 0x2, 'invert': 0x4}
+REGR_FLAGS = {'l1': 0x0, 'log_l1': 0x1, 'berhu': 0x2, 'invert': 0x4, 'automask': 0x8}
 SEL_MASKED = 255
 MAX_SCALES = 8
 MAX_SUPPORTS = 8
@@ -136,6 +136,9 @@ PROTOTYPES = {
     'smd_feat_regs_workspace_bytes': (_sz, [_vp]*3 + [_i]*2),
     'smd_feat_regs_fwd': (_i, [_vp]*5 + [_i]*3 + [_vp]*3 + [_sz, _vp]),
     'smd_feat_regs_bwd': (_i, [_vp]*8 + [_i]*3 + [_vp]),
+    'smd_hints_regr_workspace_bytes': (_sz, [_i]*4),
+    'smd_hints_regr_fwd': (_i, [_vp]*3 + [_i]*5 + [_vp]*5 + [_sz, _vp]),
+    'smd_hints_regr_bwd': (_i, [_vp]*6 + [_i]*5 + [_vp]),
     'smd_pose_fwd': (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     'smd_pose_bwd': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     'smd_intrinsics_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

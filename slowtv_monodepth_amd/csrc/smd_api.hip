@@ -1298,6 +1298,39 @@ int smd_feat_regs_bwd(const float* const* feat, const float* const* img, const f
 }
 
 // ------------------------------------------------------------------------------------------------
+// Depth-Hints regression over all scales (smd_hints.hip)
+static const int kHintsFlags = SMD_REGR_LOG_L1 | SMD_REGR_BERHU | SMD_REGR_INVERT | SMD_REGR_AUTOMASK;
+static bool hints_sizes_ok(int S, int b, int h, int w) {
+  return S >= 1 && S <= SMD_MAX_SCALES && b >= 1 && h >= 1 && w >= 1 && (size_t)b*h*w < ((size_t)1 << 31);
+}
+size_t smd_hints_regr_workspace_bytes(int S, int b, int h, int w) {
+  if (!hints_sizes_ok(S, b, h, w)) return 0;
+  return align256((size_t)smd::hints_blocks((size_t)b*h*w)*4*sizeof(double));
+}
+int smd_hints_regr_fwd(const float* depth, const float* hints, const float* err, int S, int b, int h, int w, int flags, float* loss, uint8_t* mask0,
+                       uint32_t* bits, float* stats, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!depth || !hints || !loss || !mask0 || !bits || !stats || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (!hints_sizes_ok(S, b, h, w)) return fail(SMD_E_INVALID, "invalid sizes S=%d b=%d h=%d w=%d", S, b, h, w);
+  if ((flags & ~kHintsFlags) || ((flags & SMD_REGR_LOG_L1) && (flags & SMD_REGR_BERHU))) return fail(SMD_E_INVALID, "invalid flags 0x%x", flags);
+  if (((flags & SMD_REGR_AUTOMASK) != 0) != (err != nullptr)) return fail(SMD_E_INVALID, "err goes with SMD_REGR_AUTOMASK (flags=0x%x, err %s)", flags, err ? "given" : "NULL");
+  if ((uintptr_t)bits % 4 || (uintptr_t)workspace % 8) return fail(SMD_E_INVALID, "bits needs 4-byte, the workspace 8-byte alignment");
+  if (workspace_bytes < smd_hints_regr_workspace_bytes(S, b, h, w)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  const size_t P = (size_t)b*h*w;
+  const int vec = P % 4 == 0 && (uintptr_t)depth % 16 == 0 && (uintptr_t)hints % 16 == 0 && (uintptr_t)err % 16 == 0 && (uintptr_t)mask0 % 4 == 0;
+  return check_launch(smd::launch_hints_regr_fwd(depth, hints, err, S, P, flags, vec, loss, mask0, bits, stats, (double*)workspace, (hipStream_t)stream), "hints_regr_fwd");
+}
+int smd_hints_regr_bwd(const float* depth, const float* hints, const uint32_t* bits, const float* stats, const float* g_loss, float* g_depth,
+                       int S, int b, int h, int w, int flags, void* stream) {
+  if (!depth || !hints || !bits || !stats || !g_loss || !g_depth) return fail(SMD_E_INVALID, "null pointer");
+  if (!hints_sizes_ok(S, b, h, w)) return fail(SMD_E_INVALID, "invalid sizes S=%d b=%d h=%d w=%d", S, b, h, w);
+  if ((flags & ~kHintsFlags) || ((flags & SMD_REGR_LOG_L1) && (flags & SMD_REGR_BERHU))) return fail(SMD_E_INVALID, "invalid flags 0x%x", flags);
+  if ((uintptr_t)bits % 4) return fail(SMD_E_INVALID, "bits needs 4-byte alignment");
+  const size_t P = (size_t)b*h*w;
+  const int vec = P % 4 == 0 && (uintptr_t)depth % 16 == 0 && (uintptr_t)hints % 16 == 0 && (uintptr_t)g_depth % 16 == 0;
+  return check_launch(smd::launch_hints_regr_bwd(depth, hints, bits, S, P, flags, vec, stats, g_loss, g_depth, (hipStream_t)stream), "hints_regr_bwd");
+}
+
+// ------------------------------------------------------------------------------------------------
 // Depthwise 7x7 convolution (ConvNeXt)
 static bool dw_sizes_ok(int N, int C, int H, int W) {
   return N >= 1 && C >= 1 && H >= 1 && W >= 1 && (long long)N*C*smd::dwconv_tiles(H, W) < (1ll << 31) && (long long)H*W < (1ll << 30);

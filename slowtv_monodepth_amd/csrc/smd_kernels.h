@@ -403,6 +403,12 @@ hipError_t launch_ln_cf_fwd(const float* x, const float* gamma, const float* bet
                             float eps, hipStream_t st);
 hipError_t launch_ln_cf_bwd(const float* x, const void* g_y, int g_bf16, const float* gamma, const float* mean, const float* rstd, float* g_x, float* g_gamma,
                             float* g_beta, float* ws, int N, int C, int HW, hipStream_t st);
+// smd_hints.hip: the Depth-Hints regression over all scales (blocks of 256 groups of four pixels; 0: P outside [1, 2^31)); ws: 4 doubles per block
+int hints_blocks(size_t P);
+hipError_t launch_hints_regr_fwd(const float* depth, const float* hints, const float* err, int S, size_t P, int flags, int vec, float* loss, uint8_t* mask0,
+                                 uint32_t* bits, float* stats, double* ws, hipStream_t st);
+hipError_t launch_hints_regr_bwd(const float* depth, const float* hints, const uint32_t* bits, int S, size_t P, int flags, int vec, const float* stats,
+                                 const float* g_loss, float* g_depth, hipStream_t st);
 int regr_blocks(size_t N);
 hipError_t launch_regression_fwd(const float* pred, const float* target, const uint8_t* mask, size_t N, int flags, float* loss, float* err,
                                  float* stats, float* ws, hipStream_t st);

@@ -10,16 +10,13 @@
 // [3] d loss/d delta scratch (backward).
 #include "smd_common.h"
 #include "smd_kernels.h"
+#include "smd_regression_dev.h"
 
 namespace smd {
 
 constexpr int kRegrBlock = 256;
 constexpr int kRegrPerThread = 4;
-enum { kRegrL1 = 0, kRegrLogL1 = 1, kRegrBerhu = 2 };
-
-__device__ __forceinline__ float inv_map(float x, bool invert) { return invert ? ((x > 0.f) ? 1.f/fmaxf(x, kEps32) : 0.f) : x; }
-// d to_inv(x)/dx: -1/x^2 on the pass-through branch, 0 where x <= 0 or the clamp is active
-__device__ __forceinline__ float inv_map_grad(float x, bool invert) { return invert ? ((x >= kEps32) ? -1.f/(x*x) : 0.f) : 1.f; }
+// (the per-element functions — to_inv, the criteria, their adjoints — are smd_regression_dev.h's, shared with smd_hints.hip)
 
 template <typename T> __device__ __forceinline__ void block_reduce(T val, T* red, bool is_max, T& out) {
   red[threadIdx.x] = val;
@@ -48,7 +45,7 @@ __global__ __launch_bounds__(kRegrBlock) void k_regr_sweep1(const float* __restr
       const float m = mask ? (mask[i] ? 1.f : 0.f) : 1.f;
       mx = fmaxf(mx, diff); ms += m;
       if (mode != kRegrBerhu) {
-        const float e = m*(mode == kRegrL1 ? diff : logf(1.f + diff));
+        const float e = m*(mode == kRegrL1 ? diff : logf(1.f + diff));   // (= regr_value(m, mode, diff), spelled out: the call compiles to a select instead of this branch)
         es += e;
         if (err) err[i] = e;
       }
@@ -74,10 +71,6 @@ __global__ __launch_bounds__(kRegrBlock) void k_regr_finalize1(const float* __re
     stats[0] = (float)tmx; stats[1] = (float)tms;
     if (mode != kRegrBerhu) loss[0] = (float)(o/tms);
   }
-}
-
-__device__ __forceinline__ float berhu_value(float diff, float delta) {
-  return (diff <= delta) ? diff : (diff*diff + delta*delta)/(2.f*delta + kEps32);
 }
 
 // Sweep 2 (berHu): errors with the now-known delta; per-block masked error sum and count of elements attaining the max.
@@ -128,7 +121,7 @@ __global__ __launch_bounds__(kRegrBlock) void k_regr_bwd_delta(const float* __re
     if (i < N) {
       const float diff = fabsf(inv_map(pred[i], invert) - inv_map(target[i], invert));
       const float m = mask ? (mask[i] ? 1.f : 0.f) : 1.f;
-      if (diff > delta) acc += m*(2.f*delta*q - 2.f*(diff*diff + delta*delta))/(q*q);
+      if (diff > delta) acc += berhu_ddelta(m, diff, delta, q);
     }
   }
   float o;
@@ -152,18 +145,13 @@ __global__ __launch_bounds__(kRegrBlock) void k_regr_bwd(const float* __restrict
       const float p = pred[i], t = target[i];
       const float d = inv_map(p, invert) - inv_map(t, invert), diff = fabsf(d);
       const float ge = gs*(mask ? (mask[i] ? 1.f : 0.f) : 1.f);
-      float gd;
-      if (mode == kRegrL1) gd = ge;
-      else if (mode == kRegrLogL1) gd = ge/(1.f + diff);
-      else gd = ((diff <= delta) ? ge : ge*2.f*diff/q) + ((diff == mxd) ? g_tie : 0.f);
-      const float gv = gd*((d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f));
+      const float gv = regr_grad_diff(mode, ge, d, diff, delta, q, mxd, g_tie);
       if (g_pred) g_pred[i] = gv*inv_map_grad(p, invert);
       if (g_target) g_target[i] = -gv*inv_map_grad(t, invert);
     }
   }
 }
 
-static inline int regr_mode(int flags) { return (flags & SMD_REGR_BERHU) ? kRegrBerhu : ((flags & SMD_REGR_LOG_L1) ? kRegrLogL1 : kRegrL1); }
 int regr_blocks(size_t N) { return (int)((N + (size_t)kRegrBlock*kRegrPerThread - 1)/((size_t)kRegrBlock*kRegrPerThread)); }
 
 hipError_t launch_regression_fwd(const float* pred, const float* target, const uint8_t* mask, size_t N, int flags, float* loss, float* err,

@@ -16,7 +16,7 @@ import torch
 
 from . import functional as F
 
-__all__ = ['image_recon', 'disp_smooth', 'disp_mask', 'disp_occ', 'feat_recon', 'autoenc_recon', 'stereo_const', 'depth_regr', 'feat_smooth', 'feat_smooth_pair',
+__all__ = ['image_recon', 'disp_smooth', 'disp_mask', 'disp_occ', 'feat_recon', 'autoenc_recon', 'stereo_const', 'depth_regr', 'depth_regr_fused', 'feat_smooth', 'feat_smooth_pair',
            'ScaleDict', 'LazyDepths']
 
 
@@ -193,6 +193,15 @@ def depth_regr(crit, synth, photo, depths: dict, targets: torch.Tensor, imgs: to
             masks = masks & (photo(pred_warp, im) > photo(hints_warp, im))
     loss, ld = crit(dep, tg, masks)
     return loss, {'mask_regr': ld['mask_regr'].unflatten(0, (S, -1))[0]}
+
+
+def depth_regr_fused(crit, synth, photo, depths: dict, targets: torch.Tensor, imgs: torch.Tensor, supp_imgs: torch.Tensor, Ts: torch.Tensor, Ks: torch.Tensor):
+    """`depth_regr` (same signature, same return value) without its (n, S*b, ...) expansions: the photometric errors of the hints and of every scale from ONE
+    fused reconstruction forward that writes no warp, the mask, the regression and its gradient from `smd_hints_regr_*` (hints.py).  CPU tensors, other
+    dtypes, a `photo` that is not a plain `ReconstructionLoss.compute_photo` ('ssim' | 'l1', no predictive mask), images that are not 3-channel and poses or
+    intrinsics that require a gradient run `depth_regr`."""
+    from .hints import depth_regr_fused as fused
+    return fused(crit, synth, photo, depths, targets, imgs, supp_imgs, Ts, Ks)
 
 
 def disp_smooth(crit, disps: dict, imgs: torch.Tensor, *, want_aux: bool = True, prepared=None):

@@ -13,7 +13,7 @@ import torch
 
 from . import ops
 
-__all__ = ['texture', 'kitti_K', 'lidar_depth', 'make_batch']
+__all__ = ['texture', 'kitti_K', 'lidar_depth', 'depth_hints_field', 'make_batch', 'STEREO_BASELINE', 'STEREO_SHIFT']
 
 
 def texture(gen: torch.Generator, b: int, h: int, w: int, shift=(0.0, 0.0), device='cpu', waves: int = 6, coeffs=None):
@@ -48,18 +48,50 @@ def lidar_depth(gen: torch.Generator, b: int, H: int, W: int, device='cpu', dens
     return torch.where(keep, field, torch.zeros_like(field))[:, None]
 
 
-def make_batch(b: int, h: int, w: int, supp_idxs=(-1, 1), seed: int = 42, device='cpu', depth_shape=None):
+STEREO_BASELINE = 0.1   # KITTI's 0.54 m baseline in the reference's 5.4-scaled units (src/datasets/kitti_raw.py:134)
+STEREO_SHIFT = 3.0      # pixels the stereo partner's texture is shifted by, horizontally only
+
+
+def depth_hints_field(gen: torch.Generator, b: int, h: int, w: int, device='cpu') -> torch.Tensor:
+    """(b,1,h,w) proxy depth as a stereo matcher leaves it (`y['depth_hints']`): a dense, smooth, positive field (`lidar_depth`'s, 2 .. 60), 0 = "no hint" on
+    three rectangular holes per sample and on about 10 % of scattered pixels; the LAST sample has hints in its lower half only."""
+    field = lidar_depth(gen, b, h, w, device=device, density=2.0)          # density > 1: every pixel kept
+    keep = torch.rand(b, 1, h, w, generator=gen, device=device) >= 0.1
+    box = torch.rand(b, 3, 4, generator=gen, device=device)                # per hole: centre (y, x) and half extents, as fractions of the map
+    ys, xs = torch.meshgrid(torch.arange(h, device=device), torch.arange(w, device=device), indexing='ij')
+    for k in range(3):
+        cy, cx = box[:, k, 0, None, None]*h, box[:, k, 1, None, None]*w
+        ry, rx = 1 + box[:, k, 2, None, None]*h/6, 1 + box[:, k, 3, None, None]*w/6
+        keep &= ~(((ys - cy).abs() <= ry) & ((xs - cx).abs() <= rx))[:, None]
+    keep[-1, :, :h//2] = False
+    return torch.where(keep, field, torch.zeros_like(field))
+
+
+def make_batch(b: int, h: int, w: int, supp_idxs=(-1, 1), seed: int = 42, device='cpu', depth_shape=None, depth_hints: bool = False):
     """-> (x, y, m): x = network inputs (ImageNet-standardised), y = loss inputs (raw [0,1] images, K), m = metadata.
-    `depth_shape=(H, W)` adds `y['depth']` (`lidar_depth`), drawn after everything else: the other entries are the same with and without it."""
+    `depth_shape=(H, W)` adds `y['depth']` (`lidar_depth`), drawn after everything else: the other entries are the same with and without it.
+    A 0 among `supp_idxs` is the stereo partner: that support is the texture shifted HORIZONTALLY only, and `y['T_stereo']` (b,4,4) is its known pose —
+    identity rotation, t = (-+STEREO_BASELINE, 0, 0): even samples are the left camera (t_x < 0, as the reference's KITTI loader signs it), odd ones the right,
+    and the shift has the matching sign.  `depth_hints=True` adds `y['depth_hints']` (`depth_hints_field`), drawn last of all."""
     gen = torch.Generator(device=device).manual_seed(seed)
     imgs, coeffs = texture(gen, b, h, w, device=device)
+    sign = torch.where(torch.arange(b, device=device) % 2 == 0, -1.0, 1.0)      # the sign of T_stereo's t_x per sample
     supp = []
     for k, i in enumerate(supp_idxs):
-        dx = (2.0 + k)*(1 if i > 0 else -1)
-        supp.append(texture(gen, b, h, w, shift=(dx, 0.5*dx), device=device, coeffs=coeffs)[0])
+        if int(i) == 0:    # a point at target column u projects to u + f t_x/z in the partner: supp(x) = tex(x - f t_x/z), a shift against the sign of t_x
+            shift = (-STEREO_SHIFT*sign.view(b, 1, 1, 1), 0.0)
+        else:
+            dx = (2.0 + k)*(1 if i > 0 else -1)
+            shift = (dx, 0.5*dx)
+        supp.append(texture(gen, b, h, w, shift=shift, device=device, coeffs=coeffs)[0])
     supp = torch.stack(supp)
     x = {'imgs': ops.standardize(imgs), 'supp_imgs': ops.standardize(supp), 'supp_idxs': torch.tensor(list(supp_idxs))}
     y = {'imgs': imgs, 'supp_imgs': supp, 'K': kitti_K(b, h, w, device)}
     m = {'supp': [str(i) for i in supp_idxs]}
+    if any(int(i) == 0 for i in supp_idxs):
+        T = torch.eye(4, device=device)[None].repeat(b, 1, 1)
+        T[:, 0, 3] = STEREO_BASELINE*sign
+        y['T_stereo'] = T
     if depth_shape is not None: y['depth'] = lidar_depth(gen, b, int(depth_shape[0]), int(depth_shape[1]), device=device)
+    if depth_hints: y['depth_hints'] = depth_hints_field(gen, b, h, w, device=device)
     return x, y, m

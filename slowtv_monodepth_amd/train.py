@@ -322,8 +322,10 @@ def main(argv=None):
         raise SystemExit(f'the cfg names dataset type(s) {named}: this package trains on synthetic triplets only (datasets are out of scope); '
                          'pass --synthetic-data to run the cfg on synthetic triplets of its shape, or drop the dataset `type`')
     supp_idxs = dataset_supp_idxs(cfg)
-    batch = make_batch(b, args.shape[0], args.shape[1], supp_idxs, seed=args.seed + rank, device=device)
-    val_batch = make_batch(b, args.shape[0], args.shape[1], supp_idxs, seed=args.seed + 1000 + rank, device=device, depth_shape=args.val_depth_shape) if args.val_steps > 0 else None
+    hints = 'depth_regr' in cfg.get('loss', {})      # proxy-depth supervision reads y['depth_hints'] (src/core/trainer.py:425-433)
+    batch = make_batch(b, args.shape[0], args.shape[1], supp_idxs, seed=args.seed + rank, device=device, depth_hints=hints)
+    val_batch = (make_batch(b, args.shape[0], args.shape[1], supp_idxs, seed=args.seed + 1000 + rank, device=device, depth_shape=args.val_depth_shape, depth_hints=hints)
+                 if args.val_steps > 0 else None)
     model = wrap_ddp(StepModule(module), device)
     save_dir = args.ckpt_dir/args.name/f'{args.version:03}'
     if rank == 0: save_dir.mkdir(parents=True, exist_ok=True)

@@ -50,6 +50,13 @@ class HipLossBackend:
         from . import handlers
         return handlers.disp_mask(crit, masks)
 
+    def depth_regr(self, crit, synth, photo, depths, targets, imgs, supp_imgs, Ts, Ks):
+        """Proxy-depth (Depth Hints) regression on the fused operator (`handlers.depth_regr_fused`; what it does not serve runs `handlers.depth_regr`).
+        The poses (the pose network's outputs) and learned intrinsics go in detached: they enter the loss only through the automask, a comparison that the
+        plain handler evaluates under `no_grad` on detached copies too, and the fused handler declines operands that require a gradient."""
+        from . import handlers
+        return handlers.depth_regr_fused(crit, synth, photo, depths, targets.float(), imgs, supp_imgs, Ts.detach().float(), Ks.detach().float())
+
     def image_recon(self, crit, synth, depths, masks, imgs, supp_imgs, Ts, Ks, want_warp=True, K_inv=None, prepared=None):
         from . import handlers
         self.last_sel, self.last_path = None, 'handlers: image_recon + disp_smooth as separate autograd nodes'
@@ -340,8 +347,8 @@ class MonoDepthModule(nn.Module):
                 elif k == 'depth_regr':   # proxy-depth (Depth Hints) regression, src/core/trainer.py:425-433
                     if 'depth_hints' not in y: raise KeyError('Missing proxy depth prediction "depth_hints".')
                     from . import handlers
-                    l, ld = handlers.depth_regr(crit, self.synth, self.losses['img_recon'].compute_photo, fwd['depth_up'], y['depth_hints'],
-                                                y['imgs'], y['supp_imgs'], fwd['Ts'], fwd.get('K', y['K']))
+                    l, ld = getattr(self.backend, 'depth_regr', handlers.depth_regr)(crit, self.synth, self.losses['img_recon'].compute_photo, fwd['depth_up'], y['depth_hints'],
+                                                                                     y['imgs'], y['supp_imgs'], fwd['Ts'], fwd.get('K', y['K']))
                 elif k == 'feat_recon':      # feature-metric reconstruction on an autoencoder's features, src/core/trainer.py:405-411
                     if 'autoenc_feats' not in fwd: raise KeyError('Missing autoencoder features "autoenc_feats" (no `autoencoder` network is configured).')
                     from . import handlers
