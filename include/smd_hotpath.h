@@ -623,6 +623,30 @@ int smd_hints_regr_bwd(const float* depth, const float* hints, const uint32_t* b
                        int S, int b, int h, int w, int flags, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Feature-metric reconstruction loss from the LOW-resolution features (smd_featrecon.hip) — replaces `handlers.feat_recon` (src/core/handlers.py:70-119):
+ * the bilinear up-sampling (align_corners=False) of the target features (b,C,hf,wf) and the support features (n,b,C,hf,wf) to the depth map (b,1,H,W), the
+ * warp of the up-sampled supports by depth, T (n,b,4,4), K and K_inv (b,4,4) (`ViewSynth`, as smd_view_synth_fwd), the dense error over the channels and
+ * `ReconstructionLoss`'s reduction over the supports, per pixel, without any tensor of size (C,H,W):
+ *   flags: SMD_LOSS_L1 (sum_c |d| / C) or SMD_LOSS_L2 (sqrt(max(sum_c d^2, eps))) | SMD_USE_MIN (else the mean) | SMD_USE_AUTOMASK (the static error against the
+ *   un-warped up-sampled support, + eps * noise: `noise` (b,1,H,W), or NULL: smd_recon_reduce_fwd's generator under `seed`, equal seeds draw equal noise).
+ * Outputs: loss (1) = the mean of the reduced error; sel (b,H,W) uint8: the winning support (0 for the mean), SMD_SEL_MASKED where the automask removed the
+ * pixel; warp (n,b,C,H,W) or NULL: the warped supports for the image logger, the only full-resolution C-channel tensor the call can write.
+ * Sizes served: 2 <= H, W <= 2048, 1 <= hf <= H, 1 <= wf <= W (any ratio), C >= 1, n <= SMD_MAX_SUPPORTS, b*H*W < 2^31, n*b*C*hf*wf*4 bytes < 2^32;
+ * smd_feat_recon_workspace_bytes returns 0 for anything else.  One fp64 sum per block of 64 x 4 pixels in the workspace, added by a one-block second stage in
+ * a fixed order: no atomics, two runs are bit-equal.
+ * Backward: ONE sweep from `sel`: the selected support's samples (every support's for the mean) are recomputed, g_depth (b,H,W) and g_T (n,b,4,4) through the
+ * per-block pose sums in the workspace and the fp64 finalize of smd_view_synth_bwd.  Either may be NULL (not both): the launch then never forms its terms, and
+ * the other's bits do not change.  The l2 gradient is 0 where clamp(min=eps) is active.  No gradient to the features, K or K_inv.  g_loss is a DEVICE scalar.
+ * Pointers need only their element's alignment (the workspace: 8 bytes). */
+size_t smd_feat_recon_workspace_bytes(int b, int n, int C, int H, int W, int hf, int wf);
+int smd_feat_recon_fwd(const float* depth, const float* feat, const float* supp_feat, const float* T, const float* K, const float* K_inv, const float* noise,
+                       uint64_t seed, float* loss, uint8_t* sel, float* warp, void* workspace, size_t workspace_bytes, int b, int n, int C, int H, int W,
+                       int hf, int wf, int flags, void* stream);
+int smd_feat_recon_bwd(const float* depth, const float* feat, const float* supp_feat, const float* T, const float* K, const float* K_inv, const uint8_t* sel,
+                       const float* g_loss, float* g_depth, float* g_T, void* workspace, size_t workspace_bytes, int b, int n, int C, int H, int W, int hf, int wf,
+                       int flags, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Pose / intrinsics prologue — one launch each instead of ~45 eager ATen launches.
  *
  * smd_pose_*: `T_from_AAt(aa, t)` (src/tools/geometry.py:181-209), followed by `T.inverse()` where invert[i] != 0

@@ -1331,6 +1331,46 @@ int smd_hints_regr_bwd(const float* depth, const float* hints, const uint32_t* b
 }
 
 // ------------------------------------------------------------------------------------------------
+// Feature-metric reconstruction loss from the low-resolution features (smd_featrecon.hip).  Workspace: one double per block | the pose sums, 16-byte aligned
+// inside it whatever the base (the finalize reads them as 16-byte vectors).
+static const int kFeatReconFlags = SMD_LOSS_L1 | SMD_LOSS_L2 | SMD_USE_MIN | SMD_USE_AUTOMASK;
+static size_t feat_recon_part_bytes(int b, int H, int W) { return align256((size_t)smd::feat_recon_blocks(b, H, W)*sizeof(double)); }
+static float* feat_recon_pose_partial(void* workspace, int b, int H, int W) {
+  return (float*)(((uintptr_t)workspace + feat_recon_part_bytes(b, H, W) + 15) & ~(uintptr_t)15);
+}
+static int feat_recon_check(int b, int n, int C, int H, int W, int hf, int wf, int flags, const void* workspace, size_t workspace_bytes) {
+  if (b < 1 || n < 1 || C < 1 || H < 2 || W < 2 || hf < 1 || wf < 1) return fail(SMD_E_INVALID, "invalid sizes b=%d n=%d C=%d H=%d W=%d hf=%d wf=%d (need H, W >= 2)", b, n, C, H, W, hf, wf);
+  if (hf > H || wf > W) return fail(SMD_E_INVALID, "features larger than the depth map (%dx%d vs. %dx%d): the operator up-samples", hf, wf, H, W);
+  if ((size_t)b*H*W >= ((size_t)1 << 31)) return fail(SMD_E_INVALID, "b*H*W must stay below 2^31");
+  if (!smd::feat_recon_sizes_ok(b, n, C, H, W, hf, wf)) return fail(SMD_E_INVALID, "sizes that are not served b=%d n=%d C=%d H=%d W=%d hf=%d wf=%d (n <= %d, H, W <= 2048, n*b*C*hf*wf*4 < 2^32)", b, n, C, H, W, hf, wf, SMD_MAX_SUPPORTS);
+  if ((flags & ~kFeatReconFlags) || ((flags & SMD_LOSS_L1) != 0) == ((flags & SMD_LOSS_L2) != 0)) return fail(SMD_E_INVALID, "invalid flags 0x%x (one of SMD_LOSS_L1, SMD_LOSS_L2)", flags);
+  if ((uintptr_t)workspace % 8) return fail(SMD_E_INVALID, "the workspace needs 8-byte alignment");
+  if (workspace_bytes < smd_feat_recon_workspace_bytes(b, n, C, H, W, hf, wf)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return SMD_OK;
+}
+size_t smd_feat_recon_workspace_bytes(int b, int n, int C, int H, int W, int hf, int wf) {
+  if (!smd::feat_recon_sizes_ok(b, n, C, H, W, hf, wf)) return 0;
+  return feat_recon_part_bytes(b, H, W) + align256((size_t)n*smd::feat_recon_blocks(b, H, W)*smd::kPoseSums*sizeof(float)) + 16;
+}
+int smd_feat_recon_fwd(const float* depth, const float* feat, const float* supp_feat, const float* T, const float* K, const float* K_inv, const float* noise,
+                       uint64_t seed, float* loss, uint8_t* sel, float* warp, void* workspace, size_t workspace_bytes, int b, int n, int C, int H, int W,
+                       int hf, int wf, int flags, void* stream) {
+  if (!depth || !feat || !supp_feat || !T || !K || !K_inv || !loss || !sel || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (int rc = feat_recon_check(b, n, C, H, W, hf, wf, flags, workspace, workspace_bytes)) return rc;
+  return check_launch(smd::launch_feat_recon_fwd(depth, feat, supp_feat, T, K, K_inv, noise, seed, loss, sel, warp, (double*)workspace, b, n, C, H, W, hf, wf, flags,
+                                                 (hipStream_t)stream), "feat_recon_fwd");
+}
+int smd_feat_recon_bwd(const float* depth, const float* feat, const float* supp_feat, const float* T, const float* K, const float* K_inv, const uint8_t* sel,
+                       const float* g_loss, float* g_depth, float* g_T, void* workspace, size_t workspace_bytes, int b, int n, int C, int H, int W, int hf, int wf,
+                       int flags, void* stream) {
+  if (!depth || !feat || !supp_feat || !T || !K || !K_inv || !sel || !g_loss || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (!g_depth && !g_T) return fail(SMD_E_INVALID, "nothing to compute: neither g_depth nor g_T is asked for");
+  if (int rc = feat_recon_check(b, n, C, H, W, hf, wf, flags, workspace, workspace_bytes)) return rc;
+  return check_launch(smd::launch_feat_recon_bwd(depth, feat, supp_feat, T, K, K_inv, sel, g_loss, g_depth, g_T, feat_recon_pose_partial(workspace, b, H, W), b, n, C, H, W,
+                                                 hf, wf, flags, (hipStream_t)stream), "feat_recon_bwd");
+}
+
+// ------------------------------------------------------------------------------------------------
 // Depthwise 7x7 convolution (ConvNeXt)
 static bool dw_sizes_ok(int N, int C, int H, int W) {
   return N >= 1 && C >= 1 && H >= 1 && W >= 1 && (long long)N*C*smd::dwconv_tiles(H, W) < (1ll << 31) && (long long)H*W < (1ll << 30);

@@ -409,6 +409,16 @@ hipError_t launch_hints_regr_fwd(const float* depth, const float* hints, const f
                                  uint32_t* bits, float* stats, double* ws, hipStream_t st);
 hipError_t launch_hints_regr_bwd(const float* depth, const float* hints, const uint32_t* bits, int S, size_t P, int flags, int vec, const float* stats,
                                  const float* g_loss, float* g_depth, hipStream_t st);
+// smd_featrecon.hip: the feature-metric reconstruction loss from the low-resolution features (blocks of 64 columns x 4 rows of one sample); part: one double per
+// block; pose_partial: [n*b][blocks per sample][kPoseSums] floats, 16-byte aligned (launch_pose_finalize reads it)
+bool feat_recon_sizes_ok(int b, int n, int C, int H, int W, int hf, int wf);
+int feat_recon_blocks(int b, int H, int W);
+hipError_t launch_feat_recon_fwd(const float* depth, const float* feat, const float* supp, const float* T, const float* K, const float* Kinv, const float* noise,
+                                 uint64_t seed, float* loss, uint8_t* sel, float* warp, double* part, int b, int n, int C, int H, int W, int hf, int wf, int flags,
+                                 hipStream_t st);
+hipError_t launch_feat_recon_bwd(const float* depth, const float* feat, const float* supp, const float* T, const float* K, const float* Kinv, const uint8_t* sel,
+                                 const float* g_loss, float* g_depth, float* g_T, float* pose_partial, int b, int n, int C, int H, int W, int hf, int wf, int flags,
+                                 hipStream_t st);
 int regr_blocks(size_t N);
 hipError_t launch_regression_fwd(const float* pred, const float* target, const uint8_t* mask, size_t N, int flags, float* loss, float* err,
                                  float* stats, float* ws, hipStream_t st);

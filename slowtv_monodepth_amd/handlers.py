@@ -6,7 +6,8 @@ tensors to one fused HIP forward (and, through autograd, one fused backward).
 
 The other ViewSynth users (`feat_recon`, `autoenc_recon`, `stereo_const`, `depth_regr`) keep the
 reference's structure and run on the un-fused HIP operators (`view_synth`, `photo_error`, `recon_reduce`,
-`regression_loss`), which take any channel count.
+`regression_loss`), which take any channel count.  `feat_recon_fused` and `depth_regr_fused` are the fused forms the
+trainer's backend calls; each runs its plain handler for what its kernel does not serve.
 """
 from __future__ import annotations
 
@@ -16,7 +17,7 @@ import torch
 
 from . import functional as F
 
-__all__ = ['image_recon', 'disp_smooth', 'disp_mask', 'disp_occ', 'feat_recon', 'autoenc_recon', 'stereo_const', 'depth_regr', 'depth_regr_fused', 'feat_smooth', 'feat_smooth_pair',
+__all__ = ['image_recon', 'disp_smooth', 'disp_mask', 'disp_occ', 'feat_recon', 'feat_recon_fused', 'autoenc_recon', 'stereo_const', 'depth_regr', 'depth_regr_fused', 'feat_smooth', 'feat_smooth_pair',
            'ScaleDict', 'LazyDepths']
 
 
@@ -139,6 +140,15 @@ def feat_recon(crit, synth, depths: dict, masks, feats, supp_feats, Ts: torch.Te
                                                      align_corners=False).unflatten(0, (n, -1))
     loss, ld = image_recon(crit, synth, {0: depths[0]}, ({0: masks[0]} if masks is not None else None), feats, supp_feats, Ts, Ks, noise=noise, want_warp=True)
     return loss, {'supp_feats_warp': ld['supp_imgs_warp']}
+
+
+def feat_recon_fused(crit, synth, depths: dict, masks, feats, supp_feats, Ts: torch.Tensor, Ks: torch.Tensor, *, noise=None, want_warp: bool = True):
+    """`feat_recon` (same arguments, same return value; `supp_feats_warp` only with `want_warp`) from the LOW-resolution features: one kernel up-samples, warps,
+    forms the l1 / l2 error and reduces over the supports per pixel (`smd_feat_recon_*`, featrecon.py), and one sweep gives the gradients of the depth and the
+    poses.  CPU tensors, a predictive mask or a criterion with `mask_name`, `loss_name='ssim'`, intrinsics that require a gradient, features larger than the
+    depth map and subclasses of `ReconstructionLoss` run `feat_recon`."""
+    from .featrecon import feat_recon_fused as fused
+    return fused(crit, synth, depths, masks, feats, supp_feats, Ts, Ks, noise=noise, want_warp=want_warp)
 
 
 def autoenc_recon(crit, preds: dict, targets: torch.Tensor, supp_preds: dict, supp_targets: torch.Tensor):

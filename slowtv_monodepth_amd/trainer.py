@@ -57,6 +57,13 @@ class HipLossBackend:
         from . import handlers
         return handlers.depth_regr_fused(crit, synth, photo, depths, targets.float(), imgs, supp_imgs, Ts.detach().float(), Ks.detach().float())
 
+    def feat_recon(self, crit, synth, depths, masks, feats, supp_feats, Ts, Ks):
+        """Feature-metric reconstruction on the fused operator (`handlers.feat_recon_fused`; what it does not serve runs `handlers.feat_recon`).  The warped
+        features are written only for the image logger: `log_images` is set on the backend by the module that owns it (`trainer.log_images`); a backend used
+        on its own returns them, as the plain handler does."""
+        from . import handlers
+        return handlers.feat_recon_fused(crit, synth, depths, masks, feats, supp_feats, Ts.float(), Ks.float(), want_warp=getattr(self, 'log_images', True))
+
     def image_recon(self, crit, synth, depths, masks, imgs, supp_imgs, Ts, Ks, want_warp=True, K_inv=None, prepared=None):
         from . import handlers
         self.last_sel, self.last_path = None, 'handlers: image_recon + disp_smooth as separate autograd nodes'
@@ -211,6 +218,7 @@ class MonoDepthModule(nn.Module):
         self.amp_dtype = {'32': None, '32-true': None, 'bf16': torch.bfloat16, 'bf16-mixed': torch.bfloat16}.get(prec, None)
         self.channels_last = bool(tcfg.get('channels_last', False))
         self.want_aux = bool(tcfg.get('log_images', False))  # supp_imgs_warp etc. are only for the image logger
+        self.backend.log_images = self.want_aux              # (`HipLossBackend.feat_recon` takes no `want_warp`: other backends keep the handler's signature)
         self.overlap_nets = bool(tcfg.get('overlap_nets', True))   # pose network on a second HIP stream, concurrent with the depth network
         self._side_streams = {}
         self._prep_streams = {}
