@@ -419,6 +419,22 @@ int smd_conv7x7s2_fwd(const float* x, const void* wp, float* y, int B, int C, in
 int smd_conv7x7s2_bwd_weight(const float* x, const float* g_y, float* g_weight, void* workspace, size_t workspace_bytes,
                              int B, int C, int CO, int H, int W, void* stream);
 
+/* The ResNet encoders' 3x3 stride-2 transition convolutions (ABI 8; reference: `conv1 = nn.Conv2d(c, co, 3, 2, padding=1, bias=False)` of the first BasicBlock
+ * of layer2 / layer3 / layer4 of the timm ResNets built at src/networks/depth.py:95-98, src/networks/pose.py:39-41): y (B,CO,Ho,Wo) = conv2d(x (B,C,H,W),
+ * weight (CO,C,3,3), stride 2, padding 1), Ho = (H - 1)/2 + 1, Wo = (W - 1)/2 + 1 (odd H, W are legal), fp32 NCHW in and out, ZERO padding done inside the
+ * kernels, on the split-bf16 matrix-core form of smd_conv3x3_mfma_* (three pieces, six products: fp32-class results).  The forward reads the forward operand
+ * image of smd_conv3x3_mfma_pack(weight, wp_fwd, NULL, C, CO, 3, stream) (smd_conv3x3_mfma_packed_bytes(C, CO, 3) bytes: no pack of its own; part of
+ * every forward).  smd_conv3x3s2_mfma_bwd_weight leaves g_weight (CO,C,3,3) from x and g_y (B,CO,Ho,Wo) through per-block sums and the fixed-order fp64
+ * second stage (no atomic add, no zeroing pass).  No data gradient.  Both calls take a workspace of smd_conv3x3s2_mfma_workspace_bytes (the coarse levels'
+ * forward splits K over blocks and adds the splits' outputs in split order).  Served: C % 16 == 0 and CO % 32 == 0, any B, H, W >= 1 with one sample's x and
+ * one sample's y under 2 GiB each and B x ceil(C / 64) x ceil(CO / 64) < 65536; the query returns 0 for anything else and the calls SMD_E_UNSUPPORTED,
+ * nothing launched.  Deterministic. */
+size_t smd_conv3x3s2_mfma_workspace_bytes(int B, int C, int CO, int H, int W);
+int smd_conv3x3s2_mfma_fwd(const float* x, const void* wp_fwd, float* y, void* workspace, size_t workspace_bytes,
+                           int B, int C, int CO, int H, int W, void* stream);
+int smd_conv3x3s2_mfma_bwd_weight(const float* x, const float* g_y, float* g_weight, void* workspace, size_t workspace_bytes,
+                                  int B, int C, int CO, int H, int W, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Producer side of the path: training-mode BatchNorm2d of the ResNet encoders fused with the residual add and ReLU
  * that follow it (timm resnet blocks built at src/networks/depth.py:95-98, src/networks/pose.py:39-41;

@@ -1,5 +1,5 @@
 """The routed convolutions as `torch.autograd.Function`s: every operator (forward, data gradient, weight gradient) runs on the split-bf16 MFMA kernels
-(`smd_conv3x3_mfma_*`, `smd_conv3x3z_mfma_*`, `smd_conv7x7s2_*`) or on its reference, as `conv_routing.serve` decides.  `functional` re-exports the wrappers."""
+(`smd_conv3x3_mfma_*`, `smd_conv3x3z_mfma_*`, `smd_conv7x7s2_*`; the stride-2 3x3 layers: `conv_s2`) or on its reference, as `conv_routing.serve` decides.  `functional` re-exports the wrappers."""
 from __future__ import annotations
 
 from collections import namedtuple

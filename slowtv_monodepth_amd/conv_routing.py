@@ -1,7 +1,7 @@
 """Who serves a convolution operator, the split-bf16 MFMA kernels or the reference (MIOpen; for the thin last stage the f32-MFMA kernels): the decision only,
 no autograd, no launches of its own, testable without a GPU (`conv_ops` builds the operators on `serve`).  A same-box A/B decides the first time an (operator,
 shape) pair is seen: both run on the call's own tensors, interleaved, a few times each; the faster one is cached for the process.  `set_conv_route('mfma' |
-'miopen')` pins the choice; inside a HIP-graph capture nothing is timed and `STATIC_RULES` stands in.  Operator names: `<fwd | data | wgt>[_<family suffix>]`."""
+'miopen')` pins the choice; inside a HIP-graph capture nothing is timed and `STATIC_RULES` / `STRIDED_RULES` stand in.  Operator names: `<fwd | data | wgt>[_<family suffix>]`."""
 from __future__ import annotations
 
 import torch
@@ -55,10 +55,18 @@ _BOUNDS = {'px_min': lambda v, B, C, CO, h, w: B*h*w >= v,
            'coarse': lambda v, B, C, CO, h, w: (w <= _COARSE_W_MAX and C >= _COARSE_C_MIN) == v}
 
 
+# The strided 3x3 layers (`conv3x3_s2`; h x w the INPUT size), a table of their own: `STATIC_RULES` lists the stride-1 and stem families, each with the
+# operators its kernels have.  Suffix -> {operator: clauses}, the clauses as above.  profiles/s2_convs.txt (cfg 2, b = 12 / 24): the forward wins at all
+# three transition blocks (1.27-2.06 x, the smallest 5760 input pixels per channel); the weight gradient loses at all of them (0.30-0.44 x): MIOpen's.
+STRIDED_RULES = {
+    's2': {'fwd': [dict(px_min=5000)], 'wgt': []},
+}
+
+
 def static_rule(op, B, C, CO, h, w) -> bool:
-    """`STATIC_RULES` evaluated for one operator and shape."""
+    """`STATIC_RULES` (or, for a suffix it does not know, `STRIDED_RULES`) evaluated for one operator and shape."""
     kind, _, suffix = op.partition('_')
-    clauses = STATIC_RULES[_FAMILY_OF_SUFFIX[suffix]][kind]
+    clauses = STATIC_RULES[_FAMILY_OF_SUFFIX[suffix]][kind] if suffix in _FAMILY_OF_SUFFIX else STRIDED_RULES[suffix][kind]
     return any(all(_BOUNDS[name](v, B, C, CO, h, w) for name, v in clause.items()) for clause in clauses)
 
 

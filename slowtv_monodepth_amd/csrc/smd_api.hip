@@ -1017,6 +1017,32 @@ int smd_conv7x7s2_bwd_weight(const float* x, const float* g_y, float* g_weight, 
   if (workspace_bytes < smd_conv7x7s2_workspace_bytes(B, C, CO, H, W)) return fail(SMD_E_WORKSPACE, "workspace too small");
   return check_launch(smd::launch_conv_stem_bwd_wgt(x, g_y, g_weight, (float*)workspace, B, C, H, W, (hipStream_t)stream), "conv7x7s2_bwd_weight");
 }
+// the encoders' transition convolutions: conv2d(x (B,C,H,W), weight (CO,C,3,3), stride 2, padding 1) (smd_conv_s2.hip)
+static bool s2_sizes_ok(int B, int C, int CO, int H, int W) {     // grid dimensions below 65536; one sample's x and y under 2 GiB each, a plane's offsets in an int
+  if (B < 1 || B > 65535 || C < 1 || CO < 1 || C > 4096 || CO > 4096 || H < 1 || W < 1) return false;
+  const long long ho = (H - 1)/2 + 1, wo = (W - 1)/2 + 1;
+  return (long long)C*H*W < (1ll << 29) && (long long)CO*ho*wo < (1ll << 29) && ho <= 65535 && (long long)B*((C + 63)/64)*((CO + 63)/64) < 65536;
+}
+size_t smd_conv3x3s2_mfma_workspace_bytes(int B, int C, int CO, int H, int W) {
+  if (!smd::conv_s2_served(C, CO) || !s2_sizes_ok(B, C, CO, H, W)) return 0;
+  return align256(smd::conv_s2_workspace_floats(B, C, CO, H, W)*sizeof(float));
+}
+static int s2_check(size_t workspace_bytes, int B, int C, int CO, int H, int W) {
+  if (!smd::conv_s2_served(C, CO)) return fail(SMD_E_UNSUPPORTED, "the stride-2 kernels serve C %% 16 == 0 with CO %% 32 == 0, not C=%d CO=%d", C, CO);
+  if (!s2_sizes_ok(B, C, CO, H, W)) return fail(SMD_E_UNSUPPORTED, "the stride-2 kernels do not serve B=%d C=%d CO=%d H=%d W=%d", B, C, CO, H, W);
+  if (workspace_bytes < smd_conv3x3s2_mfma_workspace_bytes(B, C, CO, H, W)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return SMD_OK;
+}
+int smd_conv3x3s2_mfma_fwd(const float* x, const void* wp_fwd, float* y, void* workspace, size_t workspace_bytes, int B, int C, int CO, int H, int W, void* stream) {
+  if (!x || !wp_fwd || !y || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (int rc = s2_check(workspace_bytes, B, C, CO, H, W)) return rc;
+  return check_launch(smd::launch_conv_s2_fwd(x, wp_fwd, y, (float*)workspace, B, C, CO, H, W, (hipStream_t)stream), "conv3x3s2_mfma_fwd");
+}
+int smd_conv3x3s2_mfma_bwd_weight(const float* x, const float* g_y, float* g_weight, void* workspace, size_t workspace_bytes, int B, int C, int CO, int H, int W, void* stream) {
+  if (!x || !g_y || !g_weight || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (int rc = s2_check(workspace_bytes, B, C, CO, H, W)) return rc;
+  return check_launch(smd::launch_conv_s2_bwd_wgt(x, g_y, g_weight, (float*)workspace, B, C, CO, H, W, (hipStream_t)stream), "conv3x3s2_mfma_bwd_weight");
+}
 int smd_elu_up_cat_pad_fwd(const void* a, const float* bias, const void* skip, void* out, int B, int Ca, int Cs, int h, int w, int dtypes, void* stream) {
   if (!a || !out || (Cs > 0 && !skip)) return fail(SMD_E_INVALID, "null pointer");
   if (B < 1 || Ca < 1 || Cs < 0 || h < 1 || w < 1 || !dec_sizes_ok((long long)B*(Ca + Cs), 2*h, 2*w))

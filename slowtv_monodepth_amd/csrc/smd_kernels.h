@@ -311,6 +311,12 @@ size_t conv_stem_wgrad_floats(int B, int C, int H, int W);                    //
 hipError_t launch_conv_stem_pack(const float* w, void* wp, int C, hipStream_t st);
 hipError_t launch_conv_stem_fwd(const float* x, const void* wp, float* y, int B, int C, int H, int W, hipStream_t st);
 hipError_t launch_conv_stem_bwd_wgt(const float* x, const float* gy, float* g_w, float* partial, int B, int C, int H, int W, hipStream_t st);
+// smd_conv_s2.hip: the encoders' 3x3 stride-2 padding-1 convolutions (C % 16 == 0, CO % 32 == 0) on the split-bf16 matrix-core form, fp32 NCHW tensors; the
+// forward reads launch_conv_mfma_pack's forward image (pieces 3)
+bool conv_s2_served(int C, int CO);
+size_t conv_s2_workspace_floats(int B, int C, int CO, int H, int W);          // the forward's K-split partial outputs | the weight gradient's partial sets + fp64 slices
+hipError_t launch_conv_s2_fwd(const float* x, const void* wp_fwd, float* y, float* split_ws, int B, int C, int CO, int H, int W, hipStream_t st);
+hipError_t launch_conv_s2_bwd_wgt(const float* x, const float* gy, float* g_w, float* partial, int B, int C, int CO, int H, int W, hipStream_t st);
 size_t decoder_bias_partials(int B, int C, int h, int w);
 hipError_t launch_elu_pad_fwd(const void* x, const float* bias, void* out, int B, int C, int h, int w, int apply_elu, int dt, hipStream_t st);
 hipError_t launch_elu_pad_bwd(const void* x, const float* bias, const void* g_out, void* g_x, float* g_bias, float* ws, int B, int C, int h, int w,

@@ -12,6 +12,7 @@ from .ddv_ops import ddv_head
 from .fusion_ops import relu_pad, up_cat_gate_pad
 from .class_ops import _ScaleMean, crop_resize, lane_shift_selftest, photo_error, recon_reduce, regression_loss, scale_mean, upsample_stack, view_synth
 from .conv_ops import conv3x3_mfma, conv3x3_same, conv3x3_thin, conv3x3_wide, conv7x7s2_stem
+from .conv_s2 import conv3x3_s2
 from .conv_routing import _conv_route, conv_routes, set_conv_route
 from .geom_ops import intrinsics, inv_intrinsics, pose_matrices
 from .metric_ops import depth_metrics
