@@ -663,6 +663,53 @@ int smd_feat_recon_bwd(const float* depth, const float* feat, const float* supp_
                        int flags, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Offline evaluation (smd_eval.hip) — replaces the per-item body of `MonoDepthEvaluator.__call__` (src/core/evaluator.py:65-94) for a batch of b items.
+ *
+ * smd_eval_metrics: `upsample` + `to_inv` (evaluator.py:70, 169-173; src/tools/geometry.py:86-90), `get_mask` and the mask (evaluator.py:73-78, 175-181),
+ * `align` (evaluator.py:200-234), `scale` (evaluator.py:236-243), `metrics_eigen` (src/core/metrics.py:39-59) and `metrics_benchmark` (metrics.py:80-105).
+ *   disp (b,1,h,w) scaleless disparity; target (b,1,H,W); mask (b,1,H,W) uint8 or NULL (all ones).  The disparity is resized to (H,W) with ATen's
+ *   align_corners=False bilinear taps, or with SMD_EVAL_NEAREST source index floor(dst*in/out) (equality with cv2.resize is not claimed), and inverted:
+ *   pred = (d > 0)/max(d, eps).  A pixel is valid where target > min_depth, target < max_depth (only with max_depth > 0: 0 means "no maximum"),
+ *   crop_y0 <= y < crop_y1, crop_x0 <= x < crop_x1, mask != 0 and pred > 0.
+ *   align_mode: SMD_EVAL_ALIGN_FACTOR (scale = factor, shift = 0), SMD_EVAL_ALIGN_MEDIAN (scale = np.median(target)/np.median(pred) over the valid pixels in
+ *   float32, both middle values of an even count selected exactly), SMD_EVAL_ALIGN_LSQR (scale and shift of the least-squares fit in disparity space from
+ *   fp64 sums; a determinant <= 0 gives (0, 0)).  p = clip(scale*pred + shift, min_depth, max_depth), through to_inv on both sides for LSQR, in float32.
+ *   groups: SMD_EVAL_EIGEN | SMD_EVAL_BENCHMARK (at least one).
+ * -> values (b,20) fp64: Scale, Shift | AbsRel, SqRel, RMSE, LogRMSE, delta<1.05, <1.1, <1.25, <1.25^2, <1.25^3 (x100) | MAE, RMSE, InvMAE, InvRMSE, LogMAE,
+ *    LogRMSE, LogSI, AbsRel, SqRel; zeros for a group that was not asked for and for an item that is not scored;
+ *    counts (b) int32 valid pixels; status (b) int32: SMD_EVAL_SCORED, SMD_EVAL_EMPTY_MASK, SMD_EVAL_ZERO_PRED (the valid predictions sum to 0);
+ *    medians (b,2) fp32: np.median(pred), np.median(target) (MEDIAN on scored items, else 0);
+ *    optional (NULL: not written): depth (b,1,H,W) the aligned prediction at the valid pixels of scored items and 0 elsewhere; valid (b,1,H,W) uint8;
+ *    resized (b,1,H,W) the resized disparity.
+ * Integer atomics and fixed-order fp64 sums only: two calls give the same bits.  No synchronisation, no copy to the host; the workspace may be reused dirty.
+ * Pointers need only their element's alignment (the workspace: 8 bytes).  smd_eval_metrics_workspace_bytes returns 0 for sizes that are not served
+ * (b > 65535, H*W or h*w >= 2^31).
+ *
+ * smd_eval_pointcloud: `metrics_pointcloud` up to its last scalar formulas (metrics.py:111-165; `BackprojectDepth.forward`, geometry.py:304-316).
+ *   depth, target (b,1,H,W); mask (b,1,H,W) uint8; prefix (b,H*W) int32: the INCLUSIVE prefix sum of (mask != 0) per item in row-major order;
+ *   K_inv (b,4,4).  Both clouds are K_inv[:3,:3] (x, y, 1) * depth at the masked pixels, compacted in row-major order; every second point of each
+ *   (`[::2]`, metrics.py:128, 131) looks up its exact nearest neighbour in the other cloud by tiled brute force on the coordinate differences.
+ * -> nn (b,2,ceil(H*W/2)) fp32: the distances of the prediction's queries and of the target's (0 past the item's query count ceil(n/2));
+ *    stats (b,2,4) fp64: per direction the sum of the distances and the counts of distances < 0.05, < 0.1, < 0.2; counts (b) int32: n.
+ * The minimum is order-independent and the sums are added in a fixed order: two calls give the same bits.  Served: b*min(32, ceil(H*W/2048)) <= 65535. */
+#define SMD_EVAL_ALIGN_FACTOR 0
+#define SMD_EVAL_ALIGN_MEDIAN 1
+#define SMD_EVAL_ALIGN_LSQR 2
+#define SMD_EVAL_EIGEN 0x1
+#define SMD_EVAL_BENCHMARK 0x2
+#define SMD_EVAL_NEAREST 0x4
+#define SMD_EVAL_SCORED 0
+#define SMD_EVAL_EMPTY_MASK 1
+#define SMD_EVAL_ZERO_PRED 2
+size_t smd_eval_metrics_workspace_bytes(int b, int H, int W);
+int smd_eval_metrics(const float* disp, const float* target, const uint8_t* mask, int b, int h, int w, int H, int W, int crop_y0, int crop_y1, int crop_x0,
+                     int crop_x1, float min_depth, float max_depth, int align_mode, float factor, int flags, double* values, int* counts, int* status,
+                     float* medians, float* depth, uint8_t* valid, float* resized, void* workspace, size_t workspace_bytes, void* stream);
+size_t smd_eval_pointcloud_workspace_bytes(int b, int H, int W);
+int smd_eval_pointcloud(const float* depth, const float* target, const uint8_t* mask, const int* prefix, const float* K_inv, int b, int H, int W,
+                        float* nn, double* stats, int* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Pose / intrinsics prologue — one launch each instead of ~45 eager ATen launches.
  *
  * smd_pose_*: `T_from_AAt(aa, t)` (src/tools/geometry.py:181-209), followed by `T.inverse()` where invert[i] != 0

@@ -65,6 +65,10 @@ PROTOTYPES = {
     'smd_regression_bwd': (_i, [_vp]*3 + [_sz, _i] + [_vp]*5 + [_sz, _vp]),
     'smd_depth_metrics_workspace_bytes': (_sz, [_i]*3),
     'smd_depth_metrics': (_i, [_vp, _vp] + [_i]*5 + [_f, _f] + [_vp]*4 + [_sz, _vp]),
+    'smd_eval_metrics_workspace_bytes': (_sz, [_i]*3),
+    'smd_eval_metrics': (_i, [_vp]*3 + [_i]*9 + [_f, _f, _i, _f, _i] + [_vp]*8 + [_sz, _vp]),
+    'smd_eval_pointcloud_workspace_bytes': (_sz, [_i]*3),
+    'smd_eval_pointcloud': (_i, [_vp]*5 + [_i]*3 + [_vp]*4 + [_sz, _vp]),
     'smd_recon_reduce_workspace_bytes': (_sz, [_i, _i, _i]),
     'smd_recon_reduce_fwd': (_i, [_vp]*4 + [_u64] + [_vp]*4 + [_sz] + [_i]*5 + [_vp]),
     'smd_recon_reduce_bwd': (_i, [_vp]*7 + [_i]*5 + [_vp]),

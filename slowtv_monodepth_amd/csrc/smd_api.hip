@@ -738,6 +738,67 @@ int smd_depth_metrics(const float* pred, const float* target, int b, int h, int 
                                                 knob("metrics_store_pred", 1) != 0, (hipStream_t)stream), "depth_metrics");
 }
 
+// workspace of smd_eval_metrics: the radix histograms (zeroed by the call) | the blocks' alignment sums | their metric sums | (scale, shift) | the masked prediction
+static size_t eval_partial_bytes(int b, int H, int W, int sums) { return align256((size_t)b*smd::eval_blocks_per_item(b, H, W)*sums*sizeof(double)); }
+
+size_t smd_eval_metrics_workspace_bytes(int b, int H, int W) {
+  if (b < 1 || H < 1 || W < 1 || b > 65535 || (size_t)H*W >= ((size_t)1 << 31)) return 0;
+  return align256(smd::eval_hist_bytes(b)) + eval_partial_bytes(b, H, W, smd::kEvAlignSums) + eval_partial_bytes(b, H, W, smd::kEvSums) +
+         align256((size_t)b*2*sizeof(double)) + align256((size_t)b*H*W*sizeof(float));
+}
+
+int smd_eval_metrics(const float* disp, const float* target, const uint8_t* mask, int b, int h, int w, int H, int W, int crop_y0, int crop_y1, int crop_x0,
+                     int crop_x1, float min_depth, float max_depth, int align_mode, float factor, int flags, double* values, int* counts, int* status,
+                     float* medians, float* depth, uint8_t* valid, float* resized, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!disp || !target || !values || !counts || !status || !medians || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (b < 1 || h < 1 || w < 1 || H < 1 || W < 1 || b > 65535) return fail(SMD_E_INVALID, "invalid sizes b=%d h=%d w=%d H=%d W=%d", b, h, w, H, W);
+  if ((size_t)H*W >= ((size_t)1 << 31) || (size_t)h*w >= ((size_t)1 << 31)) return fail(SMD_E_INVALID, "h*w and H*W must stay below 2^31");
+  if (!(min_depth >= 0.f) || !(min_depth < INFINITY)) return fail(SMD_E_INVALID, "min_depth must be finite and not negative (%g): the selection orders bit patterns", min_depth);
+  if (!(max_depth >= 0.f) || (max_depth > 0.f && !(max_depth > min_depth))) return fail(SMD_E_INVALID, "max_depth must be 0 (none) or greater than min. (%g vs. %g)", max_depth, min_depth);
+  if (align_mode < SMD_EVAL_ALIGN_FACTOR || align_mode > SMD_EVAL_ALIGN_LSQR) return fail(SMD_E_INVALID, "unknown align_mode %d", align_mode);
+  if ((flags & ~(SMD_EVAL_EIGEN | SMD_EVAL_BENCHMARK | SMD_EVAL_NEAREST)) || !(flags & (SMD_EVAL_EIGEN | SMD_EVAL_BENCHMARK))) return fail(SMD_E_INVALID, "invalid flags 0x%x (at least one of SMD_EVAL_EIGEN, SMD_EVAL_BENCHMARK)", flags);
+  if ((uintptr_t)workspace % 8 || (uintptr_t)values % 8) return fail(SMD_E_INVALID, "the workspace and values need 8-byte alignment");
+  const size_t need = smd_eval_metrics_workspace_bytes(b, H, W);
+  if (workspace_bytes < need) return fail(SMD_E_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, need);
+  smd::EvalArgs a;
+  memset(&a, 0, sizeof(a));
+  a.disp = disp; a.target = target; a.mask = mask; a.b = b; a.h = h; a.w = w; a.H = H; a.W = W;
+  a.y0 = crop_y0; a.y1 = crop_y1; a.x0 = crop_x0; a.x1 = crop_x1;
+  a.lo = min_depth; a.hi = max_depth; a.has_hi = max_depth > 0.f; a.nearest = (flags & SMD_EVAL_NEAREST) != 0;
+  a.mode = align_mode; a.groups = flags & (SMD_EVAL_EIGEN | SMD_EVAL_BENCHMARK); a.factor = factor;
+  char* ws = (char*)workspace;
+  a.hist = (unsigned*)ws; ws += align256(smd::eval_hist_bytes(b));
+  a.partial0 = (double*)ws; ws += eval_partial_bytes(b, H, W, smd::kEvAlignSums);
+  a.partial1 = (double*)ws; ws += eval_partial_bytes(b, H, W, smd::kEvSums);
+  a.align = (double*)ws; ws += align256((size_t)b*2*sizeof(double));
+  a.pred = (float*)ws;
+  a.values = values; a.counts = counts; a.status = status; a.medians = medians; a.depth = depth; a.valid = valid; a.resized = resized;
+  return check_launch(smd::launch_eval_metrics(a, (hipStream_t)stream), "eval_metrics");
+}
+
+// workspace of smd_eval_pointcloud: both clouds as x | y | z arrays of H*W slots | the smallest squared distance per query and direction
+size_t smd_eval_pointcloud_workspace_bytes(int b, int H, int W) {
+  if (b < 1 || H < 1 || W < 1 || (size_t)H*W >= ((size_t)1 << 30)) return 0;
+  const size_t cap = (size_t)H*W;
+  if ((size_t)b*smd::pc_splits((int)cap) > 65535) return 0;
+  return align256(b*6*cap*sizeof(float)) + align256((size_t)b*2*((cap + 1)/2)*sizeof(unsigned));
+}
+
+int smd_eval_pointcloud(const float* depth, const float* target, const uint8_t* mask, const int* prefix, const float* K_inv, int b, int H, int W,
+                        float* nn, double* stats, int* counts, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!depth || !target || !mask || !prefix || !K_inv || !nn || !stats || !counts || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  const size_t need = smd_eval_pointcloud_workspace_bytes(b, H, W);
+  if (need == 0) return fail(SMD_E_INVALID, "sizes that are not served b=%d H=%d W=%d (H*W < 2^30, b*min(32, ceil(H*W/2048)) <= 65535)", b, H, W);
+  if ((uintptr_t)workspace % 4 || (uintptr_t)stats % 8) return fail(SMD_E_INVALID, "the workspace needs 4-byte and stats 8-byte alignment");
+  if (workspace_bytes < need) return fail(SMD_E_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, need);
+  smd::PcArgs a;
+  memset(&a, 0, sizeof(a));
+  a.depth = depth; a.target = target; a.mask = mask; a.cs = prefix; a.Kinv = K_inv; a.b = b; a.W = W; a.cap = H*W; a.nqcap = (a.cap + 1)/2;
+  a.pts = (float*)workspace; a.best = (unsigned*)((char*)workspace + align256((size_t)b*6*a.cap*sizeof(float)));
+  a.nn = nn; a.stats = stats; a.counts = counts;
+  return check_launch(smd::launch_eval_pointcloud(a, (hipStream_t)stream), "eval_pointcloud");
+}
+
 size_t smd_recon_reduce_workspace_bytes(int B, int h, int w) {
   if (B < 1 || h < 1 || w < 1) return 0;
   return align256((size_t)smd::ceil_div(B*h*w, 256)*sizeof(float));

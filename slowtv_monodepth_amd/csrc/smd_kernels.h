@@ -436,6 +436,46 @@ int metrics_blocks_per_sample(int b, int H, int W);
 size_t metrics_hist_bytes(int b);
 hipError_t launch_depth_metrics(const float* pred, const float* target, int b, int h, int w, int H, int W, float lo, float hi, float* values,
                                 float* medians, int* counts, unsigned* hist, double* partial, float* p0, bool store, hipStream_t st);
+// smd_eval.hip: offline evaluation.  The align-and-score operator's workspace is hist | partial0 | partial1 | align | pred; the point-cloud operator's pts | best.
+constexpr int kEvBlock = 256, kEvBins = 256, kEvAlignSums = 6, kEvSums = 15, kEvValues = 20;
+constexpr int kPcBlock = 256, kPcQ = 4, kPcTile = 256;    // queries per lane; database points per LDS tile (one per thread)
+struct EvalArgs {
+  const float* disp;        // (b,1,h,w)
+  const float* target;      // (b,1,H,W)
+  const uint8_t* mask;      // (b,1,H,W) or NULL
+  int b, h, w, H, W;
+  int y0, y1, x0, x1;       // the crop rectangle
+  float lo, hi;
+  bool has_hi, nearest;
+  int mode, groups;
+  float factor;
+  float sh, sw;             // h/H, w/W (set by the launcher)
+  int nbps;                 // blocks per item (set by the launcher)
+  unsigned* hist;           // [4 levels][b][4 selections][kEvBins]
+  double* partial0;         // [b][nbps][kEvAlignSums]
+  double* partial1;         // [b][nbps][kEvSums]
+  double* align;            // (b,2) scale, shift
+  float* pred;              // (b,H*W): the inverted prediction at the valid pixels, 0 elsewhere
+  double* values;           // (b,kEvValues) out
+  int* counts;              // (b) out
+  int* status;              // (b) out
+  float* medians;           // (b,2) out
+  float* depth;             // (b,H*W) out or NULL
+  uint8_t* valid;           // (b,H*W) out or NULL
+  float* resized;           // (b,H*W) out or NULL
+};
+struct PcArgs {
+  const float* depth; const float* target; const uint8_t* mask; const int* cs; const float* Kinv;
+  int b, W, cap, nqcap, nsplit;   // cap = H*W, nqcap = ceil(cap/2); nsplit is set by the launcher
+  float* pts;               // [b][2][3][cap]
+  unsigned* best;           // [b][2][nqcap]
+  float* nn; double* stats; int* counts;
+};
+int eval_blocks_per_item(int b, int H, int W);
+size_t eval_hist_bytes(int b);
+int pc_splits(int cap);
+hipError_t launch_eval_metrics(EvalArgs a, hipStream_t st);
+hipError_t launch_eval_pointcloud(PcArgs a, hipStream_t st);
 hipError_t launch_pose_fwd(const float* aa, const float* t, const uint8_t* invert, int N, float* T, hipStream_t st);
 hipError_t launch_pose_bwd(const float* aa, const float* t, const uint8_t* invert, int N, const float* g_T, float* g_aa, float* g_t, hipStream_t st);
 hipError_t launch_intrinsics_fwd(const float* fs, const float* cs, const float* Kin, int b, int h, int w, float* K, float* Kinv, hipStream_t st);
