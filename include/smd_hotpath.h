@@ -370,7 +370,9 @@ int smd_conv3x3_thin_bwd(const float* xp, const float* weight, const float* g_y,
  * bf16 matrix cores with every fp32 operand split exactly into `pieces` bf16 pieces (3: six bf16 products per fp32 product, what is dropped is below
  * 2^-25 of the product — fp32-class results at 6/16 of the f32 MFMA's time; 2: three products, 16 significant bits, an experiment setting, never the
  * library's choice).  smd_conv3x3_mfma_pack writes the weights' pieces in the operand order of the forward (wp_fwd) and of the data gradient (wp_bwd), each
- * smd_conv3x3_mfma_packed_bytes(C, CO, pieces) bytes (either may be NULL); the backward reads what the forward's pack left.
+ * smd_conv3x3_mfma_packed_bytes(C, CO, pieces) bytes (either may be NULL; the size counts C up to a multiple of 32: the data-gradient image is whole tiles of
+ * 32 input channels); the backward reads what the forward's pack left.  For the stride-2 data gradient (smd_conv3x3s2d_mfma_bwd_data below) the pack also
+ * writes wp_bwd where C % 16 == 0 with CO % 32 == 0 and pieces == 3; the rows past C of its last tile are not written and not used.
  * pieces = 1 (ABI 8): the tensors xp, y, g_y, g_xp are BFLOAT16 (the decoder under bf16 autocast, `cfg/kbr/default.yaml`): one bf16 product per product, the
  * weights enter as their bf16 rounding (what autocast hands a bf16 convolution), accumulation and the weight gradient stay fp32.
  * Served: pieces in {1, 2, 3}; forward C % 16 == 0 and CO % 32 == 0; data gradient CO % 16 == 0 and C % 32 == 0; weight gradient CO % 32 == 0 (any C); and the
@@ -425,7 +427,7 @@ int smd_conv7x7s2_bwd_weight(const float* x, const float* g_y, float* g_weight, 
  * kernels, on the split-bf16 matrix-core form of smd_conv3x3_mfma_* (three pieces, six products: fp32-class results).  The forward reads the forward operand
  * image of smd_conv3x3_mfma_pack(weight, wp_fwd, NULL, C, CO, 3, stream) (smd_conv3x3_mfma_packed_bytes(C, CO, 3) bytes: no pack of its own; part of
  * every forward).  smd_conv3x3s2_mfma_bwd_weight leaves g_weight (CO,C,3,3) from x and g_y (B,CO,Ho,Wo) through per-block sums and the fixed-order fp64
- * second stage (no atomic add, no zeroing pass).  No data gradient.  Both calls take a workspace of smd_conv3x3s2_mfma_workspace_bytes (the coarse levels'
+ * second stage (no atomic add, no zeroing pass).  The data gradient: smd_conv3x3s2d_* below.  Both calls take a workspace of smd_conv3x3s2_mfma_workspace_bytes (the coarse levels'
  * forward splits K over blocks and adds the splits' outputs in split order).  Served: C % 16 == 0 and CO % 32 == 0, any B, H, W >= 1 with one sample's x and
  * one sample's y under 2 GiB each and B x ceil(C / 64) x ceil(CO / 64) < 65536; the query returns 0 for anything else and the calls SMD_E_UNSUPPORTED,
  * nothing launched.  Deterministic. */
@@ -434,6 +436,16 @@ int smd_conv3x3s2_mfma_fwd(const float* x, const void* wp_fwd, float* y, void* w
                            int B, int C, int CO, int H, int W, void* stream);
 int smd_conv3x3s2_mfma_bwd_weight(const float* x, const float* g_y, float* g_weight, void* workspace, size_t workspace_bytes,
                                   int B, int C, int CO, int H, int W, void* stream);
+
+/* The data gradient of the same convolutions (ABI 8): g_x (B,C,H,W) from g_y (B,CO,Ho,Wo), the forward's padding and output size, any H, W >= 1.  By the
+ * parity of the input pixel it is four stride-1 convolutions over g_y with 1, 2, 2 and 4 taps (nine per 2 x 2 input cell, no zero insertion), on the same
+ * split-bf16 form.  wp_bwd is the data-gradient operand image of smd_conv3x3_mfma_pack(weight, wp_fwd or NULL, wp_bwd, C, CO, 3, stream)
+ * (smd_conv3x3_mfma_packed_bytes(C, CO, 3) bytes: no pack of its own).  The coarse levels split K over blocks and add the splits' partial gradients in split
+ * order, in a workspace of smd_conv3x3s2d_mfma_workspace_bytes (no atomic add, no zeroing pass).  Served, argument checks and error codes: as
+ * smd_conv3x3s2_mfma_* above; the query returns 0 for anything else.  Deterministic. */
+size_t smd_conv3x3s2d_mfma_workspace_bytes(int B, int C, int CO, int H, int W);
+int smd_conv3x3s2d_mfma_bwd_data(const float* g_y, const void* wp_bwd, float* g_x, void* workspace, size_t workspace_bytes,
+                                 int B, int C, int CO, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Producer side of the path: training-mode BatchNorm2d of the ResNet encoders fused with the residual add and ReLU

@@ -103,6 +103,8 @@ PROTOTYPES = {
     'smd_conv3x3s2_mfma_workspace_bytes': (_sz, [_i]*5),
     'smd_conv3x3s2_mfma_fwd': (_i, [_vp]*4 + [_sz] + [_i]*5 + [_vp]),
     'smd_conv3x3s2_mfma_bwd_weight': (_i, [_vp]*4 + [_sz] + [_i]*5 + [_vp]),
+    'smd_conv3x3s2d_mfma_workspace_bytes': (_sz, [_i]*5),
+    'smd_conv3x3s2d_mfma_bwd_data': (_i, [_vp]*4 + [_sz] + [_i]*5 + [_vp]),
     'smd_conv3x3_head_workspace_bytes': (_sz, [_i]*4),
     'smd_conv3x3_head_fwd': (_i, [_vp]*4 + [_i]*5 + [_vp]),
     'smd_conv3x3_head_bwd': (_i, [_vp]*8 + [_sz] + [_i]*5 + [_vp]),

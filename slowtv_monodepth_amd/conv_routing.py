@@ -1,7 +1,7 @@
 """Who serves a convolution operator, the split-bf16 MFMA kernels or the reference (MIOpen; for the thin last stage the f32-MFMA kernels): the decision only,
 no autograd, no launches of its own, testable without a GPU (`conv_ops` builds the operators on `serve`).  A same-box A/B decides the first time an (operator,
 shape) pair is seen: both run on the call's own tensors, interleaved, a few times each; the faster one is cached for the process.  `set_conv_route('mfma' |
-'miopen')` pins the choice; inside a HIP-graph capture nothing is timed and `STATIC_RULES` / `STRIDED_RULES` stand in.  Operator names: `<fwd | data | wgt>[_<family suffix>]`."""
+'miopen')` pins the choice; inside a HIP-graph capture nothing is timed and `STATIC_RULES` / `STRIDED_RULES` / `TRANSPOSED_RULES` stand in. Operator names: `<fwd | data | wgt>[_<family suffix>]`."""
 from __future__ import annotations
 
 import torch
@@ -63,11 +63,29 @@ STRIDED_RULES = {
 }
 
 
+# The data gradient of the strided 3x3 layers (a transposed convolution; h x w the layer's INPUT size, the gradient's own), a third table: the test of the
+# strided table pins its operators.  profiles/s2_data_convs.txt (cfg 2, b = 12 / 24): the clause is filled from what won there.
+TRANSPOSED_RULES = {
+    't2': {'data': [dict(px_min=5000)]},
+}
+
+
 def static_rule(op, B, C, CO, h, w) -> bool:
-    """`STATIC_RULES` (or, for a suffix it does not know, `STRIDED_RULES`) evaluated for one operator and shape."""
+    """`STATIC_RULES` (or, for a suffix it does not know, `STRIDED_RULES`, then `TRANSPOSED_RULES`) evaluated for one operator and shape."""
     kind, _, suffix = op.partition('_')
-    clauses = STATIC_RULES[_FAMILY_OF_SUFFIX[suffix]][kind] if suffix in _FAMILY_OF_SUFFIX else STRIDED_RULES[suffix][kind]
+    if suffix in _FAMILY_OF_SUFFIX: clauses = STATIC_RULES[_FAMILY_OF_SUFFIX[suffix]][kind]
+    elif suffix in STRIDED_RULES or suffix not in TRANSPOSED_RULES: clauses = STRIDED_RULES[suffix][kind]
+    else: clauses = TRANSPOSED_RULES[suffix][kind]
     return any(all(_BOUNDS[name](v, B, C, CO, h, w) for name, v in clause.items()) for clause in clauses)
+
+
+def may_serve(key, unknown=True) -> bool:
+    """What `_conv_route` would say of `key` = (op, B, C, CO, h, w) without timing anything: the pinned mode, the cached decision, the static rule under
+    capture; `unknown` where the shape's A/B has not been run yet."""
+    if _MODE != 'auto': return _MODE == 'mfma'
+    r = _ROUTES.get(key)
+    if r is None: return static_rule(*key) if torch.cuda.is_initialized() and _capturing() else unknown   # (no capture without an initialised device)
+    return r[0]
 
 
 # ---- the A/B and the dispatcher ---------------------------------------------------------------------------------------------------------------------

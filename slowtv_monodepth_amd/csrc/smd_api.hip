@@ -986,7 +986,7 @@ using smd::ConvOp;
 static bool conv_two_tiles() { return knob("conv_two_tiles", 0) != 0; }   // read ONCE per entry point: its size check and its launch get the same value
 size_t smd_conv3x3_mfma_packed_bytes(int C, int CO, int pieces) {
   if (C < 1 || CO < 1 || pieces < 1 || pieces > 3) return 0;
-  return align256(smd::conv_mfma_packed_elems(C, CO, pieces)*2);
+  return align256(smd::conv_mfma_packed_elems((C + 31) & ~31, CO, pieces)*2);   // (the data-gradient image: whole tiles of 32 input channels)
 }
 static size_t mfma_workspace_bytes(bool zpad, int B, int C, int CO, int h, int w, bool two_tiles) {   // one size for the three operators
   if (!mfma_sizes_ok(B, C, CO, h, w)) return 0;
@@ -1014,7 +1014,7 @@ int smd_conv3x3_mfma_pack(const float* weight, void* wp_fwd, void* wp_bwd, int C
   if (pieces < 1 || pieces > 3) return fail(SMD_E_UNSUPPORTED, "pieces must be 1 (bfloat16 tensors), 2 or 3 (float tensors), not %d", pieces);
   if (C < 1 || CO < 1 || C > 4096 || CO > 4096) return fail(SMD_E_INVALID, "invalid sizes C=%d CO=%d", C, CO);
   if (wp_fwd && !smd::conv_mfma_served(ConvOp::Fwd, false, C, CO)) return mfma_unserved(ConvOp::Fwd, false, C, CO);
-  if (wp_bwd && !smd::conv_mfma_served(ConvOp::Data, false, C, CO)) return mfma_unserved(ConvOp::Data, false, C, CO);
+  if (wp_bwd && !smd::conv_mfma_served(ConvOp::Data, false, C, CO) && !(pieces == 3 && smd::conv_s2_served(C, CO))) return mfma_unserved(ConvOp::Data, false, C, CO);   // (or the stride-2 data gradient's channel counts)
   return check_launch(smd::launch_conv_mfma_pack(weight, wp_fwd, wp_bwd, C, CO, pieces, (hipStream_t)stream), "conv3x3_mfma_pack");
 }
 // One body for the padded (smd_conv3x3_mfma_*) and zero-padded (smd_conv3x3z_mfma_*: unpadded x / g_x, fp32 only) forward (x -> y) and data gradient (g_y -> g_x)
@@ -1103,6 +1103,19 @@ int smd_conv3x3s2_mfma_bwd_weight(const float* x, const float* g_y, float* g_wei
   if (!x || !g_y || !g_weight || !workspace) return fail(SMD_E_INVALID, "null pointer");
   if (int rc = s2_check(workspace_bytes, B, C, CO, H, W)) return rc;
   return check_launch(smd::launch_conv_s2_bwd_wgt(x, g_y, g_weight, (float*)workspace, B, C, CO, H, W, (hipStream_t)stream), "conv3x3s2_mfma_bwd_weight");
+}
+// their data gradient: the same channel counts and sizes, and a grid that 32 bits hold
+static bool s2d_sizes_ok(int B, int C, int CO, int H, int W) { return s2_sizes_ok(B, C, CO, H, W) && smd::conv_s2d_blocks(B, C, CO, H, W) < (1ll << 31); }
+size_t smd_conv3x3s2d_mfma_workspace_bytes(int B, int C, int CO, int H, int W) {
+  if (!smd::conv_s2_served(C, CO) || !s2d_sizes_ok(B, C, CO, H, W)) return 0;
+  return align256(smd::conv_s2d_workspace_floats(B, C, CO, H, W)*sizeof(float));
+}
+int smd_conv3x3s2d_mfma_bwd_data(const float* g_y, const void* wp_bwd, float* g_x, void* workspace, size_t workspace_bytes, int B, int C, int CO, int H, int W, void* stream) {
+  if (!g_y || !wp_bwd || !g_x || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (!smd::conv_s2_served(C, CO)) return fail(SMD_E_UNSUPPORTED, "the stride-2 kernels serve C %% 16 == 0 with CO %% 32 == 0, not C=%d CO=%d", C, CO);
+  if (!s2d_sizes_ok(B, C, CO, H, W)) return fail(SMD_E_UNSUPPORTED, "the stride-2 kernels do not serve B=%d C=%d CO=%d H=%d W=%d", B, C, CO, H, W);
+  if (workspace_bytes < smd_conv3x3s2d_mfma_workspace_bytes(B, C, CO, H, W)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return check_launch(smd::launch_conv_s2_bwd_data(g_y, wp_bwd, g_x, (float*)workspace, B, C, CO, H, W, (hipStream_t)stream), "conv3x3s2d_mfma_bwd_data");
 }
 int smd_elu_up_cat_pad_fwd(const void* a, const float* bias, const void* skip, void* out, int B, int Ca, int Cs, int h, int w, int dtypes, void* stream) {
   if (!a || !out || (Cs > 0 && !skip)) return fail(SMD_E_INVALID, "null pointer");

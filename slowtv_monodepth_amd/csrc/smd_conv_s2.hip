@@ -1,7 +1,7 @@
 // smd_conv_s2.hip — the ResNet encoders' transition convolutions, conv2d(x (B,C,H,W), w (CO,C,3,3), stride 2, padding 1) (`conv1` of the first BasicBlock
-// of layer2 / layer3 / layer4), forward and weight gradient on the bf16 matrix cores with fp32-class results: every fp32 operand split exactly into three
+// of layer2 / layer3 / layer4), forward, data gradient and weight gradient on the bf16 matrix cores with fp32-class results: every fp32 operand split exactly into three
 // bf16 pieces, six `v_mfma_f32_32x32x16_bf16` per K step of 16 (the scheme: smd_conv_mfma.hip; the arithmetic: smd_split_dev.h; the shared stages:
-// smd_conv_mfma_dev.h).  Zero padding inside the kernels, NCHW fp32 in and out, any H, W >= 1: Ho = (H - 1)/2 + 1, Wo = (W - 1)/2 + 1.  No data gradient.
+// smd_conv_mfma_dev.h).  Zero padding inside the kernels, NCHW fp32 in and out, any H, W >= 1: Ho = (H - 1)/2 + 1, Wo = (W - 1)/2 + 1.
 // A file of its own: the stride-1 kernels of smd_conv_mfma.hip / smd_conv_wgrad.hip are not touched and compile to the instructions they had.
 //
 // Forward: the implicit GEMM of k_conv_mfma (M = 32 output channels, N = 32-pixel fragments, K = 16 channels x 9 taps; the weights are
@@ -26,6 +26,17 @@
 // dwords funnel-shifted by one element.  The next row's loads are requested before the row's MFMAs and filed after them.  Rows -1 and H, columns -1 and W,
 // channels past C / CO are filed as zeros.  Blocks leave partial sets [tap][co][c]; launch_partial_sets_finalize adds them in fp64 in a fixed order — no
 // atomic add, no zeroing pass.  A block may walk several samples (spb) into the same accumulators where the layer has more blocks than a generation needs.
+//
+// Data gradient: by the parity of the input pixel, four stride-1 convolutions over dL/dy with 1, 2, 2 and 4 taps — nine per 2 x 2 input CELL, no zero
+// insertion.  Input row 2 r meets tap ky = 1 at output row r; row 2 r + 1 meets ky = 0 at r + 1 and ky = 2 at r; columns alike.  An implicit GEMM with M = 32
+// input channels (A: smd_conv3x3_mfma_pack's data-gradient image, m = c, k = co, tap slot 8 - (3 ky + kx)), N = a fragment of 32 cells, K = 16 output channels
+// x the class's taps.  A block's tile is TR x TCW cells (<= 64, s2d_tile: 4 x 16 at 24 x 80, 6 x 10 at 12 x 40 and 6 x 20), its patch (TR + 1) x (TCW + 1)
+// pixels of dL/dy (<= 128: one staging trip, 24 KB for two patches), zero outside dL/dy: consecutive lanes read consecutive patch pixels at every tap, so
+// nothing is de-interleaved.  The four waves are two channel tiles x two cell fragments (a staged patch feeds four wave tiles; C = 64 has two channel
+// tiles); a wave keeps the four classes' accumulators of its fragment (4 x (hi + lo) x 16 registers) and runs the nine (tap, class) products of a chunk
+// grouped by the patch pixel they read, two classes interleaved.  A lane holds columns 2 c and 2 c + 1 of its rows: one 8-byte store each where W is even,
+// contiguous over the wave; the last odd row / column of an odd H / W does not exist and is not stored.  The coarse levels split K as the forward does
+// (k_s2_split_sum, split order: deterministic), but only under one block per CU: the partial gradients are four times the forward's partial outputs.
 #include "smd_common.h"
 #include "smd_kernels.h"
 #include "smd_conv_mfma_dev.h"
@@ -344,6 +355,176 @@ unsigned s2_wgrad_sets(int B, int C, int CO, int ho, int wo) {
   return grid.x*grid.y*(unsigned)ceil_div(B, spb);
 }
 
+// ---- data gradient ----
+constexpr int kS2DPix = 128;                                      // the largest patch: 2 x 64 (TR = 1, TCW = 63); one staging trip of 256 items
+
+// The nine (tap, class) products of a chunk in the order they run, grouped by the patch pixel they read: B00 = (r, c) serves steps 0 - 3, B01 = (r, c + 1)
+// steps 4 - 5, B10 = (r + 1, c) steps 6 - 7, B11 = (r + 1, c + 1) step 8.  Step -> the tap slot of the data-gradient image (slot 8 - (3 ky + kx) holds
+// w[co][c][ky][kx]) and the class 2 (y & 1) + (x & 1) whose accumulator it feeds:
+//   step        0      1      2      3      4      5      6      7      8
+//   (ky, kx)  (1,1)  (1,2)  (2,1)  (2,2)  (1,0)  (2,0)  (0,1)  (0,2)  (0,0)
+//   slot        4      3      1      0      5      2      7      6      8
+//   class       0      1      2      3      1      3      2      3      3
+__device__ __forceinline__ constexpr int s2d_slot(int s) { return (int)((0x867250134ull >> (4*s)) & 15); }
+
+// two tiles, each with operands of its own: product t of both before product t + 1 of either (split_mfma's order and accumulators)
+template <int P>
+__device__ __forceinline__ void split_mfma_two(const bf16x8 (&A0)[P], const bf16x8 (&B0)[P], f32x16& acc0, f32x16& lo0,
+                                               const bf16x8 (&A1)[P], const bf16x8 (&B1)[P], f32x16& acc1, f32x16& lo1) {
+  constexpr int NPROD = n_products(P);
+#pragma unroll
+  for (int t = 0; t < NPROD; ++t) {
+    if (t == NPROD - 1) { acc0 = mfma_bf16(A0[0], B0[0], acc0); acc1 = mfma_bf16(A1[0], B1[0], acc1); }
+    else {
+      lo0 = mfma_bf16(A0[prod_a(P, t)], B0[prod_b(P, t)], lo0);
+      lo1 = mfma_bf16(A1[prod_a(P, t)], B1[prod_b(P, t)], lo1);
+    }
+  }
+}
+
+template <int P>
+__global__ __launch_bounds__(256, 2) void k_conv_s2_bwd_data(const float* __restrict__ gy, const uint4* __restrict__ wp, float* __restrict__ out,
+                                                             int CK, int M, int H, int W, int ho, int wo, int TR, int TCW, int KS, int kc_per_split,
+                                                             size_t split_stride, unsigned gx, unsigned gyb, unsigned gz) {
+  constexpr int NPIX = kS2DPix, kBuf = P*NPIX*2;
+  __shared__ uint4 tile[2*kBuf];                                  // two patches, [piece][pixel][half]: 24 KB
+  const int lane = threadIdx.x & 63, wall = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), j = lane & 31, g = lane >> 5;
+  const int MT = (M + 31) >> 5, MG = (MT + 1) >> 1;               // tiles of 32 input channels; pairs of them
+  const unsigned nblk = (unsigned)(MG*KS)*gx*gyb*gz, lid = xcd_block_id(nblk);
+  if (lid >= nblk) return;
+  const int nf = wall & 1;                                        // the wave's fragment of 32 cells; its channel tile (past C: the last tile again, not stored)
+  const int mt_own = (int)(lid % MG)*2 + (wall >> 1), mt = min(mt_own, MT - 1), ks = (lid/MG) % KS;
+  const unsigned tl = lid/(MG*KS);
+  const int c0 = (int)(tl % gx)*TCW, r0 = (int)((tl/gx) % gyb)*TR, b = (int)(tl/(gx*gyb));
+  const int PW = TCW + 1, NP = (TR + 1)*PW;
+  const int KC = CK >> 4, kc0 = ks*kc_per_split, kc1 = min(KC, kc0 + kc_per_split);
+  const size_t plane = (size_t)ho*wo;
+  const float* src = gy + (size_t)b*CK*plane;
+
+  // this lane's cell: cell nf 32 + j of the tile in row-major order -> its patch pixel (r, c), or none
+  const int p = nf*32 + j, r = p/TCW, c = p - r*TCW;
+  const bool have = p < TR*TCW && r0 + r < ho && c0 + c < wo;
+  const int lbase = have ? r*PW + c : 0;
+
+  using Stage = PatchStager<256, NPIX, P, float, true>;
+  constexpr int TRIPS = Stage::TRIPS;
+  Stage stage;
+#pragma unroll
+  for (int t = 0; t < TRIPS; ++t) {                               // patch pixel (rp, q) = dL/dy pixel (r0 + rp, c0 + q); outside dL/dy or past the patch: zeros
+    const int item = Stage::item(t), half = item >= NPIX ? 1 : 0, pix = item - half*NPIX;
+    const int rp = pix/PW, q = pix - rp*PW;
+    const int yy = r0 + rp, xx = c0 + q;
+    stage.pofs[t] = (pix < NP && yy < ho && xx < wo) ? yy*wo + xx : -1;
+  }
+  float v[TRIPS][8];
+  auto request = [&](int kc) { stage.request(src, plane, kc, v); };
+
+  f32x16 acc[4], lo[4];                                           // per class 2 (y & 1) + (x & 1)
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int rr = 0; rr < 16; ++rr) { acc[q][rr] = 0.f; lo[q][rr] = 0.f; }
+
+  // weight fragments in five slots (step s in A[s % 5]), steps 0 - 3 of a chunk fetched during the chunk before; the patch's four fragments in two slots
+  bf16x8 A[5][P], Bf[2][P];
+  const uint4* wq = wp + ((size_t)mt*KC*9*P)*64 + lane;
+  auto fetch_a = [&](bf16x8 (&dst)[P], int kc, int s) {
+#pragma unroll
+    for (int pc = 0; pc < P; ++pc) dst[pc] = as_frag(wq[(size_t)((kc*9 + s2d_slot(s))*P + pc)*64]);
+  };
+  auto read_b = [&](bf16x8 (&dst)[P], int buf, int d) { Stage::read(tile, buf, lbase + d, g, dst); };
+  auto chunk = [&](int kc, int cur, auto more_tag) {
+    constexpr bool MORE = decltype(more_tag)::value;
+    read_b(Bf[0], cur, 0);
+    read_b(Bf[1], cur, 1);
+    split_mfma_two<P>(A[0], Bf[0], acc[0], lo[0], A[1], Bf[0], acc[1], lo[1]);              // steps 0, 1
+    fetch_a(A[4], kc, 4); fetch_a(A[0], kc, 5);
+    __builtin_amdgcn_sched_barrier(0);
+    split_mfma_two<P>(A[2], Bf[0], acc[2], lo[2], A[3], Bf[0], acc[3], lo[3]);              // steps 2, 3
+    fetch_a(A[1], kc, 6); fetch_a(A[2], kc, 7);
+    read_b(Bf[0], cur, PW);
+    if (MORE) request(kc + 1);
+    __builtin_amdgcn_sched_barrier(0);
+    split_mfma_two<P>(A[4], Bf[1], acc[1], lo[1], A[0], Bf[1], acc[3], lo[3]);              // steps 4, 5
+    fetch_a(A[3], kc, 8);
+    if (MORE) fetch_a(A[0], kc + 1, 0);
+    read_b(Bf[1], cur, PW + 1);
+    __builtin_amdgcn_sched_barrier(0);
+    split_mfma_two<P>(A[1], Bf[0], acc[2], lo[2], A[2], Bf[0], acc[3], lo[3]);              // steps 6, 7
+    if (MORE) { fetch_a(A[1], kc + 1, 1); fetch_a(A[2], kc + 1, 2); }
+    __builtin_amdgcn_sched_barrier(0);
+    split_mfma<P>(A[3], Bf[1], acc[3], lo[3]);                                              // step 8
+    if (MORE) {
+      fetch_a(A[3], kc + 1, 3);
+      stage.file(tile, cur ^ 1, v);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();                                              // the other patch is complete, and nobody reads this one any more
+  };
+
+  if (kc0 < kc1) {
+    request(kc0);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) fetch_a(A[s], kc0, s);
+    stage.file(tile, 0, v);
+  }
+  __syncthreads();
+  int kc = kc0;
+  for (; kc + 1 < kc1; ++kc) chunk(kc, (kc - kc0) & 1, std::true_type{});
+  if (kc < kc1) chunk(kc, (kc - kc0) & 1, std::false_type{});
+
+  if (mt_own >= MT || !have) return;
+  // the cell's 2 x 2 input pixels; a row's two as one 8-byte store where every such address is aligned (W even: then column 2 c + 1 exists, too)
+  float* dst = out + (size_t)ks*split_stride;                     // (KS > 1: `out` is the workspace the splits' sum reads)
+  const int y = 2*(r0 + r), x = 2*(c0 + c);
+  const bool row1 = y + 1 < H, col1 = x + 1 < W;
+  const bool pairs = (W & 1) == 0 && (reinterpret_cast<uintptr_t>(dst) & 7) == 0;
+#pragma unroll
+  for (int rr = 0; rr < 16; ++rr) {
+    const int m = mt*32 + mfma32_row(rr, g);
+    if (m >= M) continue;
+    float* q = dst + (((size_t)b*M + m)*H + y)*W + x;
+    const float v00 = acc[0][rr] + lo[0][rr], v01 = acc[1][rr] + lo[1][rr], v10 = acc[2][rr] + lo[2][rr], v11 = acc[3][rr] + lo[3][rr];
+    if (pairs) {
+      *reinterpret_cast<f32x2v*>(q) = f32x2v{v00, v01};
+      if (row1) *reinterpret_cast<f32x2v*>(q + W) = f32x2v{v10, v11};
+    } else {
+      q[0] = v00;
+      if (col1) q[1] = v01;
+      if (row1) { q[W] = v10; if (col1) q[W + 1] = v11; }
+    }
+  }
+}
+
+// The data gradient's tile: TR x TCW cells of 2 x 2 input pixels, TR TCW <= 64, the patch (TR + 1) x (TCW + 1) within kS2DPix: s2_tile's order of preference
+void s2d_tile(int ho, int wo, int& TR, int& TCW) {
+  double best = -1.0; int best_patch = 0;
+  TR = 1; TCW = 1;
+  for (int tcw = std::min(wo, 63); tcw >= 1; --tcw) {
+    int tr = std::min(64/tcw, ho);
+    while (tr > 1 && (tr + 1)*(tcw + 1) > kS2DPix) --tr;
+    const int patch = (tr + 1)*(tcw + 1);
+    const double useful = (double)ho*wo/((double)ceil_div(ho, tr)*ceil_div(wo, tcw)*64.0);
+    if (useful > best + 1e-9 || (useful > best - 1e-9 && patch < best_patch)) { best = useful; best_patch = patch; TR = tr; TCW = tcw; }
+  }
+}
+// Blocks of two channel tiles x two cell fragments.  The partial outputs of a K split are four times the forward's (H x W against ho x wo), so K is split
+// only under one block per CU: at least two chunks per split, about two blocks per CU
+S2Shape s2d_shape(int B, int C, int CO, int H, int W) {
+  const int ho = (H - 1)/2 + 1, wo = (W - 1)/2 + 1;
+  S2Shape s;
+  s2d_tile(ho, wo, s.TR, s.TCW);
+  s.gx = ceil_div(wo, s.TCW); s.gy = ceil_div(ho, s.TR); s.gz = B;
+  const int KC = CO >> 4, MG = ceil_div(ceil_div(C, 32), 2);
+  const long long base = (long long)s.gx*s.gy*s.gz*MG;
+  int ks = 1;
+  if (base < 256) ks = (int)std::min<long long>(std::max(KC/2, 1), (512 + base - 1)/base);
+  s.kcs = ceil_div(KC, ks); s.KS = ceil_div(KC, s.kcs);
+  s.grid = dim3(8*(unsigned)ceil_div(base*s.KS, 8ll));
+  s.out_elems = (size_t)B*C*H*W;
+  return s;
+}
+
 }  // namespace
 
 bool conv_s2_served(int C, int CO) { return C >= 16 && C % 16 == 0 && CO >= 32 && CO % 32 == 0; }
@@ -370,6 +551,24 @@ hipError_t launch_conv_s2_bwd_wgt(const float* x, const float* gy, float* g_w, f
   s2_wgrad_shape(B, C, CO, ho, wo, grid, rows, spb);
   hipLaunchKernelGGL(k_conv_s2_wgrad, grid, dim3(256), 0, st, x, gy, partial, B, C, CO, H, W, ho, wo, rows, spb);
   return launch_partial_sets_finalize(partial, grid.x*grid.y*(unsigned)ceil_div(B, spb), 9*CO*C, SetIndexMap{CO, C}, g_w, st);
+}
+
+// the data gradient: its blocks (the grid is 32-bit), its workspace (the K splits' partial gradients) and its launch
+long long conv_s2d_blocks(int B, int C, int CO, int H, int W) { return (long long)s2d_shape(B, C, CO, H, W).grid.x; }
+size_t conv_s2d_workspace_floats(int B, int C, int CO, int H, int W) {
+  const S2Shape s = s2d_shape(B, C, CO, H, W);
+  return std::max((size_t)64, s.KS > 1 ? (size_t)s.KS*s.out_elems : (size_t)0);
+}
+hipError_t launch_conv_s2_bwd_data(const float* gy, const void* wp_bwd, float* g_x, float* split_ws, int B, int C, int CO, int H, int W, hipStream_t st) {
+  const int ho = (H - 1)/2 + 1, wo = (W - 1)/2 + 1;
+  const S2Shape s = s2d_shape(B, C, CO, H, W);
+  hipLaunchKernelGGL(k_conv_s2_bwd_data<3>, s.grid, dim3(256), 0, st, gy, (const uint4*)wp_bwd, s.KS > 1 ? split_ws : g_x, CO, C, H, W, ho, wo, s.TR, s.TCW, s.KS,
+                     s.kcs, s.out_elems, s.gx, s.gy, s.gz);
+  if (s.KS > 1) {
+    const size_t n4 = s.out_elems/4;                              // (B C H W is a multiple of 4: C is a multiple of 16)
+    hipLaunchKernelGGL(k_s2_split_sum, dim3((unsigned)((n4 + 255)/256)), dim3(256), 0, st, split_ws, g_x, n4, s.KS);
+  }
+  return hipGetLastError();
 }
 
 }  // namespace smd

@@ -317,6 +317,10 @@ bool conv_s2_served(int C, int CO);
 size_t conv_s2_workspace_floats(int B, int C, int CO, int H, int W);          // the forward's K-split partial outputs | the weight gradient's partial sets + fp64 slices
 hipError_t launch_conv_s2_fwd(const float* x, const void* wp_fwd, float* y, float* split_ws, int B, int C, int CO, int H, int W, hipStream_t st);
 hipError_t launch_conv_s2_bwd_wgt(const float* x, const float* gy, float* g_w, float* partial, int B, int C, int CO, int H, int W, hipStream_t st);
+// the data gradient (same channel counts): reads launch_conv_mfma_pack's data-gradient image (pieces 3; C counted up to a multiple of 32)
+long long conv_s2d_blocks(int B, int C, int CO, int H, int W);                // the grid
+size_t conv_s2d_workspace_floats(int B, int C, int CO, int H, int W);         // the K splits' partial gradients
+hipError_t launch_conv_s2_bwd_data(const float* gy, const void* wp_bwd, float* g_x, float* split_ws, int B, int C, int CO, int H, int W, hipStream_t st);
 size_t decoder_bias_partials(int B, int C, int h, int w);
 hipError_t launch_elu_pad_fwd(const void* x, const float* bias, void* out, int B, int C, int h, int w, int apply_elu, int dt, hipStream_t st);
 hipError_t launch_elu_pad_bwd(const void* x, const float* bias, const void* g_out, void* g_x, float* g_bias, float* ws, int B, int C, int h, int w,
