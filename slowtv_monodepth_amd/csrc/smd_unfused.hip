@@ -162,7 +162,8 @@ __global__ __launch_bounds__(kUfBlock) void k_photo_error_fwd(const float* __res
       window_sums(x, y, h, w, v, u, sx, sxx, sxy, sy, syy);
       const float t = sx*sy, sx2 = sx*sx;
       const float num = fmaf(2.f, t, c1)*fmaf(2.f, fmaf(9.f, sxy, -t), c2);
-      const float den = (sx2 + fmaf(sy, sy, c1))*(fmaf(9.f, sxx, -sx2) + (fmaf(9.f, syy, c2) - sy*sy));
+      // (the target's variance first, C2 after: added to 9 syy, 81 C2 = 0.07 would take the rounding of a number of size 81 sy^2 into a constant window's whole denominator)
+      const float den = (sx2 + fmaf(sy, sy, c1))*(fmaf(9.f, sxx, -sx2) + (fmaf(9.f, syy, -sy*sy) + c2));
       es += fminf(fmaxf(fmaf(-0.5f, num/den, 0.5f), 0.f), 1.f);
     }
   }
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(kUfBlock) void k_photo_coef(const float* __restrict
     window_sums(x, y, h, w, v, u, sx, sxx, sxy, sy, syy);
     const float t = sx*sy, sx2 = sx*sx;
     const float a1 = fmaf(2.f, t, c1), a2 = fmaf(2.f, fmaf(9.f, sxy, -t), c2);
-    const float b1 = sx2 + fmaf(sy, sy, c1), b2 = fmaf(9.f, sxx, -sx2) + (fmaf(9.f, syy, c2) - sy*sy);
+    const float b1 = sx2 + fmaf(sy, sy, c1), b2 = fmaf(9.f, sxx, -sx2) + (fmaf(9.f, syy, -sy*sy) + c2);      // (as the forward orders it)
     const float rden = 1.f/(b1*b2), val = a1*a2*rden, e = fmaf(-0.5f, val, 0.5f);
     const float prd = ((e >= 0.f && e <= 1.f) ? -0.5f*g : 0.f)*rden;
     float* cp = coef + ((size_t)ni*3*C + c*3)*hw + pix;
