@@ -675,6 +675,37 @@ int smd_feat_recon_bwd(const float* depth, const float* feat, const float* supp_
                        int flags, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Image reconstruction loss with a predictive weighting mask (smd_maskrecon.hip) — replaces, for a criterion built with `mask_name`, `handlers.image_recon`
+ * (src/core/handlers.py:14-67) on the un-fused operators: the warp of every support at every scale (`ViewSynth.forward`, src/tools/geometry.py:366-391), the
+ * photometric error of the warps and of the un-warped supports (`PhotoError`, src/losses/photometric.py:54-88), `ReconstructionLoss.apply_mask` on the
+ * per-support errors (src/losses/reconstruction.py:46-57) and the reduction, automask and mean (src/losses/reconstruction.py:59-77, 79-96, 125), per tile of
+ * 32 x 8 pixels with its reflection halo in LDS, without the (n,S,b,3,h,w) warps and the two (n,S,b,h,w) error stacks.
+ *   depth (S,b,h,w) the up-sampled depth stack; mask (S,b,n,h,w) the up-sampled mask stack, one channel per support; tgt (b,3,h,w); supp (n,b,3,h,w);
+ *   T (n,b,4,4); K, K_inv (b,4,4); noise (S,b,h,w) or NULL: smd_recon_reduce_fwd's generator under `seed` (equal seeds draw equal noise).
+ *   flags: SMD_USE_MIN | SMD_USE_AUTOMASK | SMD_LOSS_L1 (else 0.85 SSIM + 0.15 L1) and exactly one of SMD_MASK_EXPLAINABILITY (err * mask) /
+ *   SMD_MASK_UNCERTAINTY (err * exp(-mask) + mask).
+ * Every statement is the un-fused operators' (smd_view_synth_fwd, smd_photo_error_fwd, smd_recon_reduce_fwd) in their order: `sel` and `warp0` are theirs bit
+ * for bit.  PhotoError pads the WARPED image by reflection: the halo at an image border is the warp of the mirrored pixel.
+ * Outputs: loss (1) = the mean of the reduced error; sel (S,b,h,w) uint8: the winning support (0 for the mean), SMD_SEL_MASKED where the static error won;
+ * stat (S,b,h,w) uint8: the support whose masked static error is the smallest — written, read by the backward and required only with SMD_USE_MIN and
+ * SMD_USE_AUTOMASK together (else it may be NULL); warp0 (n,b,3,h,w) or NULL: the warps of scale 0 for the image logger.
+ * Sizes served: 2 <= h, w <= 2048, 1 <= n <= SMD_MAX_SUPPORTS, 1 <= S <= SMD_MAX_SCALES, S*b <= 65535, S*b*h*w < 2^31; smd_mask_recon_workspace_bytes returns 0
+ * and the calls SMD_E_UNSUPPORTED (nothing launched) for anything else, other flags included.  One fp64 sum per block in the workspace, added by a one-block
+ * second stage in a fixed order: no atomics, two runs are bit-equal.
+ * Backward: ONE sweep that reads the decisions (`sel`, `stat`) and never re-decides: g_mask (S,b,n,h,w), every element written, the static branch included (it
+ * feeds the mask of the static winner, or of every support for the mean, as smd_recon_reduce_bwd does); g_depth (S,b,h,w) through the error's adjoint (the
+ * nine windows that contain a pixel, with the reflection fold) and the bilinear weights' derivatives; g_T (n,b,4,4) through per-block pose sums in the
+ * workspace and the fp64 finalize of smd_view_synth_bwd.  Any of the three may be NULL (not all): the launch then never forms its terms, and the others' bits
+ * do not change.  No gradient to the images, K or K_inv.  g_loss is a DEVICE scalar.  Pointers need only their element's alignment (the workspace: 8 bytes). */
+size_t smd_mask_recon_workspace_bytes(int S, int b, int n, int h, int w);
+int smd_mask_recon_fwd(const float* depth, const float* mask, const float* tgt, const float* supp, const float* T, const float* K, const float* K_inv,
+                       const float* noise, uint64_t seed, float* loss, uint8_t* sel, uint8_t* stat, float* warp0, void* workspace, size_t workspace_bytes,
+                       int S, int b, int n, int h, int w, int flags, void* stream);
+int smd_mask_recon_bwd(const float* depth, const float* mask, const float* tgt, const float* supp, const float* T, const float* K, const float* K_inv,
+                       const uint8_t* sel, const uint8_t* stat, const float* g_loss, float* g_depth, float* g_mask, float* g_T, void* workspace,
+                       size_t workspace_bytes, int S, int b, int n, int h, int w, int flags, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Offline evaluation (smd_eval.hip) — replaces the per-item body of `MonoDepthEvaluator.__call__` (src/core/evaluator.py:65-94) for a batch of b items.
  *
  * smd_eval_metrics: `upsample` + `to_inv` (evaluator.py:70, 169-173; src/tools/geometry.py:86-90), `get_mask` and the mask (evaluator.py:73-78, 175-181),

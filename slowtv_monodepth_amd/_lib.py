@@ -151,6 +151,9 @@ PROTOTYPES = {
     'smd_feat_recon_workspace_bytes': (_sz, [_i]*7),
     'smd_feat_recon_fwd': (_i, [_vp]*7 + [_u64] + [_vp]*4 + [_sz] + [_i]*8 + [_vp]),
     'smd_feat_recon_bwd': (_i, [_vp]*11 + [_sz] + [_i]*8 + [_vp]),
+    'smd_mask_recon_workspace_bytes': (_sz, [_i]*5),
+    'smd_mask_recon_fwd': (_i, [_vp]*8 + [_u64] + [_vp]*5 + [_sz] + [_i]*6 + [_vp]),
+    'smd_mask_recon_bwd': (_i, [_vp]*14 + [_sz] + [_i]*6 + [_vp]),
     'smd_pose_fwd': (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     'smd_pose_bwd': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     'smd_intrinsics_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

@@ -1471,6 +1471,48 @@ int smd_feat_recon_bwd(const float* depth, const float* feat, const float* supp_
 }
 
 // ------------------------------------------------------------------------------------------------
+// Image reconstruction loss with a predictive weighting mask (smd_maskrecon.hip).  Workspace: one double per block | the pose sums, 16-byte aligned inside it
+// whatever the base (the finalize reads them as 16-byte vectors).
+static const int kMaskReconFlags = SMD_LOSS_L1 | SMD_USE_MIN | SMD_USE_AUTOMASK | SMD_MASK_EXPLAINABILITY | SMD_MASK_UNCERTAINTY;
+static size_t mask_recon_part_bytes(int S, int b, int h, int w) { return align256((size_t)smd::mask_recon_tiles(h, w)*S*b*sizeof(double)); }
+static float* mask_recon_pose_partial(void* workspace, int S, int b, int h, int w) {
+  return (float*)(((uintptr_t)workspace + mask_recon_part_bytes(S, b, h, w) + 15) & ~(uintptr_t)15);
+}
+static int mask_recon_check(int S, int b, int n, int h, int w, int flags, const void* workspace, size_t workspace_bytes) {
+  if (!smd::mask_recon_sizes_ok(S, b, n, h, w))
+    return fail(SMD_E_UNSUPPORTED, "the masked reconstruction does not serve S=%d b=%d n=%d h=%d w=%d (S <= %d, n <= %d, 2 <= h, w <= 2048, S*b*h*w < 2^31)", S, b, n, h, w,
+                SMD_MAX_SCALES, SMD_MAX_SUPPORTS);
+  if ((flags & ~kMaskReconFlags) || ((flags & SMD_MASK_EXPLAINABILITY) != 0) == ((flags & SMD_MASK_UNCERTAINTY) != 0))
+    return fail(SMD_E_UNSUPPORTED, "the masked reconstruction does not serve flags 0x%x (exactly one of SMD_MASK_EXPLAINABILITY, SMD_MASK_UNCERTAINTY)", flags);
+  if ((uintptr_t)workspace % 8) return fail(SMD_E_INVALID, "the workspace needs 8-byte alignment");
+  if (workspace_bytes < smd_mask_recon_workspace_bytes(S, b, n, h, w)) return fail(SMD_E_WORKSPACE, "workspace too small");
+  return SMD_OK;
+}
+size_t smd_mask_recon_workspace_bytes(int S, int b, int n, int h, int w) {
+  if (!smd::mask_recon_sizes_ok(S, b, n, h, w)) return 0;
+  return mask_recon_part_bytes(S, b, h, w) + align256((size_t)n*b*S*smd::mask_recon_tiles(h, w)*smd::kPoseSums*sizeof(float)) + 16;
+}
+int smd_mask_recon_fwd(const float* depth, const float* mask, const float* tgt, const float* supp, const float* T, const float* K, const float* K_inv,
+                       const float* noise, uint64_t seed, float* loss, uint8_t* sel, uint8_t* stat, float* warp0, void* workspace, size_t workspace_bytes,
+                       int S, int b, int n, int h, int w, int flags, void* stream) {
+  if (!depth || !mask || !tgt || !supp || !T || !K || !K_inv || !loss || !sel || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (int rc = mask_recon_check(S, b, n, h, w, flags, workspace, workspace_bytes)) return rc;
+  if ((flags & SMD_USE_MIN) && (flags & SMD_USE_AUTOMASK) && !stat) return fail(SMD_E_INVALID, "min + automask: `stat` (the static winner) is an output");
+  return check_launch(smd::launch_mask_recon_fwd(depth, mask, tgt, supp, T, K, K_inv, noise, seed, loss, sel, stat, warp0, (double*)workspace, S, b, n, h, w, flags,
+                                                 (hipStream_t)stream), "mask_recon_fwd");
+}
+int smd_mask_recon_bwd(const float* depth, const float* mask, const float* tgt, const float* supp, const float* T, const float* K, const float* K_inv,
+                       const uint8_t* sel, const uint8_t* stat, const float* g_loss, float* g_depth, float* g_mask, float* g_T, void* workspace,
+                       size_t workspace_bytes, int S, int b, int n, int h, int w, int flags, void* stream) {
+  if (!depth || !mask || !tgt || !supp || !T || !K || !K_inv || !sel || !g_loss || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (!g_depth && !g_mask && !g_T) return fail(SMD_E_INVALID, "nothing to compute: none of g_depth, g_mask, g_T is asked for");
+  if (int rc = mask_recon_check(S, b, n, h, w, flags, workspace, workspace_bytes)) return rc;
+  if ((flags & SMD_USE_MIN) && (flags & SMD_USE_AUTOMASK) && !stat) return fail(SMD_E_INVALID, "min + automask: `stat` (the static winner) is an input");
+  return check_launch(smd::launch_mask_recon_bwd(depth, mask, tgt, supp, T, K, K_inv, sel, stat, g_loss, g_depth, g_mask, g_T,
+                                                 mask_recon_pose_partial(workspace, S, b, h, w), S, b, n, h, w, flags, (hipStream_t)stream), "mask_recon_bwd");
+}
+
+// ------------------------------------------------------------------------------------------------
 // Depthwise 7x7 convolution (ConvNeXt)
 static bool dw_sizes_ok(int N, int C, int H, int W) {
   return N >= 1 && C >= 1 && H >= 1 && W >= 1 && (long long)N*C*smd::dwconv_tiles(H, W) < (1ll << 31) && (long long)H*W < (1ll << 30);

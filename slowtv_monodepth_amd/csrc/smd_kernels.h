@@ -429,6 +429,16 @@ hipError_t launch_feat_recon_fwd(const float* depth, const float* feat, const fl
 hipError_t launch_feat_recon_bwd(const float* depth, const float* feat, const float* supp, const float* T, const float* K, const float* Kinv, const uint8_t* sel,
                                  const float* g_loss, float* g_depth, float* g_T, float* pose_partial, int b, int n, int C, int H, int W, int hf, int wf, int flags,
                                  hipStream_t st);
+// smd_maskrecon.hip: the image reconstruction loss with a predictive weighting mask (blocks of 32 x 8 pixels of one (scale, sample)); part: one double per block;
+// pose_partial: [n*b][S * tiles][kPoseSums] floats, 16-byte aligned (launch_pose_finalize reads it)
+bool mask_recon_sizes_ok(int S, int b, int n, int h, int w);
+int mask_recon_tiles(int h, int w);
+hipError_t launch_mask_recon_fwd(const float* depth, const float* mask, const float* tgt, const float* supp, const float* T, const float* K, const float* Kinv,
+                                 const float* noise, uint64_t seed, float* loss, uint8_t* sel, uint8_t* stat, float* warp0, double* part,
+                                 int S, int b, int n, int h, int w, int flags, hipStream_t st);
+hipError_t launch_mask_recon_bwd(const float* depth, const float* mask, const float* tgt, const float* supp, const float* T, const float* K, const float* Kinv,
+                                 const uint8_t* sel, const uint8_t* stat, const float* g_loss, float* g_depth, float* g_mask, float* g_T, float* pose_partial,
+                                 int S, int b, int n, int h, int w, int flags, hipStream_t st);
 int regr_blocks(size_t N);
 hipError_t launch_regression_fwd(const float* pred, const float* target, const uint8_t* mask, size_t N, int flags, float* loss, float* err,
                                  float* stats, float* ws, hipStream_t st);

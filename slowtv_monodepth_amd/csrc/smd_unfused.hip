@@ -7,23 +7,13 @@
 // gradients to the warped INPUT as feature reconstruction needs them).
 #include "smd_common.h"
 #include "smd_kernels.h"
+#include "smd_photo_dev.h"
 
 namespace smd {
 
 constexpr int kUfBlock = 256;
 
-struct PixGeom { float hx, hy, hz, nx, ny, yz, rz, sx, sy; };
-
-__device__ __forceinline__ PixGeom pix_geom(const Cam& cm, float D, float uf, float vf, float wscale, float hscale) {
-  PixGeom g;
-  g.hx = fmaf(cm.H[0], uf, fmaf(cm.H[1], vf, cm.H[2]));
-  g.hy = fmaf(cm.H[3], uf, fmaf(cm.H[4], vf, cm.H[5]));
-  g.hz = fmaf(cm.H[6], uf, fmaf(cm.H[7], vf, cm.H[8]));
-  g.nx = fmaf(D, g.hx, cm.a0); g.ny = fmaf(D, g.hy, cm.a1); g.yz = fmaf(D, g.hz, cm.tz);
-  g.rz = __builtin_amdgcn_rcpf(fmaxf(g.yz, kZMin));
-  g.sx = fmaf(g.nx*g.rz, wscale, -0.5f); g.sy = fmaf(g.ny*g.rz, hscale, -0.5f);
-  return g;
-}
+// (PixGeom / pix_geom, reflect1, the SSIM statements of a pixel and masked_err: smd_photo_dev.h, shared with smd_maskrecon.hip)
 
 // ---------------------------------------------------------------------------------------------
 // ViewSynth.forward (src/tools/geometry.py:366-391)
@@ -126,8 +116,6 @@ hipError_t launch_view_synth_bwd(const float* input, const float* depth, const f
 // ---------------------------------------------------------------------------------------------
 enum { kPhotoSsim = 0, kPhotoL1 = 1, kPhotoL2 = 2 };
 
-__device__ __forceinline__ int reflect1(int i, int n) { return i < 0 ? -i : (i >= n ? 2*(n - 1) - i : i); }
-
 // Nine-tap (reflection padded) un-normalised window sums of one channel at (v, u).
 __device__ __forceinline__ void window_sums(const float* __restrict__ x, const float* __restrict__ y, int h, int w, int v, int u,
                                             float& sx, float& sxx, float& sxy, float& sy, float& syy) {
@@ -138,8 +126,7 @@ __device__ __forceinline__ void window_sums(const float* __restrict__ x, const f
 #pragma unroll
     for (int du = -1; du <= 1; ++du) {
       const int idx = rv + reflect1(u + du, w);
-      const float a = x[idx], b = y[idx];
-      sx += a; sxx = fmaf(a, a, sxx); sxy = fmaf(a, b, sxy); sy += b; syy = fmaf(b, b, syy);
+      window_tap(x[idx], y[idx], sx, sxx, sxy, sy, syy);
     }
   }
 }
@@ -151,7 +138,6 @@ __global__ __launch_bounds__(kUfBlock) void k_photo_error_fwd(const float* __res
   if (pix >= h*w) return;
   const int v = pix/w, u = pix - v*w;
   const size_t hw = (size_t)h*w;
-  constexpr float c1 = 81.f*kC1, c2 = 81.f*kC2;
   float es = 0.f, el = 0.f, e2 = 0.f;
   for (int c = 0; c < C; ++c) {
     const float* x = pred + ((size_t)ni*C + c)*hw; const float* y = target + ((size_t)ni*C + c)*hw;
@@ -160,16 +146,12 @@ __global__ __launch_bounds__(kUfBlock) void k_photo_error_fwd(const float* __res
     if (mode == kPhotoSsim) {
       float sx, sxx, sxy, sy, syy;
       window_sums(x, y, h, w, v, u, sx, sxx, sxy, sy, syy);
-      const float t = sx*sy, sx2 = sx*sx;
-      const float num = fmaf(2.f, t, c1)*fmaf(2.f, fmaf(9.f, sxy, -t), c2);
-      // (the target's variance first, C2 after: added to 9 syy, 81 C2 = 0.07 would take the rounding of a number of size 81 sy^2 into a constant window's whole denominator)
-      const float den = (sx2 + fmaf(sy, sy, c1))*(fmaf(9.f, sxx, -sx2) + (fmaf(9.f, syy, -sy*sy) + c2));
-      es += fminf(fmaxf(fmaf(-0.5f, num/den, 0.5f), 0.f), 1.f);
+      es += ssim_win_err(sx, sxx, sxy, sy, syy);
     }
   }
   const float rc = 1.f/(float)C;
   // PhotoError(weight_ssim) (src/losses/photometric.py:85-86): weight_ssim * mean_c SSIM + (1 - weight_ssim) * mean_c |.|
-  err[(size_t)ni*hw + pix] = mode == kPhotoL2 ? sqrtf(fmaxf(e2, kEps32)) : (mode == kPhotoL1 ? el*rc : fmaf(w_ssim*rc, es, ((1.f - w_ssim)*rc)*el));
+  err[(size_t)ni*hw + pix] = mode == kPhotoL2 ? sqrtf(fmaxf(e2, kEps32)) : (mode == kPhotoL1 ? el*rc : photo_mix(es, el, rc, w_ssim));
 }
 
 static inline int photo_mode(int flags) { return (flags & SMD_LOSS_L2) ? kPhotoL2 : ((flags & SMD_LOSS_L1) ? kPhotoL1 : kPhotoSsim); }
@@ -189,21 +171,13 @@ __global__ __launch_bounds__(kUfBlock) void k_photo_coef(const float* __restrict
   if (pix >= h*w) return;
   const int v = pix/w, u = pix - v*w;
   const size_t hw = (size_t)h*w;
-  constexpr float c1 = 81.f*kC1, c2 = 81.f*kC2;
   const float g = g_err[(size_t)ni*hw + pix]*(w_ssim/(float)C);
   for (int c = 0; c < C; ++c) {
     const float* x = pred + ((size_t)ni*C + c)*hw; const float* y = target + ((size_t)ni*C + c)*hw;
     float sx, sxx, sxy, sy, syy;
     window_sums(x, y, h, w, v, u, sx, sxx, sxy, sy, syy);
-    const float t = sx*sy, sx2 = sx*sx;
-    const float a1 = fmaf(2.f, t, c1), a2 = fmaf(2.f, fmaf(9.f, sxy, -t), c2);
-    const float b1 = sx2 + fmaf(sy, sy, c1), b2 = fmaf(9.f, sxx, -sx2) + (fmaf(9.f, syy, -sy*sy) + c2);      // (as the forward orders it)
-    const float rden = 1.f/(b1*b2), val = a1*a2*rden, e = fmaf(-0.5f, val, 0.5f);
-    const float prd = ((e >= 0.f && e <= 1.f) ? -0.5f*g : 0.f)*rden;
     float* cp = coef + ((size_t)ni*3*C + c*3)*hw + pix;
-    cp[0] = prd*(2.f*sy*(a2 - a1) - 2.f*sx*val*(b2 - b1));
-    cp[hw] = prd*(-9.f*val*b1);
-    cp[2*hw] = prd*(18.f*a1);
+    ssim_win_coef(sx, sxx, sxy, sy, syy, g, cp[0], cp[hw], cp[2*hw]);
   }
 }
 
@@ -268,8 +242,7 @@ hipError_t launch_photo_error_bwd(const float* pred, const float* target, const 
 // Reduction half of ReconstructionLoss.forward (src/losses/reconstruction.py:43-44, 59-77, 125)
 // ---------------------------------------------------------------------------------------------
 // Predictive weighting masks of `ReconstructionLoss.apply_mask` (src/losses/reconstruction.py:46-57): mask (B,n,h,w) in the
-// reference's layout, one channel per support.  mode 1 'explainability': err * mask; mode 2 'uncertainty': err * exp(-mask) + mask.
-__device__ __forceinline__ float masked_err(float e, float m, int mode) { return mode == 1 ? e*m : (mode == 2 ? fmaf(e, __expf(-m), m) : e); }
+// reference's layout, one channel per support (`masked_err`, smd_photo_dev.h).
 
 __global__ __launch_bounds__(kUfBlock) void k_recon_reduce_fwd(const float* __restrict__ err_warp, const float* __restrict__ err_static,
                                                                const float* __restrict__ noise, uint32_t seed_lo, uint32_t seed_hi,

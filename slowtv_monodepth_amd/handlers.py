@@ -6,8 +6,9 @@ tensors to one fused HIP forward (and, through autograd, one fused backward).
 
 The other ViewSynth users (`feat_recon`, `autoenc_recon`, `stereo_const`, `depth_regr`) keep the
 reference's structure and run on the un-fused HIP operators (`view_synth`, `photo_error`, `recon_reduce`,
-`regression_loss`), which take any channel count.  `feat_recon_fused` and `depth_regr_fused` are the fused forms the
-trainer's backend calls; each runs its plain handler for what its kernel does not serve.
+`regression_loss`), which take any channel count.  `feat_recon_fused`, `depth_regr_fused` and `image_recon_masked_fused`
+(a criterion with a predictive mask) are the fused forms the trainer's backend calls; each runs its plain handler for what
+its kernel does not serve.
 """
 from __future__ import annotations
 
@@ -17,7 +18,7 @@ import torch
 
 from . import functional as F
 
-__all__ = ['image_recon', 'disp_smooth', 'disp_mask', 'disp_occ', 'feat_recon', 'feat_recon_fused', 'autoenc_recon', 'stereo_const', 'depth_regr', 'depth_regr_fused', 'feat_smooth', 'feat_smooth_pair',
+__all__ = ['image_recon', 'image_recon_masked_fused', 'disp_smooth', 'disp_mask', 'disp_occ', 'feat_recon', 'feat_recon_fused', 'autoenc_recon', 'stereo_const', 'depth_regr', 'depth_regr_fused', 'feat_smooth', 'feat_smooth_pair',
            'ScaleDict', 'LazyDepths']
 
 
@@ -95,6 +96,17 @@ def image_recon(crit, synth, depths: dict, masks, imgs: torch.Tensor, supp_imgs:
     if crit.use_automask: ld['automask'] = sel[0] != 255
     if want_warp: ld['supp_imgs_warp'] = warp0
     return loss, ld
+
+
+def image_recon_masked_fused(crit, synth, depths: dict, masks, imgs: torch.Tensor, supp_imgs: torch.Tensor, Ts: torch.Tensor, Ks: torch.Tensor,
+                             *, K_inv: torch.Tensor | None = None, noise: torch.Tensor | None = None, want_warp: bool = True, prepared=None):
+    """`image_recon` (same arguments, same return value) for a criterion built with `mask_name` and its up-sampled masks, without the (n, S*b, ...) expansions:
+    one kernel warps, forms the photometric errors of the warps and of the un-warped supports, applies the mask and reduces over the supports per tile
+    (`smd_mask_recon_*`, maskrecon.py), and one sweep gives the gradients of the depth, the mask and the poses.  CPU tensors, other dtypes, images that are not
+    3-channel, `loss_name='l2'`, a criterion without `mask_name` or no masks, subclasses of `ReconstructionLoss`, intrinsics that require a gradient, more than
+    eight supports or scales, frames beyond 2048 a side and masks of another size run `image_recon`."""
+    from .maskrecon import image_recon_masked_fused as fused
+    return fused(crit, synth, depths, masks, imgs, supp_imgs, Ts, Ks, K_inv=K_inv, noise=noise, want_warp=want_warp, prepared=prepared)
 
 
 def _expand_views(depths: dict, imgs, supp_imgs, Ts, Ks, K_inv):

@@ -67,6 +67,8 @@ class HipLossBackend:
     def image_recon(self, crit, synth, depths, masks, imgs, supp_imgs, Ts, Ks, want_warp=True, K_inv=None, prepared=None):
         from . import handlers
         self.last_sel, self.last_path = None, 'handlers: image_recon + disp_smooth as separate autograd nodes'
+        if masks is not None:   # predictive masks: the fused masked operator (what it does not serve runs `handlers.image_recon`)
+            return handlers.image_recon_masked_fused(crit, synth, depths, masks, imgs, supp_imgs, Ts.float(), Ks.float(), K_inv=K_inv, want_warp=want_warp, prepared=prepared)
         return handlers.image_recon(crit, synth, depths, masks, imgs, supp_imgs, Ts.float(), Ks.float(), K_inv=K_inv, want_warp=want_warp, prepared=prepared)
 
     def inv_intrinsics(self, K):
@@ -87,7 +89,7 @@ class HipLossBackend:
         networks instead of after them.  None when the fused operator will not be used for these tensors."""
         from . import functional as F
         if not imgs.is_cuda or imgs.shape[1] != 3 or crit.loss_name == 'l2' or imgs.dtype != torch.float32: return None
-        if getattr(crit, 'mask_name', None): return None   # a masked criterion takes the un-fused operators (handlers.image_recon): nothing would read the buffer
+        if getattr(crit, 'mask_name', None): return None   # a masked criterion takes `handlers.image_recon_masked_fused` or the un-fused operators: neither reads the buffer
         return F.image_recon_prep(imgs, supp_imgs, flags=F.recon_flags(crit.loss_name, crit.use_min, crit.use_automask), pyramid=pyramid, stream=stream,
                                   smooth_edges=smooth_edges)
 

@@ -1,0 +1,213 @@
+"""The fused masked image reconstruction (csrc/smd_maskrecon.hip, maskrecon.py, `handlers.image_recon_masked_fused`) on the host: the new C symbols in all four
+places and their refusals, every refusal of `served` one at a time, the fused handler's plain path on CPU tensors, the names' places, and
+`HipLossBackend.image_recon`'s choice of handler.  The kernel's own cases live in tests/test_gpu_maskrecon.py."""
+import inspect
+import re
+
+import pytest
+import torch
+
+from conftest import ROOT
+from oracle import view_synth_oracle as O
+
+NEW_SYMBOLS = ['smd_mask_recon_workspace_bytes', 'smd_mask_recon_fwd', 'smd_mask_recon_bwd']
+
+
+def test_the_new_symbols_are_declared_in_all_four_places():
+    from slowtv_monodepth_amd import _lib, functional
+    header = (ROOT/'include'/'smd_hotpath.h').read_text()
+    csrc = ROOT/'slowtv_monodepth_amd'/'csrc'
+    api, kernels = (csrc/'smd_api.hip').read_text(), (csrc/'smd_kernels.h').read_text()
+    for name in NEW_SYMBOLS:
+        assert re.search(r'\b(int|size_t)\s+' + name + r'\s*\(', header), f'{name} is not declared in the header'
+        assert re.search(r'\b(int|size_t)\s+' + name + r'\s*\(', api), f'{name} is not defined in smd_api.hip'
+        assert name in _lib.PROTOTYPES and hasattr(_lib.lib, name)
+    assert 'launch_mask_recon_fwd' in kernels and 'launch_mask_recon_bwd' in kernels
+    src = (csrc/'smd_maskrecon.hip').read_text()
+    for cite in ('handlers.py:14-67', 'reconstruction.py:46-57', '59-77, 79-96, 125', 'photometric.py:54-88', 'geometry.py:366-391'):
+        assert cite in src and cite in header, cite
+    assert _lib.lib.smd_abi_version() == 8
+    assert 'smd_maskrecon.hip' in (csrc/'Makefile').read_text()
+    assert 'atomic' not in src.split('namespace smd {', 1)[1].lower() and 'gauss_noise(' in src and 'launch_pose_finalize(' in src
+    assert '#include "smd_photo_dev.h"' in src and '#include "smd_photo_dev.h"' in (csrc/'smd_unfused.hip').read_text(), 'the per-element statements are shared, not copied'
+    assert not any('mask_recon' in n or 'masked_fused' in n for n in functional.__all__)
+
+
+FWD = ('depth', 'mask', 'tgt', 'supp', 'T', 'K', 'K_inv', 'noise', 'seed', 'loss', 'sel', 'stat', 'warp', 'ws', 'nbytes', 'S', 'b', 'n', 'h', 'w', 'flags', 'stream')
+BWD = ('depth', 'mask', 'tgt', 'supp', 'T', 'K', 'K_inv', 'sel', 'stat', 'g_loss', 'g_depth', 'g_mask', 'g_T', 'ws', 'nbytes', 'S', 'b', 'n', 'h', 'w', 'flags', 'stream')
+MIN_AUTO_UNCERT = 0x1 | 0x2 | 0x100
+
+
+def _call(name, order, **kw):
+    from slowtv_monodepth_amd import _lib
+    base = dict(depth=16, mask=16, tgt=16, supp=16, T=16, K=16, K_inv=16, noise=None, seed=0, loss=16, sel=16, stat=16, warp=None, ws=16, nbytes=1 << 22, S=2, b=2, n=2, h=24, w=40,
+                flags=MIN_AUTO_UNCERT, stream=None, g_loss=16, g_depth=16, g_mask=16, g_T=16)
+    base.update(kw)
+    return _lib.call(name, *[base[k] for k in order])
+
+
+def test_the_abi_refuses_bad_arguments_without_a_gpu():
+    """Every check runs before any launch: null pointers one by one, sizes and flags outside what is served (SMD_E_UNSUPPORTED), an undersized or misaligned
+    workspace, min + automask without `stat`, a backward nobody asked anything of."""
+    from slowtv_monodepth_amd import _lib
+    ws = _lib.lib.smd_mask_recon_workspace_bytes
+    tiles = 2*3
+    assert ws(2, 2, 2, 24, 40) >= 2*2*tiles*8 + 2*2*2*tiles*12*4 and ws(4, 12, 2, 192, 640) > 0 and ws(1, 1, 1, 2, 2) > 0 and ws(8, 1, 8, 2048, 2048) > 0
+    for bad in ((0, 2, 2, 24, 40), (2, 0, 2, 24, 40), (2, 2, 0, 24, 40), (2, 2, 2, 1, 40), (2, 2, 2, 24, 1), (9, 2, 2, 24, 40), (2, 2, 9, 24, 40), (1, 1, 1, 2049, 16),
+                (1, 1, 1, 16, 2049), (8, 64, 1, 2048, 2048), (8, 8192, 1, 8, 8)):
+        assert ws(*bad) == 0, bad
+    for name, order, ptrs in (('smd_mask_recon_fwd', FWD, ('depth', 'mask', 'tgt', 'supp', 'T', 'K', 'K_inv', 'loss', 'sel', 'ws')),
+                              ('smd_mask_recon_bwd', BWD, ('depth', 'mask', 'tgt', 'supp', 'T', 'K', 'K_inv', 'sel', 'g_loss', 'ws'))):
+        for p in ptrs:
+            with pytest.raises(ValueError, match='null pointer'): _call(name, order, **{p: None})
+        for bad in (dict(S=0), dict(b=0), dict(n=0), dict(h=1), dict(w=1), dict(n=9), dict(S=9), dict(h=4096), dict(flags=0x3), dict(flags=0x183), dict(flags=0x120)):
+            with pytest.raises(_lib.Unsupported): _call(name, order, **bad)
+        with pytest.raises(ValueError, match='alignment'): _call(name, order, ws=20)
+        with pytest.raises(ValueError, match='stat'): _call(name, order, stat=None)
+        with pytest.raises(_lib.HotpathError, match='workspace too small'): _call(name, order, nbytes=ws(2, 2, 2, 24, 40) - 1)
+    with pytest.raises(ValueError, match='nothing to compute'): _call('smd_mask_recon_bwd', BWD, g_depth=None, g_mask=None, g_T=None)
+
+
+def _operands(b=2, n=2, S=2, h=24, w=40, seed=3):
+    from slowtv_monodepth_amd.synthetic import make_batch
+    _, y, _ = make_batch(b, h, w, (-1, 1), seed=5)
+    g = torch.Generator().manual_seed(seed)
+    depths = {s: 0.5 + 5*torch.rand(b, 1, h, w, generator=g) for s in range(S)}
+    masks = {s: 0.2*torch.randn(b, n, h, w, generator=g) for s in range(S)}
+    Ts = torch.eye(4).repeat(n, b, 1, 1); Ts[..., :3, 3] = 0.05*torch.randn(n, b, 3, generator=g)
+    return dict(depths=depths, masks=masks, imgs=y['imgs'], supp_imgs=y['supp_imgs'], Ts=Ts, Ks=y['K']), torch.randn(S*b, 1, h, w, generator=g)
+
+
+def test_served_declines_each_condition_one_at_a_time(monkeypatch):
+    from slowtv_monodepth_amd import maskrecon
+    from slowtv_monodepth_amd.handlers import LazyDepths
+    from slowtv_monodepth_amd.losses import ReconstructionLoss
+    ok, _ = _operands()
+    b, n, S, h, w = 2, 2, 2, 24, 40
+    crit = ReconstructionLoss('ssim', use_min=True, use_automask=True, mask_name='uncertainty')
+    assert not maskrecon.served(crit, **ok), 'CPU tensors'
+    monkeypatch.setattr(torch.Tensor, 'is_cuda', property(lambda self: True))      # every tensor claims the GPU: only the rules decide
+    assert maskrecon.served(crit, **ok) and maskrecon.served(ReconstructionLoss('l1', mask_name='explainability'), **ok)
+    assert maskrecon.served(crit, **{**ok, 'Ts': ok['Ts'].clone().requires_grad_(True)}) and maskrecon.served(crit, **ok, K_inv=torch.linalg.inv(ok['Ks']))
+    lazy = LazyDepths(range(S), [torch.rand(b, 1, h >> s, w >> s) for s in range(S)], (h, w), 0.1, 100)
+    assert maskrecon.served(crit, **{**ok, 'depths': lazy}) and lazy.pending, 'a pending LazyDepths is asked for its size only'
+
+    class Sub(ReconstructionLoss): pass
+    declined = {
+        'dtype': {'imgs': ok['imgs'].double()},
+        'mask dtype': {'masks': {s: m.half() for s, m in ok['masks'].items()}},
+        'depth dtype': {'depths': {s: d.double() for s, d in ok['depths'].items()}},
+        'not 3-channel': {'imgs': ok['imgs'][:, :2], 'supp_imgs': ok['supp_imgs'][:, :, :2]},
+        'l2': {'crit': ReconstructionLoss('l2', mask_name='uncertainty')},
+        'no mask_name': {'crit': ReconstructionLoss('ssim', use_min=True)},
+        'no masks': {'masks': None},
+        'subclass': {'crit': Sub('ssim', mask_name='uncertainty')},
+        'learned K': {'Ks': ok['Ks'].clone().requires_grad_(True)},
+        'learned K_inv': {'K_inv': torch.linalg.inv(ok['Ks']).requires_grad_(True)},
+        'n beyond the limit': {'supp_imgs': ok['supp_imgs'][:1].expand(9, b, 3, h, w), 'Ts': torch.eye(4).expand(9, b, 4, 4),
+                               'masks': {s: torch.zeros(b, 9, h, w) for s in range(S)}},
+        'S beyond the limit': {'depths': {s: ok['depths'][0] for s in range(9)}, 'masks': {s: ok['masks'][0] for s in range(9)}},
+        'frame beyond 2048': {'imgs': torch.zeros(1, 3, 2049, 8), 'supp_imgs': torch.zeros(n, 1, 3, 2049, 8), 'Ts': ok['Ts'][:, :1], 'Ks': ok['Ks'][:1],
+                              'depths': {s: torch.zeros(1, 1, 2049, 8) for s in range(S)}, 'masks': {s: torch.zeros(1, n, 2049, 8) for s in range(S)}},
+        'mask of another size': {'masks': {0: ok['masks'][0], 1: ok['masks'][1][..., :12, :20]}},
+        'mask with one channel': {'masks': {s: m[:, :1] for s, m in ok['masks'].items()}},
+        'a scale without a mask': {'masks': {0: ok['masks'][0]}},
+        'depth of another size': {'depths': {0: ok['depths'][0], 1: ok['depths'][1][..., :12, :20]}},
+    }
+    for why, over in declined.items():
+        args = {'crit': crit, **ok, **over}
+        assert not maskrecon.served(**args), why
+
+
+def _oracle_generic(crit, depths, imgs, supp_imgs, Ts, Ks, K_inv, noise, want_warp, masks=None):
+    """`handlers._image_recon_generic` on the CPU oracle, masks included (the un-fused operators have no CPU implementation)."""
+    n, S, b = supp_imgs.shape[0], len(depths), imgs.shape[0]
+    dep = torch.stack(list(depths.values())).flatten(0, 1)
+    src = supp_imgs[:, None].expand(n, S, *supp_imgs.shape[1:]).flatten(1, 2)
+    tgt = imgs[None].expand(S, *imgs.shape).flatten(0, 1)
+    warp = O.view_synth(src.flatten(0, 1), dep[None].expand(n, *dep.shape).flatten(0, 1), Ts[:, None].expand(n, S, b, 4, 4).flatten(0, 2),
+                        Ks[None, None].expand(n, S, b, 4, 4).flatten(0, 2))[0].unflatten(0, (n, S*b))
+    loss, out = O.recon_loss(warp, tgt, source=src, loss_name=crit.loss_name, use_min=crit.use_min, use_automask=crit.use_automask, noise=noise,
+                             mask=torch.stack(list(masks.values())).flatten(0, 1), mask_name=crit.mask_name)
+    ld = {}
+    if crit.use_automask: ld['automask'] = out['automask'].unflatten(0, (S, b))[0]
+    if want_warp: ld['supp_imgs_warp'] = warp.unflatten(1, (S, b))[:, 0]
+    return loss, ld
+
+
+def test_fused_handler_on_the_cpu_is_the_plain_handler(monkeypatch):
+    from slowtv_monodepth_amd import handlers, maskrecon
+    from slowtv_monodepth_amd.losses import ReconstructionLoss
+    assert list(inspect.signature(handlers.image_recon_masked_fused).parameters) == list(inspect.signature(handlers.image_recon).parameters)
+    assert list(inspect.signature(maskrecon.image_recon_masked_fused).parameters) == list(inspect.signature(handlers.image_recon).parameters)
+    ok, noise = _operands()
+
+    def run(fn, **kw):
+        crit = ReconstructionLoss('ssim', use_min=True, use_automask=True, mask_name='uncertainty')
+        d = {s: v.clone().requires_grad_(True) for s, v in ok['depths'].items()}; m = {s: v.clone().requires_grad_(True) for s, v in ok['masks'].items()}
+        loss, ld = fn(crit, None, d, m, ok['imgs'], ok['supp_imgs'], ok['Ts'], ok['Ks'], noise=noise, **kw)
+        loss.backward()
+        return loss.detach(), ld, [v.grad for v in d.values()] + [v.grad for v in m.values()], crit.noise_seed
+    msgs = []
+    for fn in (handlers.image_recon, handlers.image_recon_masked_fused):      # the un-fused operators are GPU-only: both refuse, identically
+        with pytest.raises(RuntimeError, match='must live on the GPU') as e: run(fn)
+        msgs.append(str(e.value))
+    assert msgs[0] == msgs[1]
+    monkeypatch.setattr(handlers, '_image_recon_generic', _oracle_generic)
+    monkeypatch.setattr(maskrecon, 'mask_recon_loss', lambda *a, **k: pytest.fail('a declined call reached the kernel\'s operator'))
+    plain, fused = run(handlers.image_recon), run(handlers.image_recon_masked_fused, prepared=None)
+    assert torch.equal(plain[0], fused[0]) and list(plain[1]) == list(fused[1]) == ['automask', 'supp_imgs_warp'], 'CPU tensors: the plain handler\'s bits and keys'
+    assert all(torch.equal(plain[1][k], fused[1][k]) for k in plain[1]) and all(torch.equal(a, c) for a, c in zip(plain[2], fused[2]))
+    assert plain[3] == fused[3] == 0, 'a declined call draws no seed of its own'
+    assert list(run(handlers.image_recon_masked_fused, want_warp=False)[1]) == ['automask']
+
+
+def test_the_names_are_where_they_belong():
+    from slowtv_monodepth_amd import functional, handlers, maskrecon
+    assert 'image_recon_masked_fused' in handlers.__all__ and maskrecon.__all__ == ['mask_recon_loss', 'image_recon_masked_fused', 'served']
+    for name in ('mask_recon_loss', 'image_recon_masked_fused', 'served', '_MaskRecon'):
+        assert name not in functional.__all__ and not hasattr(functional, name)
+    assert issubclass(maskrecon._MaskRecon, torch.autograd.Function)
+    want = ['depth', 'mask', 'imgs', 'supp_imgs', 'Ts', 'K', 'K_inv', 'loss_name', 'use_min', 'use_automask', 'mask_name', 'noise', 'seed', 'want_warp']
+    assert list(inspect.signature(maskrecon.mask_recon_loss).parameters) == want
+    assert list(inspect.signature(maskrecon.served).parameters)[:7] == ['crit', 'depths', 'masks', 'imgs', 'supp_imgs', 'Ts', 'Ks']
+
+
+def test_operator_refuses_wrong_shapes_and_types_before_the_device():
+    from slowtv_monodepth_amd.maskrecon import mask_recon_loss
+    ok, noise = _operands()
+    good = dict(depth=torch.stack(list(ok['depths'].values())), mask=torch.stack(list(ok['masks'].values())), imgs=ok['imgs'], supp_imgs=ok['supp_imgs'], Ts=ok['Ts'], K=ok['Ks'])
+    kw = dict(loss_name='ssim', use_min=True, use_automask=True, mask_name='uncertainty')
+    run = lambda **over: mask_recon_loss(**{**good, **{k: v for k, v in over.items() if k in good}}, **{k: v for k, v in over.items() if k not in good}, **kw)
+    with pytest.raises(KeyError): mask_recon_loss(**good, **{**kw, 'loss_name': 'l2'})
+    with pytest.raises(ValueError, match='Invalid mask type'): mask_recon_loss(**good, **{**kw, 'mask_name': None})
+    with pytest.raises(TypeError, match='must be a Tensor'): run(mask=ok['masks'])
+    with pytest.raises(ValueError, match='depth: expected'): run(depth=good['depth'][0, :, 0])
+    with pytest.raises(ValueError, match='imgs: expected'): run(imgs=good['imgs'][:, :2])
+    with pytest.raises(ValueError, match='supp_imgs: expected'): run(supp_imgs=good['supp_imgs'][0])
+    with pytest.raises(ValueError, match='mask: expected'): run(mask=good['mask'][:, :, :1])
+    with pytest.raises(ValueError, match='Ts: expected'): run(Ts=good['Ts'][:1])
+    with pytest.raises(ValueError, match='K: expected'): run(K=good['K'][:, :3, :3])
+    with pytest.raises(ValueError, match='noise: expected'): run(noise=noise[:1])
+    with pytest.raises(TypeError, match='float32'): run(mask=good['mask'].double())
+    for k in ('imgs', 'supp_imgs', 'K'):
+        with pytest.raises(ValueError, match='must not require a gradient'): run(**{k: good[k].clone().requires_grad_(True)})
+    with pytest.raises(RuntimeError, match='must live on the GPU'): run(K_inv=torch.linalg.inv(good['K']), noise=noise)      # everything in order: the device is looked at last
+
+
+def test_backend_reaches_the_fused_handler_with_masks_and_not_otherwise(monkeypatch):
+    from slowtv_monodepth_amd import handlers
+    from slowtv_monodepth_amd.losses import ReconstructionLoss
+    from slowtv_monodepth_amd.trainer import HipLossBackend
+    seen = []
+    monkeypatch.setattr(handlers, 'image_recon_masked_fused', lambda *a, **k: seen.append(('fused', a, k)) or ('fused', {}))
+    monkeypatch.setattr(handlers, 'image_recon', lambda *a, **k: seen.append(('plain', a, k)) or ('plain', {}))
+    ok, _ = _operands()
+    be = HipLossBackend()
+    crit = ReconstructionLoss('ssim', mask_name='explainability')
+    assert be.image_recon(crit, None, ok['depths'], ok['masks'], ok['imgs'], ok['supp_imgs'], ok['Ts'].double(), ok['Ks'].double(), want_warp=False, prepared='p') == ('fused', {})
+    kind, a, k = seen[-1]
+    assert kind == 'fused' and a[3] is ok['masks'] and a[6].dtype == a[7].dtype == torch.float32 and k == {'K_inv': None, 'want_warp': False, 'prepared': 'p'}
+    assert be.image_recon(ReconstructionLoss('ssim'), None, ok['depths'], None, ok['imgs'], ok['supp_imgs'], ok['Ts'], ok['Ks']) == ('plain', {})
+    assert [s[0] for s in seen] == ['fused', 'plain'] and seen[-1][2]['want_warp'] is True
+    assert be.prepare_frames(crit, ok['imgs'], ok['supp_imgs'], None, None) is None, 'a masked criterion prepares no frames'
