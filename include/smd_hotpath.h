@@ -753,6 +753,40 @@ int smd_eval_pointcloud(const float* depth, const float* target, const uint8_t* 
                         float* nn, double* stats, int* counts, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Image logging (smd_viz.hip) — what the reference's HeavyLogger (src/core/heavy_logger.py:90-210) computes per image: `rgb_from_disp` and `rgb_from_feat`
+ * (src/tools/viz.py:20-74) and torchvision's `make_grid` (heavy_logger.py:35-42).  fp32 in and out; ABI 8 (symbols were added, none changed).
+ *
+ * smd_viz_disp: disp (b,1,h,w) -> rgb (b,3,h,w).  invert: `to_inv` first (src/tools/geometry.py:86-90; a NaN stays one).  select != 0: per item
+ *   vmax = np.percentile(d[d > 0], 95) as numpy evaluates it for a float32 array — the virtual index (n - 1)*float32(0.95) in float32, the two order
+ *   statistics around it selected exactly by a radix select over the bit patterns, numpy's `_lerp` between them with its `t >= 0.5` form — written to
+ *   vmax (b), and den (b) = (vmax - vmin) + 1e-5 in float32; an item without a positive value gets vmax = 0 (viz.py:13-16) and den = den0.  select == 0:
+ *   vmax and den are read (the caller's `vmax`).  Then `apply_cmap` (src/utils/misc.py:54-60) with matplotlib's `Colormap.__call__`, in float32 with IEEE
+ *   division: clip(vmin, vmax), (x - vmin)/den, * N, `== N -> N - 1`, truncation, lut (N,3) lookup, N <= 1024; below 0 takes entry 0, N and above entry
+ *   N - 1, a NaN (0, 0, 0).  Integer atomics on the histograms only, which the call zeroes: two calls give the same bits.
+ *
+ * smd_viz_feat_moments: feat (b,C,h,w) -> mean (C) fp64 and cov (C,C) fp64 = the sums over all b*h*w samples of the products of the centred channels
+ *   (NOT divided by n - 1), through per-block fp32 tiles (32 x 32 channel pairs x a chunk of samples; `v_mfma_f32_32x32x2_f32` for C >= 64) added in fp64 in
+ *   a fixed order.  The caller decomposes cov (the exact covariance route: sklearn's `covariance_eigh`; its randomized solver is not restated).
+ * smd_viz_feat_project: rgb (b,3,h,w) = (feat - mean) V with V (C,3), then `proj -= proj.min(0); proj /= proj.max(0)` (viz.py:69-70; the maximum of the
+ *   shifted values; 0/0 gives NaN as it does there).  Served: 3 <= C <= 1024, 3 <= b*h*w < 2^31 (else the query returns 0 and the calls SMD_E_INVALID).
+ *
+ * smd_make_grid: x (b,c,h,w), c = 1 or 3, float32 or (is_u8) uint8 / bool bytes -> grid (3,Hg,Wg) of the first n = min(b, n_imgs) images, `nrow` per row:
+ *   xmaps = min(nrow, n), ymaps = ceil(n/xmaps), Hg = (h + padding) ymaps + padding, Wg = (w + padding) xmaps + padding, image k at row
+ *   (k / xmaps)(h + padding) + padding and column (k % xmaps)(w + padding) + padding, pad_value elsewhere; n == 1 gives the image itself, (3,h,w).  One
+ *   channel is repeated three times.  normalize: lo, hi = the extrema of the n images, then clamp(lo, hi) and (x - lo)/max(hi - lo, 1e-5) (scale_each=False).
+ * Pointers need only their element's alignment (fp64 arrays and the feature workspace: 8 bytes). */
+size_t smd_viz_disp_workspace_bytes(int b, int h, int w);
+int smd_viz_disp(const float* disp, int b, int h, int w, int invert, int select, float vmin, float den0, const float* lut, int N, float* rgb, float* vmax,
+                 float* den, void* workspace, size_t workspace_bytes, void* stream);
+size_t smd_viz_feat_workspace_bytes(int b, int C, int h, int w);
+int smd_viz_feat_moments(const float* feat, int b, int C, int h, int w, double* mean, double* cov, void* workspace, size_t workspace_bytes, void* stream);
+int smd_viz_feat_project(const float* feat, const double* mean, const float* V, int b, int C, int h, int w, float* rgb, void* workspace, size_t workspace_bytes,
+                         void* stream);
+size_t smd_make_grid_workspace_bytes(void);
+int smd_make_grid(const void* x, int is_u8, int b, int c, int h, int w, int n_imgs, int nrow, int padding, float pad_value, int normalize, float* grid,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Pose / intrinsics prologue — one launch each instead of ~45 eager ATen launches.
  *
  * smd_pose_*: `T_from_AAt(aa, t)` (src/tools/geometry.py:181-209), followed by `T.inverse()` where invert[i] != 0

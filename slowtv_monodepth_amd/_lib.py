@@ -69,6 +69,13 @@ PROTOTYPES = {
     'smd_eval_metrics': (_i, [_vp]*3 + [_i]*9 + [_f, _f, _i, _f, _i] + [_vp]*8 + [_sz, _vp]),
     'smd_eval_pointcloud_workspace_bytes': (_sz, [_i]*3),
     'smd_eval_pointcloud': (_i, [_vp]*5 + [_i]*3 + [_vp]*4 + [_sz, _vp]),
+    'smd_viz_disp_workspace_bytes': (_sz, [_i]*3),
+    'smd_viz_disp': (_i, [_vp] + [_i]*5 + [_f, _f, _vp, _i] + [_vp]*4 + [_sz, _vp]),
+    'smd_viz_feat_workspace_bytes': (_sz, [_i]*4),
+    'smd_viz_feat_moments': (_i, [_vp] + [_i]*4 + [_vp]*3 + [_sz, _vp]),
+    'smd_viz_feat_project': (_i, [_vp]*3 + [_i]*4 + [_vp]*2 + [_sz, _vp]),
+    'smd_make_grid_workspace_bytes': (_sz, []),
+    'smd_make_grid': (_i, [_vp] + [_i]*8 + [_f, _i] + [_vp]*2 + [_sz, _vp]),
     'smd_recon_reduce_workspace_bytes': (_sz, [_i, _i, _i]),
     'smd_recon_reduce_fwd': (_i, [_vp]*4 + [_u64] + [_vp]*4 + [_sz] + [_i]*5 + [_vp]),
     'smd_recon_reduce_bwd': (_i, [_vp]*7 + [_i]*5 + [_vp]),

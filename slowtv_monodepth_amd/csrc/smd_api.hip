@@ -799,6 +799,101 @@ int smd_eval_pointcloud(const float* depth, const float* target, const uint8_t* 
   return check_launch(smd::launch_eval_pointcloud(a, (hipStream_t)stream), "eval_pointcloud");
 }
 
+// workspace of smd_viz_disp: the radix histograms (zeroed by the call)
+size_t smd_viz_disp_workspace_bytes(int b, int h, int w) {
+  if (b < 1 || h < 1 || w < 1 || b > 65535 || (size_t)h*w >= ((size_t)1 << 31)) return 0;
+  return align256(smd::viz_hist_bytes(b));
+}
+
+int smd_viz_disp(const float* disp, int b, int h, int w, int invert, int select, float vmin, float den0, const float* lut, int N, float* rgb, float* vmax,
+                 float* den, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!disp || !lut || !rgb || !vmax || !den || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (b < 1 || h < 1 || w < 1 || b > 65535 || (size_t)h*w >= ((size_t)1 << 31)) return fail(SMD_E_INVALID, "invalid sizes b=%d h=%d w=%d", b, h, w);
+  if (N < 1 || N > smd::kVzMaxLut) return fail(SMD_E_INVALID, "the table has %d entries (1 .. %d)", N, smd::kVzMaxLut);
+  if ((uintptr_t)workspace % 4) return fail(SMD_E_INVALID, "the workspace needs 4-byte alignment");
+  const size_t need = smd_viz_disp_workspace_bytes(b, h, w);
+  if (workspace_bytes < need) return fail(SMD_E_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, need);
+  smd::VizDispArgs a;
+  memset(&a, 0, sizeof(a));
+  a.disp = disp; a.b = b; a.hw = h*w; a.invert = invert != 0; a.select = select != 0; a.vmin = vmin; a.den0 = den0; a.lut = lut; a.N = N;
+  a.rgb = rgb; a.vmax = vmax; a.den = den; a.hist = (unsigned*)workspace;
+  return check_launch(smd::launch_viz_disp(a, (hipStream_t)stream), "viz_disp");
+}
+
+// workspace of smd_viz_feat_*: the mean's block sums | the fp32 means | the blocks' tiles | the projection's block extrema | the six extrema
+static bool viz_feat_args(smd::VizFeatArgs& a, int b, int C, int h, int w) {
+  if (b < 1 || C < 3 || C > smd::kVzMaxC || h < 1 || w < 1 || (size_t)b*h*w >= ((size_t)1 << 31) || (size_t)b*h*w < 3) return false;
+  memset(&a, 0, sizeof(a));
+  a.b = b; a.C = C; a.hw = h*w;
+  smd::viz_feat_plan(a);
+  return a.nchunk <= 65535;
+}
+static size_t viz_feat_carve(smd::VizFeatArgs& a, void* workspace) {
+  // offsets first (the size query passes no workspace), pointers only where there is one
+  size_t off = 0;
+  const size_t o_mean_part = off; off += align256((size_t)a.C*a.nsplit*sizeof(double));
+  const size_t o_meanf = off; off += align256((size_t)a.C*sizeof(float));
+  const size_t o_tile = off; off += align256((size_t)a.npairs*a.nchunk*smd::kVzTileElems*sizeof(float));
+  const size_t o_ext_part = off; off += align256((size_t)a.nblk*6*sizeof(float));
+  const size_t o_ext = off; off += 256;
+  if (workspace) {
+    char* ws = (char*)workspace;
+    a.mean_part = (double*)(ws + o_mean_part); a.meanf = (float*)(ws + o_meanf); a.tile_part = (float*)(ws + o_tile);
+    a.ext_part = (float*)(ws + o_ext_part); a.ext = (float*)(ws + o_ext);
+  }
+  return off;
+}
+
+size_t smd_viz_feat_workspace_bytes(int b, int C, int h, int w) {
+  smd::VizFeatArgs a;
+  if (!viz_feat_args(a, b, C, h, w)) return 0;
+  return viz_feat_carve(a, nullptr);
+}
+
+int smd_viz_feat_moments(const float* feat, int b, int C, int h, int w, double* mean, double* cov, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!feat || !mean || !cov || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  smd::VizFeatArgs a;
+  if (!viz_feat_args(a, b, C, h, w)) return fail(SMD_E_INVALID, "sizes that are not served b=%d C=%d h=%d w=%d (3 <= C <= %d, 3 <= b*h*w < 2^31)", b, C, h, w, smd::kVzMaxC);
+  if ((uintptr_t)workspace % 8 || (uintptr_t)mean % 8 || (uintptr_t)cov % 8) return fail(SMD_E_INVALID, "the workspace, mean and cov need 8-byte alignment");
+  const size_t need = viz_feat_carve(a, workspace);
+  if (workspace_bytes < need) return fail(SMD_E_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, need);
+  a.feat = feat; a.mean = mean; a.cov = cov;
+  return check_launch(smd::launch_viz_feat_moments(a, (hipStream_t)stream), "viz_feat_moments");
+}
+
+int smd_viz_feat_project(const float* feat, const double* mean, const float* V, int b, int C, int h, int w, float* rgb, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+  if (!feat || !mean || !V || !rgb || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  smd::VizFeatArgs a;
+  if (!viz_feat_args(a, b, C, h, w)) return fail(SMD_E_INVALID, "sizes that are not served b=%d C=%d h=%d w=%d (3 <= C <= %d, 3 <= b*h*w < 2^31)", b, C, h, w, smd::kVzMaxC);
+  if ((uintptr_t)workspace % 8 || (uintptr_t)mean % 8) return fail(SMD_E_INVALID, "the workspace and mean need 8-byte alignment");
+  const size_t need = viz_feat_carve(a, workspace);
+  if (workspace_bytes < need) return fail(SMD_E_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, need);
+  a.feat = feat; a.mean = (double*)mean; a.V = V; a.rgb = rgb;
+  return check_launch(smd::launch_viz_feat_project(a, (hipStream_t)stream), "viz_feat_project");
+}
+
+// workspace of smd_make_grid: the extrema of the blocks of the normalize pass
+size_t smd_make_grid_workspace_bytes(void) { return align256((size_t)smd::kVzGridParts*2*sizeof(float)); }
+
+int smd_make_grid(const void* x, int is_u8, int b, int c, int h, int w, int n_imgs, int nrow, int padding, float pad_value, int normalize, float* grid,
+                  void* workspace, size_t workspace_bytes, void* stream) {
+  if (!x || !grid || !workspace) return fail(SMD_E_INVALID, "null pointer");
+  if (b < 1 || (c != 1 && c != 3) || h < 1 || w < 1) return fail(SMD_E_INVALID, "invalid sizes b=%d c=%d h=%d w=%d (c is 1 or 3)", b, c, h, w);
+  if (n_imgs < 1 || nrow < 1 || padding < 0) return fail(SMD_E_INVALID, "invalid grid n_imgs=%d nrow=%d padding=%d", n_imgs, nrow, padding);
+  if ((uintptr_t)workspace % 4) return fail(SMD_E_INVALID, "the workspace needs 4-byte alignment");
+  if (workspace_bytes < smd_make_grid_workspace_bytes()) return fail(SMD_E_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, smd_make_grid_workspace_bytes());
+  smd::GridArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = x; a.u8 = is_u8 != 0; a.c = c; a.h = h; a.w = w; a.n = std::min(b, n_imgs);
+  a.xmaps = std::min(nrow, a.n); a.ymaps = smd::ceil_div(a.n, a.xmaps);
+  a.pad = a.n == 1 ? 0 : padding;                  // a single image is returned as it is (torchvision: `tensor.squeeze(0)`)
+  const size_t Hg = (size_t)(h + a.pad)*a.ymaps + a.pad, Wg = (size_t)(w + a.pad)*a.xmaps + a.pad;
+  if (3*Hg*Wg >= ((size_t)1 << 31) || (size_t)a.n*c*h*w >= ((size_t)1 << 31)) return fail(SMD_E_INVALID, "the grid and the images must stay below 2^31 elements");
+  a.Hg = (int)Hg; a.Wg = (int)Wg; a.pad_value = pad_value; a.normalize = normalize != 0; a.grid = grid; a.ext_part = (float*)workspace;
+  return check_launch(smd::launch_make_grid(a, (hipStream_t)stream), "make_grid");
+}
+
 size_t smd_recon_reduce_workspace_bytes(int B, int h, int w) {
   if (B < 1 || h < 1 || w < 1) return 0;
   return align256((size_t)smd::ceil_div(B*h*w, 256)*sizeof(float));

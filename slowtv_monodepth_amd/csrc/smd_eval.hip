@@ -24,6 +24,7 @@
 
 #include "smd_common.h"
 #include "smd_kernels.h"
+#include "smd_select_dev.h"
 
 namespace smd {
 
@@ -56,8 +57,8 @@ __device__ __forceinline__ float ev_nearest(const float* __restrict__ plane, int
   return plane[(size_t)y*w + x];
 }
 
-// `to_inv` (src/tools/geometry.py:86-90): (d > 0)/clamp(d, eps).  A NaN gives 0/NaN = NaN there and is masked out by `pred > 0`; it is 0 here.
-__device__ __forceinline__ float ev_inv(float d) { return d > 0.f ? 1.f/fmaxf(d, kEps32) : 0.f; }
+// `to_inv` on one value (smd_select_dev.h): a NaN is 0 here and masked out by `pred > 0`.
+__device__ __forceinline__ float ev_inv(float d) { return to_inv1(d); }
 
 __device__ __forceinline__ double ev_wave_sum(double v) {
 #pragma unroll
@@ -80,26 +81,10 @@ __device__ __forceinline__ void ev_block_sums(const double* s, double* red, doub
   }
 }
 
-// Block-wide: the bin of hist[0, kEvBins) that holds the element of rank k (0-based, ascending) and k's rank inside that bin; -> the histogram's total.
-// One bin per thread (kEvBins == kEvBlock).  With k >= total nothing is selected (bin = rank = 0).  sh: kEvWaves + 2 words of LDS.
+// One digit of the select: smd_select_dev.h (shared with smd_viz.hip).  kEvBins == kEvBlock == kSelBlock: one bin per thread.
+static_assert(kEvBlock == kSelBlock && kEvBins == kSelBlock, "select_bin256 takes one bin per thread");
 __device__ __forceinline__ unsigned ev_select(const unsigned* __restrict__ hist, unsigned k, unsigned* sh, unsigned& bin, unsigned& rank) {
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid/kWave;
-  const unsigned mine = hist[tid];
-  unsigned incl = mine;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) { const unsigned v = __shfl_up(incl, off, kWave); if (lane >= off) incl += v; }
-  if (lane == kWave - 1) sh[wv] = incl;
-  if (tid == 0) { sh[kEvWaves] = 0; sh[kEvWaves + 1] = 0; }
-  __syncthreads();
-  unsigned before = 0, total = 0;
-#pragma unroll
-  for (int q = 0; q < kEvWaves; ++q) { if (q < wv) before += sh[q]; total += sh[q]; }
-  const unsigned excl = before + incl - mine;
-  if (k >= excl && k < excl + mine) { sh[kEvWaves] = (unsigned)tid; sh[kEvWaves + 1] = k - excl; }   // exactly one thread when k < total
-  __syncthreads();
-  bin = sh[kEvWaves]; rank = sh[kEvWaves + 1];
-  __syncthreads();                               // sh is reused by the next call
-  return total;
+  return select_bin256(hist, k, sh, bin, rank);
 }
 
 // The prefixes that levels [0, upto) selected for the four (array, rank) combinations of item bi: combo 0, 1 = the prediction's ranks (n-1)/2 and n/2,

@@ -490,6 +490,60 @@ size_t eval_hist_bytes(int b);
 int pc_splits(int cap);
 hipError_t launch_eval_metrics(EvalArgs a, hipStream_t st);
 hipError_t launch_eval_pointcloud(PcArgs a, hipStream_t st);
+// smd_viz.hip: image logging.  viz_disp's workspace is hist; viz_feat's mean partials | mean (fp32) | tile partials, then (project) the blocks' extrema | the
+// six extrema; make_grid's the blocks' extrema.
+constexpr int kVzBlock = 256, kVzBins = 256, kVzMaxLut = 1024, kVzMaxC = 1024;
+constexpr int kVzTile = 32, kVzK = 64, kVzTileElems = kVzTile*kVzTile;     // covariance: 32 x 32 channel tiles, 64 samples per LDS stage
+constexpr int kVzGridParts = 256;                                           // make_grid(normalize=True): blocks of the extrema pass
+struct VizDispArgs {
+  const float* disp;        // (b,1,h,w)
+  int b, hw;
+  bool invert, select;      // select: vmax = np.percentile(d[d > 0], 95) per item (else vmax and den are the caller's)
+  float vmin, den0;         // den0: the denominator of an item without a positive value (vmax = 0)
+  const float* lut;         // (N,3)
+  int N;
+  float* rgb;               // (b,3,h,w) out
+  float* vmax;              // (b) out with select, else in
+  float* den;               // (b) vmax - vmin + 1e-5: out with select, else in
+  unsigned* hist;           // [4 levels][b][2 ranks][kVzBins]
+  int nbps;                 // blocks per item (set by the launcher)
+};
+struct VizFeatArgs {
+  const float* feat;        // (b,C,h,w)
+  int b, C, hw;
+  long n;                   // b*hw samples
+  int nsplit;               // blocks per channel of the mean pass
+  int T, npairs, nchunk;    // channel tiles, tile pairs (ti <= tj), sample chunks of the moment pass
+  long chunk;               // samples per chunk (a multiple of kVzK)
+  double* mean_part;        // [C][nsplit]
+  float* meanf;             // [C]
+  float* tile_part;         // [npairs][nchunk][kVzTileElems]
+  double* mean;             // (C) out
+  double* cov;              // (C,C) out: the sums of the centred products (not divided)
+  // projection
+  const float* V;           // (C,3): the three leading eigenvectors
+  float* rgb;               // (b,3,h,w) out
+  float* ext_part;          // [nblk][6]: min0..2, max0..2 per block
+  float* ext;               // [6]
+  int nblk;
+};
+struct GridArgs {
+  const void* x;            // (b,c,h,w) float32 or uint8
+  bool u8;
+  int c, h, w, n, xmaps, ymaps, pad, Hg, Wg;
+  float pad_value;
+  bool normalize;
+  float* grid;              // (3,Hg,Wg) out
+  float* ext_part;          // [kVzGridParts][2]
+};
+int viz_blocks_per_item(int b, int hw);
+size_t viz_hist_bytes(int b);
+void viz_feat_plan(VizFeatArgs& a);
+int viz_proj_blocks(long n);
+hipError_t launch_viz_disp(VizDispArgs a, hipStream_t st);
+hipError_t launch_viz_feat_moments(VizFeatArgs a, hipStream_t st);
+hipError_t launch_viz_feat_project(VizFeatArgs a, hipStream_t st);
+hipError_t launch_make_grid(GridArgs a, hipStream_t st);
 hipError_t launch_pose_fwd(const float* aa, const float* t, const uint8_t* invert, int N, float* T, hipStream_t st);
 hipError_t launch_pose_bwd(const float* aa, const float* t, const uint8_t* invert, int N, const float* g_T, float* g_aa, float* g_t, hipStream_t st);
 hipError_t launch_intrinsics_fwd(const float* fs, const float* cs, const float* Kin, int b, int h, int w, float* K, float* Kinv, hipStream_t st);

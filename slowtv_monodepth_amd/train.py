@@ -288,6 +288,13 @@ def restore_training_state(ckpt: dict, opt, sched, verbose: bool = True) -> int:
     return first_epoch
 
 
+def make_image_logger(log_dir, writer: str = 'npy'):
+    """`--log-images DIR` -> a `HeavyLogger` writing to DIR; None without the flag (nothing of the logger is imported or built)."""
+    if log_dir is None: return None
+    from .heavy_logger import HeavyLogger, NpyWriter, TensorBoardWriter
+    return HeavyLogger(writer={'npy': NpyWriter, 'tensorboard': TensorBoardWriter}[writer](log_dir))
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description='Monocular depth trainer (MI355X hot path).')
     p.add_argument('--cfg-files', '-c', type=Path, nargs='*', required=True, help='YAML configs (default, override...).')
@@ -303,9 +310,12 @@ def main(argv=None):
                                                                'optimizer and scheduler state, epoch counter')
     p.add_argument('--val-steps', default=0, type=int, help='validation steps after every epoch (0: none): synthetic batches with LiDAR-like depth, depth metrics printed')
     p.add_argument('--val-depth-shape', default=[375, 1242], type=int, nargs=2, help='size of the synthetic ground-truth depth maps of the validation batches')
+    p.add_argument('--log-images', type=Path, default=None, metavar='DIR', help='log image grids of the last train (and val) batch at the end of every epoch (rank 0)')
+    p.add_argument('--log-writer', default='npy', choices=('npy', 'tensorboard'), help='npy: one .npy per key and epoch; tensorboard: needs the tensorboard package')
     args = p.parse_args(argv)
 
     cfg = io.load_merge_yaml(*args.cfg_files)
+    if args.log_images is not None: cfg.setdefault('trainer', {})['log_images'] = True     # the losses keep their artefacts (`MonoDepthModule.want_aux`)
     rank, local, world = init_distributed()
     device = torch.device('cuda', local) if torch.cuda.is_available() else torch.device('cpu')
     torch.manual_seed(args.seed)
@@ -339,6 +349,7 @@ def main(argv=None):
         load_reference_checkpoint(module, ckpt)
         first_epoch = restore_training_state(ckpt, opt, sched, verbose=rank == 0)
         if rank == 0: print(f'resumed from {args.resume}: epoch {first_epoch}, global step {ckpt.get("global_step", 0)}', flush=True)
+    image_logger = make_image_logger(args.log_images, args.log_writer) if rank == 0 else None
     for epoch in range(first_epoch, tcfg.get('max_epochs', 1)):
         t0 = time.time()
         # (shallow copies: the aspect-ratio augmentation replaces entries of the batch dicts in place, as in the reference)
@@ -353,6 +364,15 @@ def main(argv=None):
             if val: print(f'epoch {epoch}: val ' + '  '.join(f'{k} {v.item():.4f}' for k, v in val.items()), flush=True)
             from .networks.checkpoint import reference_checkpoint
             torch.save(reference_checkpoint(module, epoch=epoch, global_step=(epoch + 1)*args.steps, optimizer=opt, scheduler=sched), save_dir/'last.ckpt')
+            if image_logger is not None:     # the last batch of each mode, as the reference's callback logs `current_batch[mode]`
+                # (the train step runs in train mode under no_grad, as Lightning's on_train_epoch_end does: it updates this rank's BatchNorm running statistics
+                # and draws from the generator, after the checkpoint of the epoch was written)
+                image_logger.log_step(module, batch, 'train', epoch)
+                if val_batch is not None:     # in eval mode, as the reference's validation callback runs (BatchNorm's running statistics, and none updated)
+                    was_training = module.training
+                    module.eval()
+                    try: image_logger.log_step(module, val_batch, 'val', epoch)
+                    finally: module.train(was_training)
     if world > 1: dist.destroy_process_group()
 
 
