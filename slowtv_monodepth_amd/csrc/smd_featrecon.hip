@@ -13,7 +13,7 @@
 //              the un-warped up-sample of the support at (x, y);
 //   reduce     k_recon_reduce_fwd's statements: min (first index wins ties) or mean over the supports, the static candidate + eps * noise, sel = 255 where it wins.
 //              The noise is the caller's tensor or `gauss_noise(seed, b*H*W index)` (smd_common.h), as in smd_recon_reduce_fwd: equal seeds draw equal noise.
-// The loss is the mean of the reduced error: one fp64 sum per block, added by a one-block second stage in a fixed order (no atomics, bit-reproducible).
+// The loss is the mean of the reduced error: one fp64 sum per block, added by a one-block second stage in a fixed order (`launch_sum_partials_f64`; no atomics, bit-reproducible).
 //
 // Backward, one sweep: `sel` names the support(s) that carry a gradient (the winner for min, all for mean, none where the automask won).  For those the samples
 // are recomputed together with d warp / d fx and d warp / d fy (the same nine loads), summed over the channels into d err / d sx, d err / d sy, and pushed through
@@ -26,6 +26,7 @@
 // channel plane as the scalar offset, the tap as the per-lane offset: DESIGN §3); an offset outside the tensor would read 0 instead of faulting.
 #include "smd_common.h"
 #include "smd_kernels.h"
+#include "smd_photo_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -35,21 +36,7 @@ namespace {
 
 constexpr int kFrCols = 64, kFrRows = 4, kFrBlock = kFrCols*kFrRows;
 
-// k_view_synth_fwd's per-pixel projection (smd_unfused.hip: pix_geom), statement by statement.  pix_geom is local to that file, so this is a second copy: whoever
-// changes one changes the other (moving both into smd_common.h is the follow-up).  What ties them today: tests/test_gpu_featrecon.py holds `sel` to the plain
-// path's pixel for pixel on every case and the warp and the gradients to fp64 within the plain path's own error.
-struct FrGeom { float hx, hy, hz, nx, ny, yz, rz, sx, sy; };
-
-__device__ __forceinline__ FrGeom fr_geom(const Cam& cm, float D, float uf, float vf, float wscale, float hscale) {
-  FrGeom g;
-  g.hx = fmaf(cm.H[0], uf, fmaf(cm.H[1], vf, cm.H[2]));
-  g.hy = fmaf(cm.H[3], uf, fmaf(cm.H[4], vf, cm.H[5]));
-  g.hz = fmaf(cm.H[6], uf, fmaf(cm.H[7], vf, cm.H[8]));
-  g.nx = fmaf(D, g.hx, cm.a0); g.ny = fmaf(D, g.hy, cm.a1); g.yz = fmaf(D, g.hz, cm.tz);
-  g.rz = __builtin_amdgcn_rcpf(fmaxf(g.yz, kZMin));
-  g.sx = fmaf(g.nx*g.rz, wscale, -0.5f); g.sy = fmaf(g.ny*g.rz, hscale, -0.5f);
-  return g;
-}
+// (the projection `pix_geom`, the dense errors, the reduction over the supports and ViewSynth's adjoint: smd_photo_dev.h, the un-fused operators' own statements)
 
 // ATen's bilinear up-sampling along one axis (align_corners=False): out[d] = (1 - l1) in[i0] + l1 in[i1]
 struct UpTap { int i0, i1; float l1; };
@@ -145,8 +132,6 @@ __device__ __forceinline__ float warp9(rsrc_t r, const Warp9& w, unsigned plane,
   return fmaf(w.fy, bot - top, top);
 }
 
-__device__ __forceinline__ float dense_err(float e1, float e2, int l1, float rc) { return l1 ? e1*rc : sqrtf(fmaxf(e2, kEps32)); }
-
 // ------------------------------------------------------------------------------------------------- forward
 template <bool WARP>
 __global__ __launch_bounds__(kFrBlock) void k_feat_recon_fwd(const FrArgs a) {
@@ -168,7 +153,7 @@ __global__ __launch_bounds__(kFrBlock) void k_feat_recon_fwd(const FrArgs a) {
     Cam cm;
     make_cam(cm, a.T + ((size_t)i*a.b + bi)*16, a.K + (size_t)bi*16, a.Kinv + (size_t)bi*16);
     if (!live) continue;
-    const FrGeom g = fr_geom(cm, D, (float)x, (float)y, a.wscale, a.hscale);
+    const PixGeom g = pix_geom(cm, D, (float)x, (float)y, a.wscale, a.hscale);
     const Taps tp = make_taps(g.sx, g.sy, a.H, a.W, a.W);
     const Warp9 w9 = make_warp9(tp, a.W, a);
     const unsigned pt0 = (unsigned)bi*(unsigned)a.C*plane, ps0 = ((unsigned)i*(unsigned)a.b + (unsigned)bi)*(unsigned)a.C*plane;
@@ -207,15 +192,6 @@ __global__ __launch_bounds__(kFrBlock) void k_feat_recon_fwd(const FrArgs a) {
   block_store_sum<Waves::Sequential, kFrRows, double>(live ? (double)e : 0.0, red, a.part + ((size_t)bi*gridDim.y + blockIdx.y)*gridDim.x + blockIdx.x);
 }
 
-// one block: the blocks' sums in a fixed order -> loss = sum * scale
-__global__ __launch_bounds__(kFrBlock) void k_feat_recon_fin(const double* __restrict__ part, int nblk, double scale, float* __restrict__ loss) {
-  __shared__ double red[kFrBlock/64];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nblk; i += kFrBlock) s += part[i];
-  const double t = block_sum<Waves::Sequential, kFrBlock/64, double>(s, red);
-  if (threadIdx.x == 0) loss[0] = (float)(t*scale);
-}
-
 // ------------------------------------------------------------------------------------------------- backward
 template <bool WT, bool WD>
 __global__ __launch_bounds__(kFrBlock) void k_feat_recon_bwd(const FrArgs a) {
@@ -239,7 +215,7 @@ __global__ __launch_bounds__(kFrBlock) void k_feat_recon_bwd(const FrArgs a) {
     float ps[kPoseSums] = {};
     if (live && (a.use_min ? s == i : s != SMD_SEL_MASKED)) {
       const float uf = (float)x, vf = (float)y;
-      const FrGeom g = fr_geom(cm, D, uf, vf, a.wscale, a.hscale);
+      const PixGeom g = pix_geom(cm, D, uf, vf, a.wscale, a.hscale);
       const Taps tp = make_taps(g.sx, g.sy, a.H, a.W, a.W);
       const Warp9 w9 = make_warp9(tp, a.W, a);
       const unsigned pt0 = (unsigned)bi*(unsigned)a.C*plane, ps0 = ((unsigned)i*(unsigned)a.b + (unsigned)bi)*(unsigned)a.C*plane;
@@ -249,30 +225,21 @@ __global__ __launch_bounds__(kFrBlock) void k_feat_recon_bwd(const FrArgs a) {
         float ddx, ddy;
         const float d = warp9(rs, w9, ps0 + (unsigned)c*plane, ddx, ddy) - t;
         if (a.l1) {
-          const float sg = (d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f);
+          const float sg = sgn(d);
           sx_ = fmaf(sg, ddx, sx_); sy_ = fmaf(sg, ddy, sy_);
         } else {
           e2 = fmaf(d, d, e2); sx_ = fmaf(d, ddx, sx_); sy_ = fmaf(d, ddy, sy_);
         }
       }
       // d err / d warp_c = d / sqrt(e2) (0 where clamp(min=eps) is active: k_photo_error_bwd) | sign(d) / C
-      const float k = a.l1 ? ge/(float)a.C : ((e2 >= kEps32) ? ge/sqrtf(e2) : 0.f);
-      const float gsx = k*sx_, gsy = k*sy_;
-      // k_view_synth_bwd's statements
-      const float gpx = gsx*tp.mx*a.wscale, gpy = gsy*tp.my*a.hscale;
-      const float gnx = gpx*g.rz, gny = gpy*g.rz;
-      const float gz = (g.yz >= kZMin) ? -(gpx*g.nx + gpy*g.ny)*g.rz*g.rz : 0.f;
-      gd += fmaf(gnx, g.hx, fmaf(gny, g.hy, gz*g.hz));
-      if (WT) {
-        const float dnx = gnx*D, dny = gny*D, dz = gz*D;
-        ps[0] = dnx*uf; ps[1] = dnx*vf; ps[2] = dnx; ps[3] = dny*uf; ps[4] = dny*vf; ps[5] = dny;
-        ps[6] = dz*uf; ps[7] = dz*vf; ps[8] = dz; ps[9] = gnx; ps[10] = gny; ps[11] = gz;
-      }
+      const float k = a.l1 ? ge/(float)a.C : dense_l2_gfac(ge, e2);
+      float gnx, gny, gz;
+      synth_adj(g, tp, k*sx_, k*sy_, a.wscale, a.hscale, gnx, gny, gz);
+      gd += synth_adj_depth(g, gnx, gny, gz);
+      if (WT) pose_sums(ps, gnx, gny, gz, D, uf, vf);
     }
     if (WT) {
-      stage_wave_sums(ps, &red[0][0]);
-      if (threadIdx.x < kPoseSums)
-        a.pose_partial[(((size_t)i*a.b + bi)*nblk + blk)*kPoseSums + threadIdx.x] = 0.f + sum_waves<Waves::Sequential, kFrRows>(&red[0][0], kPoseSums, threadIdx.x);
+      store_pose_sums<kFrRows>(ps, &red[0][0], a.pose_partial + (((size_t)i*a.b + bi)*nblk + blk)*kPoseSums);
       __syncthreads();      // `red` is written again for the next support
     }
   }
@@ -300,8 +267,8 @@ static FrArgs fr_args(const float* depth, const float* feat, const float* supp, 
   FrArgs a = {};
   a.depth = depth; a.feat = feat; a.supp = supp; a.T = T; a.K = K; a.Kinv = Kinv;
   a.b = b; a.n = n; a.C = C; a.H = H; a.W = W; a.hf = hf; a.wf = wf;
-  a.l1 = (flags & SMD_LOSS_L1) ? 1 : 0; a.use_min = (flags & SMD_USE_MIN) ? 1 : 0; a.automask = (flags & SMD_USE_AUTOMASK) ? 1 : 0;
-  a.wscale = (float)((double)W/(double)(W - 1)); a.hscale = (float)((double)H/(double)(H - 1));      // launch_view_synth_fwd's
+  recon_switches(flags, a.l1, a.use_min, a.automask);
+  a.wscale = synth_scale(W); a.hscale = synth_scale(H);
   a.rx = (float)wf/(float)W; a.ry = (float)hf/(float)H;                                              // ATen: area_pixel_compute_scale<float>
   return a;
 }
@@ -315,8 +282,7 @@ hipError_t launch_feat_recon_fwd(const float* depth, const float* feat, const fl
   for_bool(warp != nullptr, [&](auto w) { hipLaunchKernelGGL((k_feat_recon_fwd<decltype(w)::value>), grid, dim3(kFrBlock), 0, st, a); });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_feat_recon_fin, dim3(1), dim3(kFrBlock), 0, st, (const double*)part, feat_recon_blocks(b, H, W), 1.0/((double)b*H*W), loss);
-  return hipGetLastError();
+  return launch_sum_partials_f64(part, feat_recon_blocks(b, H, W), 1.0/((double)b*H*W), loss, st);
 }
 
 hipError_t launch_feat_recon_bwd(const float* depth, const float* feat, const float* supp, const float* T, const float* K, const float* Kinv, const uint8_t* sel,

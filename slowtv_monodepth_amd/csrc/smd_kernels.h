@@ -212,7 +212,11 @@ void note_variant(int which, const char* fmt, ...);   // smd_api.hip: the instan
 hipError_t launch_recon_prep(const ReconPrepArgs& a, hipStream_t st);
 hipError_t launch_recon_main(const ReconMainArgs& a, hipStream_t st);
 hipError_t launch_recon_bwd(const ReconBwdArgs& a, hipStream_t st);
+// smd_unfused / smd_maskrecon / smd_featrecon launchers: ViewSynth's scale of an axis of n pixels (pix_geom's wscale, hscale), and the reduction's switches of a flag word
+static inline float synth_scale(int n) { return (float)((double)n/(double)(n - 1)); }
+static inline void recon_switches(int flags, int& l1, int& use_min, int& automask) { l1 = (flags & SMD_LOSS_L1) ? 1 : 0; use_min = (flags & SMD_USE_MIN) ? 1 : 0; automask = (flags & SMD_USE_AUTOMASK) ? 1 : 0; }
 hipError_t launch_sum_partials(const float* partial, int count, double scale, float* out, hipStream_t st);
+hipError_t launch_sum_partials_f64(const double* partial, int count, double scale, float* out, hipStream_t st);
 hipError_t launch_pose_finalize(const float* pose_partial, int entries, int stride, const float* T, const float* K, const float* Kinv,
                                 float* g_T, float* g_K, float* g_Kinv, int b, int n, hipStream_t st);
 

@@ -18,7 +18,7 @@
 //
 // Forward, a block = a tile of 32 x 8 pixels of one (scale, sample): per support the warp of the tile and a halo of one goes to LDS (three channels), next to
 // the target's and, with the automask, the un-warped support's; a barrier; every thread forms its pixel's errors from LDS.  The loss is the mean of the
-// reduced error: one fp64 sum per block, added by a one-block second stage in a fixed order.  `stat` keeps the static winner where min and automask are both
+// reduced error: one fp64 sum per block, added by a one-block second stage in a fixed order (`launch_sum_partials_f64`).  `stat` keeps the static winner where min and automask are both
 // on: the backward reads decisions, it never re-decides.
 //
 // Backward, one sweep, per tile and support: the warp with a halo of two; the three SSIM coefficients of every pixel of the tile and a halo of one
@@ -68,11 +68,8 @@ __device__ __forceinline__ float photo_err(const Tile<R>& x, const Tile<R>& y, i
     const float d = x.v[c][ly][lx] - y.v[c][ly][lx];
     el += fabsf(d);
     if (SSIM) {
-      float sx = 0.f, sxx = 0.f, sxy = 0.f, sy = 0.f, syy = 0.f;
-#pragma unroll
-      for (int dv = -1; dv <= 1; ++dv)
-#pragma unroll
-        for (int du = -1; du <= 1; ++du) window_tap(x.v[c][ly + dv][lx + du], y.v[c][ly + dv][lx + du], sx, sxx, sxy, sy, syy);
+      float sx, sxx, sxy, sy, syy;
+      window_walk([&](int dv, int du, float& p, float& t) { p = x.v[c][ly + dv][lx + du]; t = y.v[c][ly + dv][lx + du]; }, sx, sxx, sxy, sy, syy);
       es += ssim_win_err(sx, sxx, sxy, sy, syy);
     }
   }
@@ -183,21 +180,7 @@ __global__ __launch_bounds__(kMrBlock) void k_mask_recon_fwd(const MrArgs a) {
   block_store_sum<Waves::Sequential, kMrWaves, double>(live ? (double)e : 0.0, red, a.part + ((size_t)z*gridDim.y + blockIdx.y)*gridDim.x + blockIdx.x);
 }
 
-// one block: the blocks' sums in a fixed order -> loss = sum * scale
-__global__ __launch_bounds__(kMrBlock) void k_mask_recon_fin(const double* __restrict__ part, int nblk, double scale, float* __restrict__ loss) {
-  __shared__ double red[kMrWaves];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nblk; i += kMrBlock) s += part[i];
-  const double t = block_sum<Waves::Sequential, kMrWaves, double>(s, red);
-  if (threadIdx.x == 0) loss[0] = (float)(t*scale);
-}
-
 // ------------------------------------------------------------------------------------------------- backward
-// The gradient that reaches the MASKED warped error of support i at a pixel (k_recon_reduce_bwd: routed by `sel`), and the one that reaches its masked static error.
-__device__ __forceinline__ float routed(int s, int i, float g, float gn, int use_min) {
-  return use_min ? (s == i ? g : 0.f) : (s != SMD_SEL_MASKED ? gn : 0.f);
-}
-
 template <bool SSIM, bool WT, bool WD, bool WM>
 __global__ __launch_bounds__(kMrBlock) void k_mask_recon_bwd(const MrArgs a) {
   constexpr int R = SSIM ? 2 : 0, RC = SSIM ? 1 : 0;       // halo of the images, of the coefficients
@@ -246,11 +229,8 @@ __global__ __launch_bounds__(kMrBlock) void k_mask_recon_bwd(const MrArgs a) {
         for (int c = 0; c < kMrC; ++c) {
           float ca = 0.f, cb = 0.f, cc = 0.f;
           if (ge != 0.f && !a.l1) {
-            float sx = 0.f, sxx = 0.f, sxy = 0.f, sy = 0.f, syy = 0.f;
-#pragma unroll
-            for (int dv = -1; dv <= 1; ++dv)
-#pragma unroll
-              for (int du = -1; du <= 1; ++du) window_tap(wp.v[c][ly + dv][lx + du], tg.v[c][ly + dv][lx + du], sx, sxx, sxy, sy, syy);
+            float sx, sxx, sxy, sy, syy;
+            window_walk([&](int dv, int du, float& p, float& t) { p = wp.v[c][ly + dv][lx + du]; t = tg.v[c][ly + dv][lx + du]; }, sx, sxx, sxy, sy, syy);
             ssim_win_coef(sx, sxx, sxy, sy, syy, gc, ca, cb, cc);
           }
           cf[c*3][cy][cx] = ca; cf[c*3 + 1][cy][cx] = cb; cf[c*3 + 2][cy][cx] = cc;
@@ -265,10 +245,10 @@ __global__ __launch_bounds__(kMrBlock) void k_mask_recon_bwd(const MrArgs a) {
       float v = routed(sq, i, g, gn, a.use_min);
       const float dm = a.mask_mode == 1 ? m : __expf(-m);      // d masked / d err
       if (WM) {
-        const float gs = (a.automask && sq == SMD_SEL_MASKED) ? (a.use_min ? (i == jq ? g : 0.f) : gn) : 0.f;      // reaches the masked STATIC error of support i
+        const float gs = routed_static(sq, i, jq, g, gn, a.use_min, a.automask);      // reaches the masked STATIC error of support i
         const float ew = (v != 0.f) ? photo_err<SSIM, R>(wp, tg, lx, ly, a.l1) : 0.f;
         const float es = (gs != 0.f) ? photo_err<SSIM, R>(sp, tg, lx, ly, a.l1) : 0.f;
-        a.g_mask[((size_t)z*n + i)*hw + pix] = a.mask_mode == 1 ? v*ew + gs*es : v*fmaf(-ew, dm, 1.f) + gs*fmaf(-es, dm, 1.f);
+        a.g_mask[((size_t)z*n + i)*hw + pix] = a.mask_mode == 1 ? v*ew + gs*es : v*fmaf(-ew, dm, 1.f) + gs*fmaf(-es, dm, 1.f);      // (`mask_grad`, smd_photo_dev.h)
       }
       v *= dm;
       if (GEO) {
@@ -284,7 +264,7 @@ __global__ __launch_bounds__(kMrBlock) void k_mask_recon_bwd(const MrArgs a) {
         for (int c = 0; c < kMrC; ++c) {
           const float xv = wp.v[c][ly][lx], yv = tg.v[c][ly][lx];
           const float d = xv - yv;
-          float gx = gl*((d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f));
+          float gx = gl*sgn(d);
           if (SSIM && !a.l1) {
             float SA = 0.f, SB = 0.f, SC = 0.f;
 #pragma unroll
@@ -307,23 +287,13 @@ __global__ __launch_bounds__(kMrBlock) void k_mask_recon_bwd(const MrArgs a) {
           gsx = fmaf(gx, ddx, gsx); gsy = fmaf(gx, ddy, gsy);
         }
         // k_view_synth_bwd's statements
-        const float uf = (float)x, vf = (float)y;
-        const float gpx = gsx*tp.mx*a.wscale, gpy = gsy*tp.my*a.hscale;
-        const float gnx = gpx*pg.rz, gny = gpy*pg.rz;
-        const float gz = (pg.yz >= kZMin) ? -(gpx*pg.nx + gpy*pg.ny)*pg.rz*pg.rz : 0.f;
-        gd += fmaf(gnx, pg.hx, fmaf(gny, pg.hy, gz*pg.hz));
-        if (WT) {
-          const float dnx = gnx*D, dny = gny*D, dz = gz*D;
-          ps[0] = dnx*uf; ps[1] = dnx*vf; ps[2] = dnx; ps[3] = dny*uf; ps[4] = dny*vf; ps[5] = dny;
-          ps[6] = dz*uf; ps[7] = dz*vf; ps[8] = dz; ps[9] = gnx; ps[10] = gny; ps[11] = gz;
-        }
+        float gnx, gny, gz;
+        synth_adj(pg, tp, gsx, gsy, a.wscale, a.hscale, gnx, gny, gz);
+        gd += synth_adj_depth(pg, gnx, gny, gz);
+        if (WT) pose_sums(ps, gnx, gny, gz, D, (float)x, (float)y);
       }
     }
-    if (WT) {
-      stage_wave_sums(ps, &red[0][0]);
-      if (threadIdx.x < kPoseSums)
-        a.pose_partial[((((size_t)i*a.b + bi)*a.S + s)*nblk + blk)*kPoseSums + threadIdx.x] = 0.f + sum_waves<Waves::Sequential, kMrWaves>(&red[0][0], kPoseSums, threadIdx.x);
-    }
+    if (WT) store_pose_sums<kMrWaves>(ps, &red[0][0], a.pose_partial + ((((size_t)i*a.b + bi)*a.S + s)*nblk + blk)*kPoseSums);
   }
   if (WD && live) a.g_depth[idx] = gd;
 }
@@ -344,9 +314,9 @@ static MrArgs mr_args(const float* depth, const float* mask, const float* tgt, c
   MrArgs a = {};
   a.depth = depth; a.mask = mask; a.tgt = tgt; a.supp = supp; a.T = T; a.K = K; a.Kinv = Kinv;
   a.S = S; a.b = b; a.n = n; a.h = h; a.w = w;
-  a.l1 = (flags & SMD_LOSS_L1) ? 1 : 0; a.use_min = (flags & SMD_USE_MIN) ? 1 : 0; a.automask = (flags & SMD_USE_AUTOMASK) ? 1 : 0;
+  recon_switches(flags, a.l1, a.use_min, a.automask);
   a.mask_mode = (flags & SMD_MASK_UNCERTAINTY) ? 2 : 1;
-  a.wscale = (float)((double)w/(double)(w - 1)); a.hscale = (float)((double)h/(double)(h - 1));      // launch_view_synth_fwd's
+  a.wscale = synth_scale(w); a.hscale = synth_scale(h);
   return a;
 }
 
@@ -361,8 +331,7 @@ hipError_t launch_mask_recon_fwd(const float* depth, const float* mask, const fl
     hipLaunchKernelGGL((k_mask_recon_fwd<decltype(ss)::value, decltype(wr)::value>), grid, dim3(kMrBlock), 0, st, a); }); });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_mask_recon_fin, dim3(1), dim3(kMrBlock), 0, st, (const double*)part, mask_recon_tiles(h, w)*S*b, 1.0/((double)S*b*h*w), loss);
-  return hipGetLastError();
+  return launch_sum_partials_f64(part, mask_recon_tiles(h, w)*S*b, 1.0/((double)S*b*h*w), loss, st);
 }
 
 hipError_t launch_mask_recon_bwd(const float* depth, const float* mask, const float* tgt, const float* supp, const float* T, const float* K, const float* Kinv,

@@ -27,6 +27,20 @@ hipError_t launch_sum_partials(const float* partial, int count, double scale, fl
   return hipGetLastError();
 }
 
+// ... of fp64 block sums (the fused masked and feature-metric reconstruction forwards): the blocks' sums in a fixed order -> out = sum * scale
+__global__ __launch_bounds__(256) void k_sum_partials_f64(const double* __restrict__ part, int count, double scale, float* __restrict__ out) {
+  __shared__ double red[4];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < count; i += 256) s += part[i];
+  const double t = block_sum<Waves::Sequential, 4, double>(s, red);
+  if (threadIdx.x == 0) out[0] = (float)(t*scale);
+}
+
+hipError_t launch_sum_partials_f64(const double* partial, int count, double scale, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(k_sum_partials_f64, dim3(1), dim3(256), 0, st, partial, count, scale, out);
+  return hipGetLastError();
+}
+
 // STREAM-style device copy (4 independent 16-B loads per lane in flight, grid-stride): the measured HBM ceiling quoted
 // beside the datasheet peak.  `mode` 0 = copy (read + write), 1 = read-only sum (writes one value per block).
 __global__ __launch_bounds__(256) void k_stream_copy(const f4* __restrict__ src, f4* __restrict__ dst, size_t n16, int mode) {

@@ -13,7 +13,7 @@ namespace smd {
 
 constexpr int kUfBlock = 256;
 
-// (PixGeom / pix_geom, reflect1, the SSIM statements of a pixel and masked_err: smd_photo_dev.h, shared with smd_maskrecon.hip)
+// (the per-element statements of every kernel here: smd_photo_dev.h, shared with smd_maskrecon.hip and smd_featrecon.hip)
 
 // ---------------------------------------------------------------------------------------------
 // ViewSynth.forward (src/tools/geometry.py:366-391)
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(kUfBlock) void k_view_synth_fwd(const float* __rest
 
 hipError_t launch_view_synth_fwd(const float* input, const float* depth, const float* T, const float* K, const float* Kinv,
                                  float* warp, float* depth_warp, uint8_t* mask_valid, int B, int C, int h, int w, hipStream_t st) {
-  const float wscale = (float)((double)w/(double)(w - 1)), hscale = (float)((double)h/(double)(h - 1));
+  const float wscale = synth_scale(w), hscale = synth_scale(h);
   hipLaunchKernelGGL(k_view_synth_fwd, dim3(ceil_div(h*w, kUfBlock), B), dim3(kUfBlock), 0, st, input, depth, T, K, Kinv, warp, depth_warp,
                      mask_valid, C, h, w, wscale, hscale);
   return hipGetLastError();
@@ -84,24 +84,19 @@ __global__ __launch_bounds__(kUfBlock) void k_view_synth_bwd(const float* __rest
         atomicAdd(gi + w, go*(1.f - tp.fx)*tp.fy); atomicAdd(gi + w + 1, go*tp.fx*tp.fy);
       }
     }
-    const float gpx = gsx*tp.mx*wscale, gpy = gsy*tp.my*hscale;
-    const float gnx = gpx*g.rz, gny = gpy*g.rz;
-    float gz = (g.yz >= kZMin) ? -(gpx*g.nx + gpy*g.ny)*g.rz*g.rz : 0.f;
+    float gnx, gny, gz;
+    synth_adj(g, tp, gsx, gsy, wscale, hscale, gnx, gny, gz);
     if (g_depth_warp && g.yz >= kEps32) gz += g_depth_warp[(size_t)bi*hw + pix];               // depth_warp = clamp(Yz, eps)
-    g_depth[(size_t)bi*hw + pix] = fmaf(gnx, g.hx, fmaf(gny, g.hy, gz*g.hz));
-    const float dnx = gnx*D, dny = gny*D, dz = gz*D;
-    ps[0] = dnx*uf; ps[1] = dnx*vf; ps[2] = dnx; ps[3] = dny*uf; ps[4] = dny*vf; ps[5] = dny;
-    ps[6] = dz*uf; ps[7] = dz*vf; ps[8] = dz; ps[9] = gnx; ps[10] = gny; ps[11] = gz;
+    g_depth[(size_t)bi*hw + pix] = synth_adj_depth(g, gnx, gny, gz);
+    pose_sums(ps, gnx, gny, gz, D, uf, vf);
   }
-  stage_wave_sums(ps, &red[0][0]);
-  // (0.f +: these sums have always started from +0, and a pose sum, unlike an accumulator, can be -0 in every wave)
-  if (threadIdx.x < kPoseSums) pose_partial[((size_t)bi*gridDim.x + blockIdx.x)*kPoseSums + threadIdx.x] = 0.f + sum_waves<Waves::Sequential, kUfBlock/64>(&red[0][0], kPoseSums, threadIdx.x);
+  store_pose_sums<kUfBlock/64>(ps, &red[0][0], pose_partial + ((size_t)bi*gridDim.x + blockIdx.x)*kPoseSums);
 }
 
 hipError_t launch_view_synth_bwd(const float* input, const float* depth, const float* T, const float* K, const float* Kinv,
                                  const float* g_warp, const float* g_depth_warp, float* g_input, float* g_depth,
                                  float* g_T, float* g_K, float* g_Kinv, float* ws, int B, int C, int h, int w, hipStream_t st) {
-  const float wscale = (float)((double)w/(double)(w - 1)), hscale = (float)((double)h/(double)(h - 1));
+  const float wscale = synth_scale(w), hscale = synth_scale(h);
   const int nblk = ceil_div(h*w, kUfBlock);
   if (g_input) { hipError_t e = hipMemsetAsync(g_input, 0, (size_t)B*C*h*w*sizeof(float), st); if (e != hipSuccess) return e; }
   hipLaunchKernelGGL(k_view_synth_bwd, dim3(nblk, B), dim3(kUfBlock), 0, st, input, depth, T, K, Kinv, g_warp, g_depth_warp, g_input, g_depth,
@@ -119,16 +114,7 @@ enum { kPhotoSsim = 0, kPhotoL1 = 1, kPhotoL2 = 2 };
 // Nine-tap (reflection padded) un-normalised window sums of one channel at (v, u).
 __device__ __forceinline__ void window_sums(const float* __restrict__ x, const float* __restrict__ y, int h, int w, int v, int u,
                                             float& sx, float& sxx, float& sxy, float& sy, float& syy) {
-  sx = sxx = sxy = sy = syy = 0.f;
-#pragma unroll
-  for (int dv = -1; dv <= 1; ++dv) {
-    const int rv = reflect1(v + dv, h)*w;
-#pragma unroll
-    for (int du = -1; du <= 1; ++du) {
-      const int idx = rv + reflect1(u + du, w);
-      window_tap(x[idx], y[idx], sx, sxx, sxy, sy, syy);
-    }
-  }
+  window_walk([&](int dv, int du, float& a, float& b) { const int rv = reflect1(v + dv, h)*w, idx = rv + reflect1(u + du, w); a = x[idx]; b = y[idx]; }, sx, sxx, sxy, sy, syy);
 }
 
 __global__ __launch_bounds__(kUfBlock) void k_photo_error_fwd(const float* __restrict__ pred, const float* __restrict__ target,
@@ -151,7 +137,7 @@ __global__ __launch_bounds__(kUfBlock) void k_photo_error_fwd(const float* __res
   }
   const float rc = 1.f/(float)C;
   // PhotoError(weight_ssim) (src/losses/photometric.py:85-86): weight_ssim * mean_c SSIM + (1 - weight_ssim) * mean_c |.|
-  err[(size_t)ni*hw + pix] = mode == kPhotoL2 ? sqrtf(fmaxf(e2, kEps32)) : (mode == kPhotoL1 ? el*rc : photo_mix(es, el, rc, w_ssim));
+  err[(size_t)ni*hw + pix] = mode == kPhotoL2 ? dense_err(el, e2, 0, rc) : (mode == kPhotoL1 ? dense_err(el, e2, 1, rc) : photo_mix(es, el, rc, w_ssim));
 }
 
 static inline int photo_mode(int flags) { return (flags & SMD_LOSS_L2) ? kPhotoL2 : ((flags & SMD_LOSS_L1) ? kPhotoL1 : kPhotoSsim); }
@@ -194,7 +180,7 @@ __global__ __launch_bounds__(kUfBlock) void k_photo_error_bwd(const float* __res
   if (mode == kPhotoL2) {   // sqrt(clamp(sum d^2, eps)): zero gradient where the clamp is active
     float e2 = 0.f;
     for (int c = 0; c < C; ++c) { const float d = pred[((size_t)ni*C + c)*hw + pix] - target[((size_t)ni*C + c)*hw + pix]; e2 = fmaf(d, d, e2); }
-    const float k = (e2 >= kEps32) ? ge/sqrtf(e2) : 0.f;
+    const float k = dense_l2_gfac(ge, e2);
     for (int c = 0; c < C; ++c) g_pred[((size_t)ni*C + c)*hw + pix] = k*(pred[((size_t)ni*C + c)*hw + pix] - target[((size_t)ni*C + c)*hw + pix]);
     return;
   }
@@ -205,7 +191,7 @@ __global__ __launch_bounds__(kUfBlock) void k_photo_error_bwd(const float* __res
   for (int c = 0; c < C; ++c) {
     const float x = pred[((size_t)ni*C + c)*hw + pix], y = target[((size_t)ni*C + c)*hw + pix];
     const float d = x - y;
-    float gx = gl*((d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f));
+    float gx = gl*sgn(d);
     if (mode == kPhotoSsim) {
       const float* cp = coef + ((size_t)ni*3*C + c*3)*hw;
       float SA = 0.f, SB = 0.f, SC = 0.f;
@@ -294,11 +280,11 @@ __global__ __launch_bounds__(kUfBlock) void k_recon_reduce_bwd(const uint8_t* __
                                                                const float* __restrict__ mask, float* __restrict__ g_mask, int mask_mode, unsigned hw) {
   const unsigned idx = blockIdx.x*kUfBlock + threadIdx.x;
   if (idx >= total) return;
-  const float g = g_loss[0]/(float)total;
-  const uint8_t s = sel[idx];
+  const float g = g_loss[0]/(float)total, gn = g/(float)n;
+  const int s = sel[idx];
   const unsigned bi = idx/hw, pix = idx - bi*hw;
   int jstat = -1;                       // static winner (min-reprojection over the masked identity errors), when the automask removed the pixel
-  if (mask_mode && s == (uint8_t)SMD_SEL_MASKED && use_min && err_static) {
+  if (mask_mode && s == SMD_SEL_MASKED && use_min && err_static) {
     float sb = 0.f;
     for (int i = 0; i < n; ++i) {
       const float v = masked_err(err_static[(size_t)i*total + idx], mask[((size_t)bi*n + i)*hw + pix], mask_mode);
@@ -306,17 +292,15 @@ __global__ __launch_bounds__(kUfBlock) void k_recon_reduce_bwd(const uint8_t* __
     }
   }
   for (int i = 0; i < n; ++i) {
-    float v = 0.f;
-    if (use_min) v = (s == (uint8_t)i) ? g : 0.f;
-    else v = (s != (uint8_t)SMD_SEL_MASKED) ? g/(float)n : 0.f;
+    float v = routed(s, i, g, gn, use_min);
     if (mask_mode) {
       const size_t mi = ((size_t)bi*n + i)*hw + pix;
       const float m = mask[mi];
-      float gs = 0.f;                   // gradient reaching the masked STATIC error of support i
-      if (s == (uint8_t)SMD_SEL_MASKED && err_static) gs = use_min ? (i == jstat ? g : 0.f) : g/(float)n;
+      const float gs = routed_static(s, i, jstat, g, gn, use_min, err_static != nullptr);      // gradient reaching the masked STATIC error of support i
       const float ew = err_warp[(size_t)i*total + idx], es = err_static ? err_static[(size_t)i*total + idx] : 0.f;
-      if (mask_mode == 1) { g_mask[mi] = v*ew + gs*es; v *= m; }
-      else { const float em = __expf(-m); g_mask[mi] = v*fmaf(-ew, em, 1.f) + gs*fmaf(-es, em, 1.f); v *= em; }
+      const float dm = mask_mode == 1 ? m : __expf(-m);      // d masked / d err
+      g_mask[mi] = mask_grad(v, gs, ew, es, dm, mask_mode);
+      v *= dm;
     }
     g_err_warp[(size_t)i*total + idx] = v;
   }

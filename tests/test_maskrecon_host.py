@@ -29,7 +29,9 @@ def test_the_new_symbols_are_declared_in_all_four_places():
     assert _lib.lib.smd_abi_version() == 8
     assert 'smd_maskrecon.hip' in (csrc/'Makefile').read_text()
     assert 'atomic' not in src.split('namespace smd {', 1)[1].lower() and 'gauss_noise(' in src and 'launch_pose_finalize(' in src
-    assert '#include "smd_photo_dev.h"' in src and '#include "smd_photo_dev.h"' in (csrc/'smd_unfused.hip').read_text(), 'the per-element statements are shared, not copied'
+    for f in ('smd_unfused.hip', 'smd_featrecon.hip'): assert '#include "smd_photo_dev.h"' in src and '#include "smd_photo_dev.h"' in (csrc/f).read_text(), 'the per-element statements are shared, not copied'
+    everything = ''.join(f.read_text() for f in sorted(csrc.iterdir()) if f.suffix in ('.hip', '.h', '.inc') or f.name == 'Makefile')
+    for gone in ('fr_geom', 'FrGeom', 'k_mask_recon_fin', 'k_feat_recon_fin'): assert gone not in everything, f'{gone}: the copy is back'
     assert not any('mask_recon' in n or 'masked_fused' in n for n in functional.__all__)
 
 
