@@ -1,7 +1,8 @@
 """Who serves a convolution operator, the split-bf16 MFMA kernels or the reference (MIOpen; for the thin last stage the f32-MFMA kernels): the decision only,
 no autograd, no launches of its own, testable without a GPU (`conv_ops` builds the operators on `serve`).  A same-box A/B decides the first time an (operator,
 shape) pair is seen: both run on the call's own tensors, interleaved, a few times each; the faster one is cached for the process.  `set_conv_route('mfma' |
-'miopen')` pins the choice; inside a HIP-graph capture nothing is timed and `STATIC_RULES` / `STRIDED_RULES` / `TRANSPOSED_RULES` stand in. Operator names: `<fwd | data | wgt>[_<family suffix>]`."""
+'miopen')` pins the choice; inside a HIP-graph capture nothing is timed and `RULES` stands in.  Operator names, the keys of `RULES` and of `conv_routes()`:
+`<fwd | data | wgt>[_<family suffix>]`."""
 from __future__ import annotations
 
 import torch
@@ -27,25 +28,34 @@ def conv_routes() -> dict:
     return dict(_ROUTES)
 
 
-# ---- the static rule, the stand-in where nothing may be timed (graph capture).  Per operator family and operator: the MFMA kernels serve a shape that
-# meets EVERY bound of ANY one clause (`_BOUNDS`; px = B h w, thin: CO == 16, coarse: the row-band tiles' levels, w <= 80 with C >= 256) ----
+# ---- the static rule, the stand-in where nothing may be timed (graph capture).  Per operator: the MFMA kernels serve a shape that meets EVERY bound of ANY
+# one clause (`_BOUNDS`; px = B h w, thin: CO == 16, coarse: the row-band tiles' levels, w <= 80 with C >= 256); no clause: never the kernels.  h x w and
+# the profile that filled the clauses, per family of operator names:
+#   fwd / data / wgt     fp32 tensors, reflection-padded input (the decoder), h x w the OUTPUT size: the shapes that won on an MI355X at cfg 2,
+#                        profiles/r06_decoder_convs.txt; the coarse levels on the row-band tiles (1.18-1.59 x forward, 1.09-1.74 x data gradient,
+#                        0.92-1.37 x weight gradient): profiles/r08_coarse_convs.txt
+#   *_bf16               the same layers on bf16 tensors, the OUTPUT size: MIOpen's bf16 kernels serve the wide layers; the thin stage is the stencil-like
+#                        case (profiles/r06_decoder_convs.txt)
+#   *_z                  the zero-padded encoder layers (C = CO), the OUTPUT size (= the input's), profiles/r08_coarse_convs.txt: the data gradient wins at
+#                        every stage (1.4-1.7 x); forward and weight gradient win 1.13-1.6 x from 64 to 256 channels and at 512 channels with b = 24 (2880
+#                        pixels), and are even with MIOpen at 512 channels with b = 12 (1440)
+#   fwd_s / wgt_s        the 7x7 stride-2 stems, the INPUT size: profiles/stem_convs.txt (the data gradient is ATen's: no route)
+#   fwd_s2 / wgt_s2      the strided 3x3 layers (`conv3x3_s2`), the INPUT size, profiles/s2_convs.txt (cfg 2, b = 12 / 24): the forward wins at all three
+#                        transition blocks (1.27-2.06 x, the smallest 5760 input pixels per channel); the weight gradient loses at all of them (0.30-0.44 x)
+#   data_t2              their data gradient (a transposed convolution), the layer's INPUT size, the gradient's own: profiles/s2_data_convs.txt (cfg 2,
+#                        b = 12 / 24), the clause filled from what won there
 _COARSE_W_MAX, _COARSE_C_MIN = 80, 256
 _Z_FWD_WGT = [dict(px_min=1000, ch_max=511), dict(px_min=2400)]
-STATIC_RULES = {
-    # fp32 tensors, reflection-padded input (the decoder): the shapes that won on an MI355X at cfg 2, profiles/r06_decoder_convs.txt; the coarse levels on the
-    # row-band tiles (1.18-1.59 x forward, 1.09-1.74 x data gradient, 0.92-1.37 x weight gradient): profiles/r08_coarse_convs.txt
-    'padded': {'fwd': [dict(thin=True), dict(thin=False, px_min=20000, c_co_max=128*64), dict(thin=False, coarse=True, px_min=1000)],
-               'data': [dict(thin=True), dict(thin=False, px_min=5000, c_max=256), dict(thin=False, coarse=True, px_min=1000)],
-               'wgt': [dict(thin=False, px_min=20000, co_max=64), dict(thin=False, coarse=True, px_min=2400)]},
-    # bf16 tensors: MIOpen's bf16 kernels serve the wide layers; the thin stage is the stencil-like case (profiles/r06_decoder_convs.txt)
-    'bf16': {'fwd': [dict(thin=True)], 'data': [dict(thin=True)], 'wgt': [dict(thin=True)]},
-    # the zero-padded encoder layers (C = CO; profiles/r08_coarse_convs.txt): the data gradient wins at every stage (1.4-1.7 x); forward and weight gradient
-    # win 1.13-1.6 x from 64 to 256 channels and at 512 channels with b = 24 (2880 pixels), and are even with MIOpen at 512 channels with b = 12 (1440)
-    'zpad': {'fwd': _Z_FWD_WGT, 'data': [dict(px_min=1000)], 'wgt': _Z_FWD_WGT},
-    # the 7x7 stride-2 stems, h x w the INPUT size: profiles/stem_convs.txt
-    'stem': {'fwd': [dict(px_min=20000)], 'wgt': [dict(px_min=20000)]},
+RULES = {
+    'fwd': [dict(thin=True), dict(thin=False, px_min=20000, c_co_max=128*64), dict(thin=False, coarse=True, px_min=1000)],
+    'data': [dict(thin=True), dict(thin=False, px_min=5000, c_max=256), dict(thin=False, coarse=True, px_min=1000)],
+    'wgt': [dict(thin=False, px_min=20000, co_max=64), dict(thin=False, coarse=True, px_min=2400)],
+    'fwd_bf16': [dict(thin=True)], 'data_bf16': [dict(thin=True)], 'wgt_bf16': [dict(thin=True)],
+    'fwd_z': _Z_FWD_WGT, 'data_z': [dict(px_min=1000)], 'wgt_z': _Z_FWD_WGT,
+    'fwd_s': [dict(px_min=20000)], 'wgt_s': [dict(px_min=20000)],
+    'fwd_s2': [dict(px_min=5000)], 'wgt_s2': [],
+    'data_t2': [dict(px_min=5000)],
 }
-_FAMILY_OF_SUFFIX = {'': 'padded', 'bf16': 'bf16', 'z': 'zpad', 's': 'stem'}
 _BOUNDS = {'px_min': lambda v, B, C, CO, h, w: B*h*w >= v,
            'c_max': lambda v, B, C, CO, h, w: C <= v,
            'co_max': lambda v, B, C, CO, h, w: CO <= v,
@@ -55,28 +65,9 @@ _BOUNDS = {'px_min': lambda v, B, C, CO, h, w: B*h*w >= v,
            'coarse': lambda v, B, C, CO, h, w: (w <= _COARSE_W_MAX and C >= _COARSE_C_MIN) == v}
 
 
-# The strided 3x3 layers (`conv3x3_s2`; h x w the INPUT size), a table of their own: `STATIC_RULES` lists the stride-1 and stem families, each with the
-# operators its kernels have.  Suffix -> {operator: clauses}, the clauses as above.  profiles/s2_convs.txt (cfg 2, b = 12 / 24): the forward wins at all
-# three transition blocks (1.27-2.06 x, the smallest 5760 input pixels per channel); the weight gradient loses at all of them (0.30-0.44 x): MIOpen's.
-STRIDED_RULES = {
-    's2': {'fwd': [dict(px_min=5000)], 'wgt': []},
-}
-
-
-# The data gradient of the strided 3x3 layers (a transposed convolution; h x w the layer's INPUT size, the gradient's own), a third table: the test of the
-# strided table pins its operators.  profiles/s2_data_convs.txt (cfg 2, b = 12 / 24): the clause is filled from what won there.
-TRANSPOSED_RULES = {
-    't2': {'data': [dict(px_min=5000)]},
-}
-
-
 def static_rule(op, B, C, CO, h, w) -> bool:
-    """`STATIC_RULES` (or, for a suffix it does not know, `STRIDED_RULES`, then `TRANSPOSED_RULES`) evaluated for one operator and shape."""
-    kind, _, suffix = op.partition('_')
-    if suffix in _FAMILY_OF_SUFFIX: clauses = STATIC_RULES[_FAMILY_OF_SUFFIX[suffix]][kind]
-    elif suffix in STRIDED_RULES or suffix not in TRANSPOSED_RULES: clauses = STRIDED_RULES[suffix][kind]
-    else: clauses = TRANSPOSED_RULES[suffix][kind]
-    return any(all(_BOUNDS[name](v, B, C, CO, h, w) for name, v in clause.items()) for clause in clauses)
+    """`RULES[op]` evaluated for one shape (`KeyError`: an operator no family has)."""
+    return any(all(_BOUNDS[name](v, B, C, CO, h, w) for name, v in clause.items()) for clause in RULES[op])
 
 
 def may_serve(key, unknown=True) -> bool:

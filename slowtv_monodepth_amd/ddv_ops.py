@@ -5,7 +5,7 @@ import torch
 
 from . import _lib
 from ._device import _check, _on, _ptr, _stream, _workspace, call
-from .conv_ops import _mfma_pack, _mfma_ws_bytes, _served, _wide_backward
+from .conv_ops import conv3x3_wide_backward, pack_weights
 
 __all__ = ['ddv_head', 'NUM_BINS']
 
@@ -22,7 +22,7 @@ class _DdvHead(torch.autograd.Function):
         weight = _check('weight', weight, (M, C, 3, 3))
         bias = _check('bias', bias, (M,))
         if _lib.lib.smd_ddv_head_workspace_bytes(B, C, G, h, w) == 0: raise ValueError(f'ddv_head does not serve the sizes B={B} C={C} out_ch={G} h={h} w={w}')
-        wf, _ = _mfma_pack(weight, C, M, 3, True, False)
+        wf, _ = pack_weights(weight, C, M, 3, True, False)
         disp = torch.empty((B, G, h, w), device=xp.device, dtype=torch.float32)
         stats = torch.empty((B, G, 2, h, w), device=xp.device, dtype=torch.float32)
         call('smd_ddv_head_fwd', xp.data_ptr(), wf.data_ptr(), bias.data_ptr(), disp.data_ptr(), stats.data_ptr(), B, C, G, h, w, _stream())
@@ -45,8 +45,7 @@ class _DdvHead(torch.autograd.Function):
         ws, nbytes = _workspace(dev, _lib.lib.smd_ddv_head_workspace_bytes, B, C, G, h, w)
         call('smd_ddv_head_bwd_logits', xp.data_ptr(), wf.data_ptr(), bias.data_ptr(), disp.data_ptr(), stats.data_ptr(), g_disp.data_ptr(), g_logits.data_ptr(),
              _ptr(g_bias), ws.data_ptr(), nbytes, B, C, G, h, w, _stream())
-        sv = _served(C, M, False, _mfma_ws_bytes(B, C, M, h, w, False) > 0)
-        g_xp, g_w = _wide_backward(xp, weight, None, g_logits, 3, False, False, sv, need_x, need_w, deterministic_ref=True)
+        g_xp, g_w = conv3x3_wide_backward(xp, weight, g_logits, need_x=need_x, need_w=need_w, deterministic_ref=True)
         return g_xp, g_w, g_bias, None
 
 

@@ -4,15 +4,14 @@ PyTorch's role here is plumbing only: it owns the device buffers, provides the c
 Every function validates its inputs on the host and raises the exception types the reference raises (`ValueError`) before any launch; there is no fallback path —
 CPU tensors are rejected.  The operators live in one module per family, and every name here IS the object of its home module: `recon_ops` (the loss path), `row_skip`
 (the fused backward's row-loop tuner and its diagnostics), `class_ops` (the un-fused class-level operators), `net_ops` (the network glue), `geom_ops` (pose and
-intrinsics), `conv_ops` / `conv_routing` (the routed MFMA convolutions), `metric_ops` (the validation depth metrics), `attention_ops` (the CADepth decoder's attention blocks), `fusion_ops` (the DiffNet decoder's glue), `subpixel` (the SuperDepth decoder's sub-pixel convolution), `blend` (the flip-and-blend post-process of the inference path); `_device` holds what they share."""
+intrinsics), `conv_ops` / `conv_routing` (the routed MFMA convolutions, the stem and the stride-2 layers included: one operator skeleton, one rule table), `metric_ops` (the validation depth metrics), `attention_ops` (the CADepth decoder's attention blocks), `fusion_ops` (the DiffNet decoder's glue), `subpixel` (the SuperDepth decoder's sub-pixel convolution), `blend` (the flip-and-blend post-process of the inference path); `_device` holds what they share."""
 from ._device import _stream, call
 from .attention_ops import channel_attention, se_gate
 from .blend import flip_blend, flip_blend_pyramid
 from .ddv_ops import ddv_head
 from .fusion_ops import relu_pad, up_cat_gate_pad
 from .class_ops import _ScaleMean, crop_resize, lane_shift_selftest, photo_error, recon_reduce, regression_loss, scale_mean, upsample_stack, view_synth
-from .conv_ops import conv3x3_mfma, conv3x3_same, conv3x3_thin, conv3x3_wide, conv7x7s2_stem
-from .conv_s2 import conv3x3_s2
+from .conv_ops import conv3x3_mfma, conv3x3_s2, conv3x3_same, conv3x3_thin, conv3x3_wide, conv7x7s2_stem
 from .conv_routing import _conv_route, conv_routes, set_conv_route
 from .geom_ops import intrinsics, inv_intrinsics, pose_matrices
 from .metric_ops import depth_metrics

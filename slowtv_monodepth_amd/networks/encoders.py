@@ -58,7 +58,7 @@ class BatchNormAct2d(nn.BatchNorm2d):
 def _conv3x3(conv: nn.Conv2d, x):
     """A block's 3x3 convolution on the GPU in fp32 (the fused BatchNorm's gate): the stride-1 ones through `conv3x3_same`, the stride-2 ones (a transition
     block's `conv1`) through `conv3x3_s2` — split-bf16 MFMA kernels with the zero padding inside them, or MIOpen, per operator and shape
-    (`conv_routing._conv_route`); anywhere else the module itself."""
+    (`conv_routing.serve`); anywhere else the module itself."""
     if (conv.stride in ((1, 1), (2, 2)) and BatchNormAct2d.fused_enabled and x.is_cuda and x.dtype == torch.float32 and conv.weight.dtype == torch.float32
             and not torch.is_autocast_enabled() and x.is_contiguous()):
         from .. import functional as HF

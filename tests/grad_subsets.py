@@ -223,7 +223,7 @@ def _conv(name, fn, wrapper, xs, ws, ys, kw):
 
 
 def _convs():
-    from slowtv_monodepth_amd.conv_ops import _Conv3x3Thin, _Conv3x3Wide, _Conv7x7s2Stem
+    from slowtv_monodepth_amd.conv_ops import _Conv3x3s2, _Conv3x3Thin, _Conv3x3Wide, _Conv7x7s2Stem
     pad = lambda d: ((d[0], d[1], d[3] + 2, d[4] + 2), (d[2], d[1], 3, 3), (d[0], d[2], d[3], d[4]))
     for dims in [(2, 16, 32, 5, 7), (2, 16, 16, 7, 70)]: _conv(f'conv3x3_mfma{dims}', _Conv3x3Wide, 'conv3x3_mfma', *pad(dims), {})      # (the second: the thin stage)
     _conv('conv3x3_wide(2, 16, 32, 5, 7)', _Conv3x3Wide, 'conv3x3_wide', *pad((2, 16, 32, 5, 7)), {})
@@ -231,6 +231,8 @@ def _convs():
     for B, C, CO, h, w in X.SAME[:2]: _conv(f'conv3x3_same{(B, C, CO, h, w)}', _Conv3x3Wide, 'conv3x3_same', (B, C, h, w), (CO, C, 3, 3), (B, CO, h, w), dict(padding=1))
     for B, C, H, W in X.STEM[:2]:
         _conv(f'conv7x7s2_stem{(B, C, H, W)}', _Conv7x7s2Stem, 'conv7x7s2_stem', (B, C, H, W), (64, C, 7, 7), (B, 64, (H - 1)//2 + 1, (W - 1)//2 + 1), dict(stride=2, padding=3))
+    for B, C, CO, H, W in [(2, 16, 32, 4, 6), (2, 32, 96, 9, 14)]:      # (shapes of test_gpu_conv_stride2_data.py: the smallest two-sample one; odd sizes with a wave past CO)
+        _conv(f'conv3x3_s2{(B, C, CO, H, W)}', _Conv3x3s2, 'conv3x3_s2', (B, C, H, W), (CO, C, 3, 3), (B, CO, (H - 1)//2 + 1, (W - 1)//2 + 1), dict(stride=2, padding=1))
 
 
 _convs()

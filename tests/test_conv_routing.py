@@ -1,7 +1,12 @@
-"""`conv_routing`: the dispatcher's branches with fake callables and an injected timer, and the static rule on the shapes the project runs.  No GPU."""
+"""`conv_routing`: the dispatcher's branches with fake callables and an injected timer, the one rule table's structure, and the static rule on the shapes the
+project runs and on the grid recorded before the three tables became one (tests/golden/make_golden_conv_skeleton.py).  No GPU."""
 import math
 
+import numpy as np
 import pytest
+
+import conv_skeleton_cases as K
+from conftest import GOLDEN
 
 from slowtv_monodepth_amd import _lib, conv_routing as R
 
@@ -149,7 +154,7 @@ def test_set_conv_route_clears_the_cache_and_rejects_unknown_modes(timer):
 def test_functional_keeps_its_surface():
     from slowtv_monodepth_amd import _device, conv_ops, functional as F
     assert F.set_conv_route is R.set_conv_route and F.conv_routes is R.conv_routes and F._conv_route is R._conv_route
-    for name in ('conv3x3_thin', 'conv3x3_mfma', 'conv3x3_wide', 'conv3x3_same', 'conv7x7s2_stem'): assert getattr(F, name) is getattr(conv_ops, name)
+    for name in ('conv3x3_thin', 'conv3x3_mfma', 'conv3x3_wide', 'conv3x3_same', 'conv7x7s2_stem', 'conv3x3_s2'): assert getattr(F, name) is getattr(conv_ops, name)
     assert F.call is conv_ops.call is _device.call and F._stream is conv_ops._stream is _device._stream     # one `_tls` behind all of them
     assert not hasattr(F, '_tls') and not hasattr(conv_ops, '_tls')
 
@@ -263,9 +268,32 @@ def test_static_rule_on_the_shapes_the_project_runs():
             assert R.static_rule(op, B, C, CO, h, w) is e, (op, B, C, CO, h, w)
 
 
-def test_static_rule_table_names_only_known_bounds_and_every_op_family():
-    assert set(R.STATIC_RULES) == set(R._FAMILY_OF_SUFFIX.values())
-    for family, ops in R.STATIC_RULES.items():
-        assert set(ops) == {op.partition('_')[0] for op in _OPS[family]}
-        for clauses in ops.values():
-            assert clauses and all(set(c) <= set(R._BOUNDS) for c in clauses)
+def test_rules_is_one_table_keyed_by_the_operator_names():
+    """Forward, data and weight gradient plain and as `_bf16` and `_z`; the stem and the stride-2 layers' forward and weight gradient; the stride-2 data
+    gradient: fourteen operators (the stem has no `data_s`), each under its own key of the one table."""
+    names = {k + s for k in ('fwd', 'data', 'wgt') for s in ('', '_bf16', '_z')} | {'fwd_s', 'wgt_s', 'fwd_s2', 'wgt_s2', 'data_t2'}
+    assert set(R.RULES) == names == set(K.OPS) == {op for ops in _OPS.values() for op in ops} | {'fwd_s2', 'wgt_s2', 'data_t2'} and len(names) == 14
+    for name in ('STATIC_RULES', 'STRIDED_RULES', 'TRANSPOSED_RULES', '_FAMILY_OF_SUFFIX'): assert not hasattr(R, name), name
+
+
+def test_every_clause_names_known_bounds_and_only_wgt_s2_has_none():
+    for op, clauses in R.RULES.items():
+        assert all(set(c) <= set(R._BOUNDS) for c in clauses), op
+        assert bool(clauses) is (op != 'wgt_s2'), op              # `wgt_s2`: never the kernels under capture (MIOpen's wins at every transition block)
+    assert not any(R.static_rule('wgt_s2', *p[1:]) for p in K.grid() if p[0] == 'wgt_s2')
+
+
+@pytest.mark.parametrize('op', K.NO_SUCH_OP)
+def test_static_rule_raises_for_an_operator_no_family_has(op):
+    assert set(K.NO_SUCH_OP) == {'data_s', 'data_s2', 'fwd_t2', 'fwd_s3'}
+    with pytest.raises(KeyError): R.static_rule(op, 12, 64, 128, 48, 160)
+
+
+def test_static_rule_equals_the_recording_on_every_grid_point():
+    """Every operator x batch size x channel pair x size of conv_skeleton_cases.grid() (the networks' layers at both resolutions and one step on either side of
+    every bound): the booleans `static_rule` returned before the tables were merged."""
+    with np.load(GOLDEN/'conv_skeleton_rules.npz') as z: n, served = int(z['n']), np.unpackbits(z['served'])
+    pts = K.grid()
+    assert len(pts) == n == len(K.OPS)*len(K.BATCHES)*len(K.CHANNELS)*len(K.sizes()) and {p[0] for p in pts} == set(R.RULES)
+    bad = [p for p, e in zip(pts, served[:n]) if R.static_rule(*p) is not bool(e)]
+    assert not bad, f'{len(bad)} of {n} decisions changed, the first: {bad[:5]}'

@@ -1,9 +1,8 @@
-"""Host side of the stride-2 3x3 convolutions' data gradient (`smd_conv3x3s2d_*`): the C prototypes, the static stand-in of its route, the size query."""
+"""Host side of the stride-2 3x3 convolutions' data gradient (`smd_conv3x3s2d_*`): the C prototypes, the size query, `may_serve` (the static stand-in of its
+route: test_conv_routing.py)."""
 import ctypes as C
 import re
 from pathlib import Path
-
-import pytest
 
 from slowtv_monodepth_amd import _lib, conv_routing as R
 
@@ -24,20 +23,6 @@ def test_header_prototypes_match_ctypes_and_the_abi_stays():
         assert res is (C.c_size_t if name.endswith('_bytes') else C.c_int)
         assert hasattr(_lib.lib, name)
     assert _lib.lib.smd_abi_version() == 8
-
-
-@pytest.mark.parametrize('dims', CFG2 + TALL + [(2, 16, 32, 4, 6)])
-def test_static_rule_reads_the_transposed_table(dims):
-    clauses = R.TRANSPOSED_RULES['t2']['data']
-    table = any(all(R._BOUNDS[name](v, *dims) for name, v in clause.items()) for clause in clauses)
-    assert R.static_rule('data_t2', *dims) is table
-
-
-def test_transposed_table_is_a_table_of_its_own():
-    assert set(R.TRANSPOSED_RULES) == {'t2'} and set(R.TRANSPOSED_RULES['t2']) == {'data'}
-    assert not set(R.TRANSPOSED_RULES) & (set(R.STRIDED_RULES) | set(R._FAMILY_OF_SUFFIX))
-    for clause in R.TRANSPOSED_RULES['t2']['data']: assert set(clause) <= set(R._BOUNDS)
-    with pytest.raises(KeyError): R.static_rule('fwd_t2', 12, 64, 128, 48, 160)
 
 
 def test_workspace_query_states_what_is_served():

@@ -1,38 +1,15 @@
-"""Host side of the stride-2 3x3 convolutions (`conv3x3_s2`): the static stand-in of its routes, the rule tables' key sets, the C prototypes."""
+"""Host side of the stride-2 3x3 convolutions (`conv3x3_s2`): the C prototypes, the size query, the Makefile (the static stand-in of its routes:
+test_conv_routing.py)."""
 import ctypes as C
 import re
 from pathlib import Path
 
-import pytest
-
-from slowtv_monodepth_amd import _lib, conv_routing as R
+from slowtv_monodepth_amd import _lib
 
 ROOT = Path(__file__).resolve().parents[1]
 # (B, C, CO, H, W) of the transition blocks' conv1, H x W its INPUT: cfg 2 (192 x 640; depth net b = 12, pose net b = 24) and the 384 x 640 counterparts
 CFG2 = [(b, c, 2*c, 48*64//c, 160*64//c) for b in (12, 24) for c in (64, 128, 256)]
 TALL = [(b, c, co, 2*h, w) for b, c, co, h, w in CFG2]
-
-
-def _table(kind, B, C, CO, h, w):
-    clauses = R.STRIDED_RULES['s2'][kind]
-    return any(all(R._BOUNDS[name](v, B, C, CO, h, w) for name, v in clause.items()) for clause in clauses)
-
-
-@pytest.mark.parametrize('dims', CFG2 + TALL)
-@pytest.mark.parametrize('kind', ['fwd', 'wgt'])
-def test_static_rule_reads_the_strided_table(kind, dims):
-    assert R.static_rule(kind + '_s2', *dims) is _table(kind, *dims)
-
-
-def test_strided_table_names_known_bounds_and_the_old_tables_keep_their_families():
-    assert set(R.STATIC_RULES) == set(R._FAMILY_OF_SUFFIX.values()) == {'padded', 'bf16', 'zpad', 'stem'}
-    assert set(R._FAMILY_OF_SUFFIX) == {'', 'bf16', 'z', 's'}
-    assert set(R.STRIDED_RULES) == {'s2'} and set(R.STRIDED_RULES['s2']) == {'fwd', 'wgt'}   # (the data gradient is ATen's: no route)
-    assert not set(R.STRIDED_RULES) & set(R._FAMILY_OF_SUFFIX)
-    for clauses in R.STRIDED_RULES['s2'].values():
-        for clause in clauses: assert set(clause) <= set(R._BOUNDS)
-    with pytest.raises(KeyError): R.static_rule('data_s2', 12, 64, 128, 48, 160)
-    with pytest.raises(KeyError): R.static_rule('fwd_s3', 12, 64, 128, 48, 160)
 
 
 def test_header_prototypes_match_ctypes_and_the_abi_stays():
